@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec of 64-step MaskBit-12bit sampling with CFG + conv-VQGAN decode.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch: per GPU, B=64 class-conditional images through
 the whole of sample() -- noise draw (reference RNG protocol), 64 x [2B-sequence LFQBert forward, CFG,
@@ -12,13 +12,21 @@ the uint8 images are all-gathered once per batch over RCCL.  Weights are random-
 architecture (304.8 M-param generator, 29.4 M-param decoder), labels synthetic; no checkpoint or
 dataset is available offline.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline     : dominant kernel (the fp16 MFMA GEMM family) algorithmic FLOPs / HIP-event duration
-  cpu_baseline : the CPU oracle (oracle/, a parity-checked port of the reference) timed on the host
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run only sets up, warms up, times the K steps (and writes the
+outputs with --dump-outputs); everything else is measured with --full only, after the timed region (the kernel timers and the clock sampler
+inside it), and is null / empty in a plain run:
+  roofline        : dominant kernel (the fp16 MFMA GEMM family) algorithmic FLOPs / HIP-event duration, kernels, telemetry
+  precision_modes : measured parity of the timed mode and the other precision modes; other_configs: the other configurations
+  cpu_baseline    : the CPU oracle (oracle/, a parity-checked port of the reference) timed on the host
+
+--dump-outputs DIR writes what the last timed step returned -- the uint8 images (all ranks', gathered) and the token codes -- as
+DIR/images.npy and DIR/codes.npy in float32 (at most DUMP_BYTES in all: beyond that a fixed, seeded sample of the images, listed in
+DIR/rows.npy).  Weights, labels and noise depend only on the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -44,6 +52,7 @@ DEC_BYTES_IDEAL = 426e6                  # per decoded image: 213.06 M elements 
 HBM_PEAK_GBS = 8000.0
 PROF_EVERY = 8                           # HIP-event timing of every 8th forward of the timed region (forwards 4, 12, .. 60 of a 64-step run: all guided)
 GEN_SEED, HEAD_GAIN, TOK_SEED = 100, 12.0, 200   # maskbit_amd/synth.py: the same synthetic checkpoints the golden fixtures were made with
+DUMP_BYTES = 64 * 10**6                  # --dump-outputs: the arrays' float32 payload in all
 
 
 class Cfg(dict):
@@ -291,6 +300,28 @@ def variant_configs(dev):
     return out
 
 
+def dump_outputs(outdir: str, arrays: dict, limit: int = DUMP_BYTES, seed: int = 0) -> dict:
+    """Write `arrays` (tensors sharing the leading sample axis) as outdir/<name>.npy in float32.  If together they exceed `limit` bytes, the same
+    fixed, seeded sample of rows is written of every array, and the row indices as outdir/rows.npy (float64).  -> {name: shape written}."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrs.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrs.items()}
+    n = n.pop()
+    row_bytes = sum(4 * a[0].size for a in arrs.values())
+    budget = limit - 1024                                    # the .npy headers
+    rows = None
+    if n * row_bytes > budget:
+        k = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(outdir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    return {name: list(a.shape) for name, a in arrs.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,11 +332,21 @@ def main():
                     help="precision mode of the TIMED region (LFQBert.precision): strict (default; the product default: differential guidance + MX-fp4 "
                          "correction mini-tiles for the weights' fp16 rounding on every trunk GEMM + hi/lo head weights: 5.5e-4 token mismatch over three "
                          "reference runs), diff (differential guidance alone: faster, AT the 1e-3 bound) or single fp16 (independent streams: 1.4e-3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: HIP-event kernel timing and roofline, clock / power telemetry, parity and the "
+                         "other precision modes, the other configurations, the rocprofv3 --pmc traffic sub-passes and the CPU baseline (the --no-* "
+                         "options below switch single parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's images and token codes as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="skip the HIP-event kernel timing (roofline becomes null)")
     ap.add_argument("--no-modes", action="store_true", help="skip the extra (untimed-region) measurements: parity replay and the other precision mode")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc sub-passes that measure roofline.traffic (N = 1 only; about a minute)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                   # a plain run: set-up, warm-up, the timed steps, the outputs and the line -- nothing else
+        args.no_cpu_baseline = args.no_prof = args.no_modes = args.no_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -355,15 +396,15 @@ def main():
     def one_batch(i: int):
         labels = ((torch.arange(B) + (rank * B + i * world * B)) * 37 % 1000).to(dev)
         # the product's own path (sample() / generate_uint8()): noise drawn chunk by chunk in the reference's generator order, overlapped with the loop
-        _, u8, _, _ = run_chunked(gen, tok, labels, plan, SAMPLER["randomize_temperature"], want_steps=False, want_image=False, want_u8=True)
+        _, u8, _, codes = run_chunked(gen, tok, labels, plan, SAMPLER["randomize_temperature"], want_steps=False, want_image=False, want_u8=True)
         if world == 1:
-            return u8
+            return u8, codes
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         out_ = gather_images(u8, equal=True)            # every rank holds B images: one collective per batch, no size exchange
         e1.record()
         gather_ev.append((e0, e1))
-        return out_
+        return out_, codes
 
     def fence():
         torch.cuda.synchronize()
@@ -377,14 +418,17 @@ def main():
     gather_ev.clear()
     if not args.no_prof:
         _lib.prof_enable(True, every=PROF_EVERY)        # sampled: the event pairs themselves cost 3-5 % when every launch carries them
-    from maskbit_amd.telemetry import ClockSampler
-    with ClockSampler(dev_index) as clocks:             # shader clock / socket power while the timed region runs (the part is power-capped: boxes differ)
+    clocks = None
+    if args.full:
+        from maskbit_amd.telemetry import ClockSampler
+        clocks = ClockSampler(dev_index)                # shader clock / socket power while the timed region runs (the part is power-capped: boxes differ)
+    with clocks or contextlib.nullcontext():
         t0 = time.perf_counter()
         for i in range(args.steps):
-            out = one_batch(args.warmup + i)
+            out, codes = one_batch(args.warmup + i)
         fence()
         elapsed = time.perf_counter() - t0
-    telemetry = clocks.summary()
+    telemetry = clocks.summary() if clocks is not None else None
     prof = {}
     if not args.no_prof:
         prof = _lib.prof_read()
@@ -397,6 +441,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, gather_ms = float(t[0].item()), float(t[1].item())
     assert out.shape[0] == B * world and out.dtype == torch.uint8
+    if args.dump_outputs:
+        # what the last timed step returned: the images every rank's caller receives and the token codes (gathered here, outside the timed region)
+        all_codes = gather_images(codes, equal=True) if world > 1 else codes
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"images": out, "codes": all_codes})
     # Outside the timed region, N = 1 only: (1) the MEASURED token mismatch of the timed mode against the reference's own full-size run,
     # (2) the same workload and the same parity measurement in the other precision mode, one batch.
     modes = None
@@ -518,8 +567,9 @@ def main():
             "other_configs": others,
             "ranks_seen": ranks_seen if world > 1 else 1, "backend": dist.get_backend() if world > 1 else None,
             "gather_ms": gather_ms,       # N > 1: the batch's one all-gather of uint8 images incl. the wait for the slowest rank (max over ranks); part of ms_per_step
-            "kernels_note": f"HIP events on the launch stream inside the timed region; generator kernels sampled on every {PROF_EVERY}th guided forward "
-                            f"(names as they are) and every {PROF_EVERY}th plain forward (the zero-scale steps: names + '.plain'), counted separately",
+            "kernels_note": (f"HIP events on the launch stream inside the timed region; generator kernels sampled on every {PROF_EVERY}th guided forward "
+                             f"(names as they are) and every {PROF_EVERY}th plain forward (the zero-scale steps: names + '.plain'), counted separately")
+                            if prof else None,
         }
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -284,3 +284,25 @@ def test_precision_knob_resolution(monkeypatch):
     assert "MB_PREC_FP16 = 0, MB_PREC_DIFF = 1, MB_PREC_WCORR = 2, MB_PREC_ALO = 3" in hdr
     assert [n for n, _ in _lib.GenCfg._fields_][-3:] == ["prenorm", "embed_tables", "precision"]
     assert not re.search(r"\b(weight_split|act_split|cfg_pair)\b", hdr)
+
+
+def test_bench_dump_outputs_float32_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 arrays in full below the size limit; above it the same fixed, seeded rows of every array (and their indices)."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))   # bench sets it at import; restored afterwards
+    import bench
+    g = torch.Generator().manual_seed(0)
+    img = torch.randint(0, 256, (10, 8, 8, 3), dtype=torch.uint8, generator=g)
+    codes = torch.randint(0, 4096, (10, 16), dtype=torch.int64, generator=g)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"images": img, "codes": codes}) == {"images": [10, 8, 8, 3], "codes": [10, 16]}
+    a = np.load(tmp_path / "a" / "images.npy")
+    assert a.dtype == np.float32 and (a == img.numpy()).all() and (np.load(tmp_path / "a" / "codes.npy") == codes.numpy()).all()
+    assert not (tmp_path / "a" / "rows.npy").exists()
+    row = 4 * (8 * 8 * 3 + 16)
+    limit = 1024 + 4 * (row + 8)
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), {"images": img, "codes": codes}, limit=limit)["images"] == [4, 8, 8, 3]
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert rows.dtype == np.float64 and (rows == np.load(tmp_path / "c" / "rows.npy")).all() and len(set(rows.tolist())) == 4
+    r = rows.astype(np.int64)
+    assert (np.load(tmp_path / "b" / "images.npy") == img.numpy()[r]).all() and (np.load(tmp_path / "b" / "codes.npy") == codes.numpy()[r]).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit

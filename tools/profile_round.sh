@@ -13,7 +13,7 @@ export PAIR_ONE_MINI=1
 cd /tmp
 # (round 6: the bench keeps its own HIP-event kernel timing on under the tracer, so that ONE run carries both figures of the dominant kernel: the line's
 #  roofline.avg_launch_us and the trace's average duration -- boxes sustain different clocks, two runs on two boxes do not compare)
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-modes --no-traffic > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-modes --no-traffic > $OUT/bench_under_rocprof.log 2>&1
 if [ -n "${PROFILE_ONLY_KT:-}" ]; then
   cd $ROOT
   DB=$(find $OUT/kt -name "*.db" | head -1)
