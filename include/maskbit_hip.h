@@ -144,6 +144,20 @@ int mb_dec_saturation_count(mb_dec* d, unsigned* count, int reset, mb_stream str
  * zq (+-1 latent, fp32 [B,K,h,w]) and zraw (pre-sign encoder output) may be NULL.  Needs build_encoder = 1. */
 int mb_enc_encode(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, int B, mb_stream stream);
 
+/* ---- lookup (VQ) tokenizer: ConvVQModel with quantizer_type "lookup" (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119) ---------- *
+ * A handle with a codebook of codebook_size (2 .. 65 536) entries of token_size (1 .. 256) channels; l2_normalize = use_l2_normalisation
+ * (z and the codebook rows through F.normalize).  The codebook is the checkpoint entry quantize.embedding.weight [codebook_size, token_size],
+ * loaded through mb_dec_load (which prepares the fp32 rows, normalised if required, and their squared norms); decoding or encoding before it is
+ * loaded is an error.  On such a handle mb_dec_decode takes codebook indices (clamped to [0, codebook_size) on the device) and mb_enc_encode
+ * behaves as mb_enc_encode_vq with row_dist = NULL. */
+int mb_dec_create_vq(const mb_dec_cfg* cfg, int codebook_size, int l2_normalize, int max_batch, mb_dec** out);
+/* ConvVQModel.decode (conv_vqgan.py:85-96) of any float latent z_nchw fp32 [B, token_size, h, w]; VQ handles only. */
+int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream);
+/* ConvVQModel.encode with the lookup quantizer: img fp32 [B,C,H,W] -> indices int64 [B, h*w] (nearest entry, ties to the lowest index), and
+ * optionally zq fp32 [B,K,h,w] (the selected rows), zraw fp32 [B,K,h,w] (encoder output before normalisation) and row_dist fp32 [B*h*w] =
+ * sum_k (z_k - e_idx,k)^2 over the (possibly normalised) vectors. */
+int mb_enc_encode_vq(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, mb_stream stream);
+
 /* ---- whole loop: modeling.modules.sample, sampling.py:55-136 ------------------------------- *
  * Runs num_steps x (forward [+CFG], step) then combine (factorization.py:7-24) + decode.
  * exp_noise [steps, B*n*m, C] and conf_noise [steps, B, n, m] (= gumbel * randomize_temperature *

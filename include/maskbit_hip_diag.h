@@ -74,6 +74,11 @@ int mb_gen_set_alo(mb_gen* g, int from_layer, int gemm_mask);
  * n = the CUs the following launches should size their grids for, 0 = the device's count (default).  Process-wide, not thread-safe. */
 int mb_set_cu_count(int n);
 
+/* The lookup quantizer's search on caller buffers (vq.hip): z fp32 [N, K], codebook fp32 [C, K] (K <= 256, 2 <= C <= 65 536), l2 = normalise both;
+ * idx int64 [N] = argmin_j ||z - e_j||^2 (ties to the lowest index), dist fp32 [N] (may be NULL) = that squared distance; splits = codebook splits
+ * across workgroups (0 = automatic; clamped to [1, min(64, C / 64 rounded up)]). */
+int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,14 @@ The encoder half (image -> tokens; stage-I plumbing outside the sampling hot pat
 next-1) runs on the same kernels through ``mb_enc_encode``: ``encode(x) -> (z_quantized,
 result_dict)`` with ``min_encoding_indices`` and ``forward(x) -> (reconstruction, result_dict)``
 (conv_vqgan.py:70-83,114-127), inference only.
+
+Both quantizers of the reference are built: ``quantizer_type="lookup-free"`` (LFQ, the MaskBit tokenizers) and ``"lookup"``
+(``SimpleVectorizer``, modeling/quantizer/quantizer.py: the VQGAN+ and MaskGIT tokenizers, a learned codebook
+``quantize.embedding.weight`` [codebook_size, token_size], optionally L2-normalised).  The lookup encoder ends in the fused
+nearest-codeword search of vq.hip (``mb_enc_encode_vq``), its decoder input is the codebook row gather.  ``legacy=True``
+(``ConvDecoderLegacy``, modeling/modules/autoencoder.py:289-353: the MaskGIT checkpoint layout) is a naming switch only: the
+same decoder with ``decoder.up.{i}`` holding level ``i`` (0 = finest) and ``num_res_blocks`` everywhere; its keys are
+remapped onto the canonical layout when the engine is loaded.
 """
 from __future__ import annotations
 
@@ -83,14 +91,30 @@ def _tokenizer_specs(K, hc, mult, R, nrb_enc, nrb_dec, nch, sample_with_conv) ->
     return s
 
 
+def _legacy_level(key: str, num_resolutions: int) -> str:
+    """``decoder.up.{i}.*`` of one layout -> the other (level i <-> stage R-1-i; the map is its own inverse); other keys unchanged."""
+    if not key.startswith("decoder.up."):
+        return key
+    rest = key[len("decoder.up."):]
+    i, tail = rest.split(".", 1)
+    return f"decoder.up.{num_resolutions - 1 - int(i)}.{tail}"
+
+
+def legacy_to_canonical(state_dict, num_resolutions: int):
+    """A ``legacy=True`` (ConvDecoderLegacy) state dict with its keys renamed to the ``legacy=False`` layout (same tensors)."""
+    return {_legacy_level(k, num_resolutions): v for k, v in state_dict.items()}
+
+
 class ConvVQModel(BaseModel):
     def __init__(self, config, legacy: bool = False, finetune_decoder: bool = False):
         super().__init__()
-        if legacy:
-            raise NotImplementedError("legacy decoder layout (MaskGIT/older weights) is not paired with any MaskBit generator; not built")
         qt = _cfg_get(config, "quantizer_type", "lookup-free")
-        if qt != "lookup-free":
-            raise NotImplementedError(f"quantizer_type={qt!r}: only the lookup-free (LFQ) tokenizer is on the MaskBit path")
+        if qt == "vae":
+            raise NotImplementedError("quantizer_type='vae' is not supported (the reference does not implement it either)")
+        if qt not in ("lookup-free", "lookup"):
+            raise NotImplementedError(f"quantizer_type={qt!r}: only the lookup-free (LFQ) and lookup (VQ) tokenizers are built")
+        self.quantizer_type = qt
+        self.legacy = bool(legacy)
         self.config = config
         self.finetune_decoder = finetune_decoder
         self.token_size = int(config.token_size)
@@ -98,17 +122,34 @@ class ConvVQModel(BaseModel):
         self.channel_mult = tuple(int(v) for v in config.channel_mult)
         self.num_resolutions = int(config.num_resolutions)
         self.num_res_blocks = int(config.num_res_blocks)
-        self.num_res_blocks_decoder = int(_cfg_get(config, "num_res_blocks_decoder", self.num_res_blocks))
+        self.num_res_blocks_decoder = self.num_res_blocks if self.legacy else int(_cfg_get(config, "num_res_blocks_decoder", self.num_res_blocks))
         self.num_channels = int(_cfg_get(config, "num_channels", 3))
         self.sample_with_conv = bool(_cfg_get(config, "sample_with_conv", False))
-        self._build(_tokenizer_specs(self.token_size, self.hidden_channels, self.channel_mult, self.num_resolutions,
-                                     self.num_res_blocks, self.num_res_blocks_decoder, self.num_channels,
-                                     bool(_cfg_get(config, "sample_with_conv", False))))
+        if qt == "lookup":
+            self.codebook_size = int(config.codebook_size)
+            if not 1 <= self.token_size <= 256:
+                raise ValueError(f"token_size={self.token_size}: the lookup tokenizer supports 1 .. 256 channels")
+            if not 2 <= self.codebook_size <= 65536:
+                raise ValueError(f"codebook_size={self.codebook_size}: the lookup tokenizer supports 2 .. 65536 entries")
+            self.use_l2_normalisation = bool(_cfg_get(config, "use_l2_normalisation", False))
+            self.commitment_cost = float(_cfg_get(config, "commitment_cost", 0.25))
+        else:
+            self.codebook_size = 2 ** self.token_size
+        specs = _tokenizer_specs(self.token_size, self.hidden_channels, self.channel_mult, self.num_resolutions,
+                                 self.num_res_blocks, self.num_res_blocks_decoder, self.num_channels,
+                                 bool(_cfg_get(config, "sample_with_conv", False)))
+        if self.legacy:
+            specs = [(_legacy_level(k, self.num_resolutions), shape, kind) for k, shape, kind in specs]
+        self._build(specs)
+        self._latent_size = 16
+        if qt == "lookup":                                                                  # quantizer.py:36-37
+            self._attach("quantize.embedding.weight",
+                         torch.empty(self.codebook_size, self.token_size).uniform_(-1.0 / self.codebook_size, 1.0 / self.codebook_size))
+            return
         weights = (2 ** torch.arange(self.token_size)).to(torch.int32)
         self._attach("quantize.bits_to_indices", weights, buffer=True)                      # lookup_free.py:38-39
         codes = torch.arange(2 ** self.token_size)
         self._attach("quantize.codebook", ((codes[:, None] & weights) != 0).float() * 2.0 - 1.0, buffer=True)   # :41-43
-        self._latent_size = 16
 
     def get_last_layer(self):
         return self.decoder.conv_out.weight
@@ -125,6 +166,10 @@ class ConvVQModel(BaseModel):
         cfg.build_encoder = 1
         cfg.enc_res_blocks = self.num_res_blocks
         h = C.c_void_p()
+        if self.quantizer_type == "lookup":
+            _lib.check(_lib.load().mb_dec_create_vq(C.byref(cfg), self.codebook_size, 1 if self.use_l2_normalisation else 0, capacity, C.byref(h)),
+                       "mb_dec_create_vq")
+            return h
         _lib.check(_lib.load().mb_dec_create(C.byref(cfg), capacity, C.byref(h)), "mb_dec_create")
         return h
 
@@ -132,6 +177,8 @@ class ConvVQModel(BaseModel):
         _lib.load().mb_dec_destroy(h)
 
     def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
+        if self.legacy:
+            key = _legacy_level(key, self.num_resolutions)                  # the engine speaks the canonical layout
         shape = (C.c_int64 * t.dim())(*t.shape)
         _lib.check(_lib.load().mb_dec_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_dec_load({key})")
 
@@ -162,7 +209,16 @@ class ConvVQModel(BaseModel):
     def decode_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
         """tokens [b, n] of any numeric dtype (the sampler hands float32, factorization.py:19) -> image."""
         dev = self._require_cuda("decode_tokens")
+        self._check_codes(tokens)
         return self._decode_codes(tokens.to(dev).long().contiguous())
+
+    def _check_codes(self, tokens: torch.Tensor) -> None:
+        """Host-resident codes of a lookup tokenizer are range-checked (nn.Embedding raises IndexError, quantizer.py:115); device-resident
+        ones are clamped to [0, codebook_size) in the gather kernel, with no host synchronisation."""
+        if self.quantizer_type == "lookup" and tokens.device.type == "cpu" and tokens.numel():
+            t = tokens.long()
+            if int(t.min()) < 0 or int(t.max()) >= self.codebook_size:
+                raise IndexError(f"code outside [0, {self.codebook_size})")
 
     def saturation_count(self, reset: bool = True) -> int:
         """Number of 4-channel activation groups the engine clamped at the fp16 range (+-65504) since the last reset, over every conv layer
@@ -182,15 +238,19 @@ class ConvVQModel(BaseModel):
     def decode_tokens_uint8(self, tokens: torch.Tensor):
         """-> (image fp32 NCHW, uint8 NHWC = trunc(clamp(x,0,1)*255)) in one pass (eval_maskbit.py:134-135 fused)."""
         dev = self._require_cuda("decode_tokens")
+        self._check_codes(tokens)
         return self._decode_codes(tokens.to(dev).long().contiguous(), want_u8=True)
 
     @torch.no_grad()
     def decode(self, z_quantized: torch.Tensor) -> torch.Tensor:
-        """z [b, K, h, w] in {-1,+1} -> image.  LFQ latents are exactly the bit pattern of a code, so the
-        latent is re-packed to codes (sign -> bit, LSB first) and decoded through the token path."""
+        """z [b, K, h, w] -> image.  Lookup tokenizer: any float latent (ConvDecoder.forward on it, ``mb_dec_decode_latent``).
+        LFQ: z in {-1,+1} only; LFQ latents are exactly the bit pattern of a code, so the latent is re-packed to codes (sign -> bit,
+        LSB first) and decoded through the token path."""
         dev = self._require_cuda("decode")
         if z_quantized.dim() != 4 or z_quantized.shape[1] != self.token_size:
             raise ValueError(f"decode expects [b, {self.token_size}, h, w], got {tuple(z_quantized.shape)}")
+        if self.quantizer_type == "lookup":
+            return self._decode_latent(z_quantized)
         z = z_quantized.to(dev)
         if not bool(((z == 1) | (z == -1)).all()):
             raise ValueError("decode(): the HIP decoder takes quantized LFQ latents (+-1) only")
@@ -198,8 +258,22 @@ class ConvVQModel(BaseModel):
         codes = ((z > 0).long() * w).sum(1).reshape(z.shape[0], -1)
         return self._decode_codes(codes.contiguous())
 
+    def _decode_latent(self, z_quantized: torch.Tensor) -> torch.Tensor:
+        dev = self._require_cuda("decode")
+        b, _, hh, ww = z_quantized.shape
+        if hh != ww or hh % 16:
+            raise ValueError(f"decode expects a square latent grid with a side that is a multiple of 16, got {hh}x{ww}")
+        z = z_quantized.to(device=dev, dtype=torch.float32).contiguous()
+        res = hh << (self.num_resolutions - 1)
+        img = torch.empty((b, self.num_channels, res, res), dtype=torch.float32, device=dev)
+        h = self.engine(b, hh)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mb_dec_decode_latent(h, z.data_ptr(), img.data_ptr(), None, b, torch.cuda.current_stream().cuda_stream),
+                       "mb_dec_decode_latent")
+        return img
+
     @torch.no_grad()
-    def _encode(self, x: torch.Tensor, want_raw: bool = False):
+    def _encode(self, x: torch.Tensor, want_raw: bool = False, want_dist: bool = False):
         dev = self._require_cuda("encode")
         if x.dim() != 4 or x.shape[1] != self.num_channels:
             raise ValueError(f"encode expects [b, {self.num_channels}, H, W], got {tuple(x.shape)}")
@@ -213,6 +287,13 @@ class ConvVQModel(BaseModel):
         zq = torch.empty((b, self.token_size, side, side), dtype=torch.float32, device=dev)
         zraw = torch.empty_like(zq) if want_raw else None
         h = self.engine(b, side)
+        if self.quantizer_type == "lookup":
+            dist = torch.empty((b, side, side), dtype=torch.float32, device=dev) if want_dist else None
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().mb_enc_encode_vq(h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), zraw.data_ptr() if want_raw else None,
+                                                        dist.data_ptr() if want_dist else None, b, torch.cuda.current_stream().cuda_stream),
+                           "mb_enc_encode_vq")
+            return (zq, idx, zraw, dist) if want_dist else (zq, idx, zraw)
         with torch.cuda.device(dev):
             _lib.check(_lib.load().mb_enc_encode(h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), zraw.data_ptr() if want_raw else None, b,
                                                  torch.cuda.current_stream().cuda_stream), "mb_enc_encode")
@@ -221,7 +302,17 @@ class ConvVQModel(BaseModel):
     def encode(self, x: torch.Tensor):
         """ConvVQModel.encode (conv_vqgan.py:70-83): image -> (z_quantized [b,K,h,w] in {-1,+1}, result_dict) with
         ``min_encoding_indices`` [b,h,w] (lookup_free.py:57-95).  Inference only: the quantizer losses are returned as zeros
-        except the commitment term, which needs the pre-sign latent and is not computed on this path."""
+        except the commitment term, which needs the pre-sign latent and is not computed on this path.
+        Lookup tokenizer (SimpleVectorizer.forward, quantizer.py:45-103, eval mode): z_quantized = the selected codebook rows (L2-normalised
+        when configured); codebook_loss = mean((zq - z)^2) from the kernel's per-row squared distances, commitment_loss = commitment_cost *
+        codebook_loss, quantizer_loss their sum; the entropy terms are zero (the reference computes them only in training)."""
+        if self.quantizer_type == "lookup":
+            zq, idx, _, dist = self._encode(x, want_dist=True)
+            codebook_loss = (dist.sum() / float(dist.numel() * self.token_size)).reshape(())
+            commitment_loss = self.commitment_cost * codebook_loss
+            zero = torch.zeros((), device=zq.device)
+            return zq, dict(quantizer_loss=commitment_loss + codebook_loss, commitment_loss=commitment_loss, codebook_loss=codebook_loss,
+                            entropy_loss=zero, per_sample_entropy=zero, avg_entropy=zero, min_encoding_indices=idx)
         zq, idx, _ = self._encode(x)
         zero = torch.zeros((), device=zq.device)
         return zq, dict(quantizer_loss=zero, commitment_loss=zero, entropy_loss=zero, per_sample_entropy=zero, avg_entropy=zero,

@@ -22,6 +22,7 @@
 
 #include "mb_decoder.h"
 #include "mb_kernels.h"
+#include "mb_vq.h"
 
 namespace mb {
 
@@ -504,7 +505,13 @@ struct mb_dec {
   std::vector<mb::ResBlock> e_mid;
   std::vector<mb::Stage> e_down;
   h16* buf[3] = {nullptr, nullptr, nullptr};
-  h16* z = nullptr;
+  h16* z = nullptr;              // decoder input latent, [max_batch * latent^2][conv_in.cin_pad]
+  // lookup quantizer (mb_dec_create_vq; SimpleVectorizer, modeling/quantizer/quantizer.py): the prepared codebook and the search buffers
+  bool vq = false, cb_loaded = false;
+  mb::VqCodebook q;
+  float* vq_zT = nullptr;        // [Kp/4][Npad][4] rows of the encoder output (normalised when l2)
+  float* vq_ps = nullptr;        // [VQ_SPLIT_MAX][Npad] per-split best score ...
+  int* vq_pi = nullptr;          // ... and its entry
   unsigned* sat = nullptr;  // device counter: fp16 clamps in the conv epilogues since the last read
   float* gn_part = nullptr;
   float2* gn_ss = nullptr;
@@ -621,11 +628,14 @@ bool find_norm(Norm& nm, const std::string& n, float** dst) {
 }
 }  // namespace
 
-mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err) {
+mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err, int codebook_size, int l2_normalize) {
   const int R = cfg.num_resolutions;
+  const bool vq = codebook_size > 0;
   if (R < 1 || R > 7) { err = "num_resolutions out of range"; return nullptr; }
   if (cfg.hidden_channels % 64) { err = "hidden_channels must be a multiple of 64 for the HIP decoder"; return nullptr; }
-  if (cfg.token_size > CK || cfg.token_size < 1) { err = "token_size must be in [1, 64]"; return nullptr; }
+  if (!vq && (cfg.token_size > CK || cfg.token_size < 1)) { err = "token_size must be in [1, 64]"; return nullptr; }
+  if (vq && (cfg.token_size > 256 || cfg.token_size < 1)) { err = "token_size must be in [1, 256]"; return nullptr; }
+  if (vq && (codebook_size < 2 || codebook_size > 65536)) { err = "codebook_size must be in [2, 65536]"; return nullptr; }
   if (cfg.latent_size % 16) { err = "latent_size must be a multiple of 16"; return nullptr; }
   if (cfg.num_channels > 4) { err = "num_channels > 4 unsupported"; return nullptr; }
   mb_dec* d = new mb_dec();
@@ -702,9 +712,19 @@ mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err) {
     d->has_enc = ok;
   }
   for (int i = 0; ok && i < 3; ++i) ok = dalloc(d, &d->buf[i], (size_t)max_batch * max_elems, err);
-  ok = ok && dalloc(d, &d->z, (size_t)max_batch * cfg.latent_size * cfg.latent_size * CK, err) &&
+  const size_t nlat = (size_t)max_batch * cfg.latent_size * cfg.latent_size;
+  ok = ok && dalloc(d, &d->z, nlat * d->conv_in.cin_pad, err) &&
        dalloc(d, &d->gn_part, (size_t)max_batch * std::max(GN_MAXCHUNK, (d->out_res / TH8) * (d->out_res / TW)) * 64, err) &&
        dalloc(d, &d->gn_ss, (size_t)max_batch * 4096, err);
+  if (ok && vq) {
+    VqCodebook& q = d->q;
+    q.C = codebook_size; q.K = cfg.token_size; q.Kp = vq_kp(q.K); q.Cpad = vq_cpad(q.C); q.l2 = l2_normalize ? 1 : 0;
+    const size_t npad = (size_t)vq_npad((int)nlat);
+    ok = dalloc(d, &q.cb, (size_t)q.C * q.K, err) && dalloc(d, &q.cbT, (size_t)q.Kp * q.Cpad, err) && dalloc(d, &q.cbn, (size_t)q.Cpad, err) &&
+         dalloc(d, &d->vq_zT, (size_t)q.Kp * npad, err) && dalloc(d, &d->vq_ps, VQ_SPLIT_MAX * npad, err) &&
+         dalloc(d, &d->vq_pi, VQ_SPLIT_MAX * npad, err);
+    d->vq = ok;
+  }
   if (!ok) { dec_destroy(d); return nullptr; }
   return d;
 }
@@ -717,6 +737,12 @@ void dec_destroy(mb_dec* d) {
 
 int dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shape, int ndim, hipStream_t s, std::string& err) {
   const std::string n(name);
+  if (d->vq && n == "quantize.embedding.weight") {                               // SimpleVectorizer.embedding [C, K]
+    if (ndim != 2 || shape[0] != d->q.C || shape[1] != d->q.K) { err = n + ": expected [codebook_size, token_size]"; return -4; }
+    vq_prep_codebook(d->q, data, s);
+    d->cb_loaded = true;
+    return 0;
+  }
   if (n.rfind("quantize.", 0) == 0) return 0;                                    // derived buffers
   if (n.rfind("encoder.", 0) == 0 && !d->has_enc) return 0;                       // encode half not built in this engine
   size_t numel = 1;
@@ -760,13 +786,10 @@ int dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shap
   return -2;
 }
 
-int dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s, std::string& err) {
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
-  const mb_dec_cfg& c = d->c;
-  int res = c.latent_size;
-  const size_t npix = (size_t)B * res * res;
-  hipLaunchKernelGGL(latent_kernel, dim3((unsigned)std::min<size_t>(2048, (npix * CK + 255) / 256)), dim3(256), 0, s,
-                     tokens, d->z, npix, c.token_size);
+namespace {
+// ConvDecoder.forward (autoencoder.py:399-423) from the latent in d->z
+void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s) {
+  int res = d->c.latent_size;
   launch_conv(s, d, d->conv_in, d->z, nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
   for (auto& rb : d->mid) xi = run_block(s, d, rb, xi, B, res, res);
@@ -781,6 +804,30 @@ int dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_n
   }
   launch_gn(s, d, d->norm_out, d->buf[xi], B, res * res);
   launch_conv(s, d, d->conv_out, d->buf[xi], d->gn_ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, res, res, true);
+}
+}  // namespace
+
+int dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s, std::string& err) {
+  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
+  const mb_dec_cfg& c = d->c;
+  const size_t npix = (size_t)B * c.latent_size * c.latent_size;
+  if (d->vq) {                                        // SimpleVectorizer.get_codebook_entry (quantizer.py:105-119): codebook rows
+    if (!d->cb_loaded) { err = "the codebook (quantize.embedding.weight) is not loaded"; return -1; }
+    vq_gather(d->q, tokens, npix, d->z, d->conv_in.cin_pad, d->sat, s);
+  } else {
+    hipLaunchKernelGGL(latent_kernel, dim3((unsigned)std::min<size_t>(2048, (npix * CK + 255) / 256)), dim3(256), 0, s,
+                       tokens, d->z, npix, c.token_size);
+  }
+  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
+  return 0;
+}
+
+int dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s, std::string& err) {
+  if (!d->vq) { err = "decode of a float latent needs a lookup (VQ) handle"; return -1; }
+  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
+  const int hw = d->c.latent_size * d->c.latent_size;
+  vq_pack_latent(z_nchw, B, d->c.token_size, hw, d->z, d->conv_in.cin_pad, d->sat, s);
+  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
   return 0;
 }
 
@@ -791,9 +838,9 @@ int dec_saturation_count(mb_dec* d, unsigned* count, bool reset, hipStream_t s) 
   return hipStreamSynchronize(s) == hipSuccess ? 0 : -10;
 }
 
-int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, int B, hipStream_t s, std::string& err) {
-  if (!d->has_enc) { err = "this engine was created without the encoder half (mb_dec_cfg.build_encoder)"; return -1; }
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
+namespace {
+// ConvEncoder.forward (autoencoder.py:264-286) -> index of the buffer holding z (fp16 NHWC, e_conv_out.cout channels per pixel); *res_out = its side
+int encode_to_z(mb_dec* d, const float* img, int B, hipStream_t s, int* res_out) {
   const mb_dec_cfg& c = d->c;
   int res = d->out_res;
   const size_t npix = (size_t)B * res * res;
@@ -825,6 +872,31 @@ int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* 
   launch_gn(s, d, d->e_norm_out, d->buf[xi], B, res * res);
   const int t = (xi + 1) % 3;
   launch_conv(s, d, d->e_conv_out, d->buf[xi], d->gn_ss, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
+  *res_out = res;
+  return t;
+}
+}  // namespace
+
+int enc_encode_vq(mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, hipStream_t s, std::string& err) {
+  if (!d->has_enc) { err = "this engine was created without the encoder half (mb_dec_cfg.build_encoder)"; return -1; }
+  if (!d->vq) { err = "not a lookup (VQ) handle"; return -1; }
+  if (!d->cb_loaded) { err = "the codebook (quantize.embedding.weight) is not loaded"; return -1; }
+  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
+  int res = 0;
+  const int t = encode_to_z(d, img, B, s, &res);
+  const int hw = res * res, N = B * hw;
+  vq_prep_rows(d->q, d->buf[t], d->e_conv_out.cout, nullptr, N, hw, d->vq_zT, zraw, s);
+  vq_search(d->q, d->vq_zT, N, hw, vq_splits(d->q, N, 0), d->vq_ps, d->vq_pi, indices, zq, row_dist, s);
+  return 0;
+}
+
+int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, int B, hipStream_t s, std::string& err) {
+  if (d->vq) return enc_encode_vq(d, img, indices, zq, zraw, nullptr, B, s, err);
+  if (!d->has_enc) { err = "this engine was created without the encoder half (mb_dec_cfg.build_encoder)"; return -1; }
+  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
+  const mb_dec_cfg& c = d->c;
+  int res = 0;
+  const int t = encode_to_z(d, img, B, s, &res);
   const size_t np = (size_t)B * res * res;
   hipLaunchKernelGGL(lfq_kernel, dim3((unsigned)std::min<size_t>(1024, (np + 255) / 256)), dim3(256), 0, s, d->buf[t], indices, zq, zraw, B, res * res,
                      c.token_size, d->e_conv_out.cout);

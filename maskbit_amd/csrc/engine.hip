@@ -15,6 +15,7 @@
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_decoder.h"
 #include "mb_kernels.h"
+#include "mb_vq.h"
 
 namespace {
 
@@ -865,6 +866,45 @@ int mb_dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* im
   ProfScope p("decode", (hipStream_t)stream);
   int rc = mb::dec_decode(d, tokens, img_nchw, img_nhwc_u8, B, (hipStream_t)stream, err);
   if (rc) return fail(rc, "mb_dec_decode: %s", err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int mb_dec_create_vq(const mb_dec_cfg* cfg, int codebook_size, int l2_normalize, int max_batch, mb_dec** out) {
+  if (!cfg || !out || max_batch <= 0) return fail(-1, "mb_dec_create_vq: bad arguments");
+  if (codebook_size < 2 || codebook_size > 65536) return fail(-1, "mb_dec_create_vq: codebook_size %d outside [2, 65536]", codebook_size);
+  std::string err;
+  mb_dec* d = mb::dec_create(*cfg, max_batch, err, codebook_size, l2_normalize);
+  if (!d) return fail(-1, "mb_dec_create_vq: %s", err.c_str());
+  *out = d;
+  return 0;
+}
+int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
+  if (!d || !z_nchw) return fail(-1, "mb_dec_decode_latent: null argument");
+  std::string err;
+  ProfScope p("decode", (hipStream_t)stream);
+  int rc = mb::dec_decode_latent(d, z_nchw, img_nchw, img_nhwc_u8, B, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "mb_dec_decode_latent: %s", err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+int mb_enc_encode_vq(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, mb_stream stream) {
+  if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode_vq: null argument");
+  std::string err;
+  ProfScope p("encode", (hipStream_t)stream);
+  int rc = mb::enc_encode_vq(d, img_nchw, indices, zq, zraw, row_dist, B, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "mb_enc_encode_vq: %s", err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream) {
+  if (!z || !codebook || !idx) return fail(-1, "mb_vq_argmin: null argument");
+  std::string err;
+  int rc = mb::vq_argmin(z, codebook, N, C, K, l2, splits, idx, dist, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "mb_vq_argmin: %s", err.c_str());
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
   return 0;

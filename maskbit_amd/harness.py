@@ -19,7 +19,7 @@ import torch
 
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
-from .sampling import build_plan, run_chunked, _ForcedPlan
+from .sampling import build_plan, check_tokenizer, run_chunked, _ForcedPlan
 
 
 def eval_labels(device, nclass: int = 1000, repeats: int = 50) -> torch.Tensor:
@@ -44,6 +44,7 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
     tokens each image was decoded from (what the reference's evaluator takes as ``codebook_indices``, evaluator.py:536)."""
     if not isinstance(model, LFQBert) or not isinstance(vqgan_model, ConvVQModel):
         raise TypeError("generate_uint8() needs a maskbit_amd generator and tokenizer")
+    check_tokenizer(model, vqgan_model)
     dev = model._require_cuda("generate_uint8")
     model.eval()
     vqgan_model.eval()

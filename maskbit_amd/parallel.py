@@ -85,7 +85,8 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
     because a caller that seeds every rank identically -- what ``noise="batch"``, the default until round 3, wanted -- would then draw the same
     noise on every rank.  Pass ``noise="rank"`` (and seed the ranks differently) or ``noise="batch"`` explicitly."""
     import torch.distributed as dist
-    from .sampling import _ForcedPlan, build_plan, draw_noise, plan_arrays, run_loop, step_chunks
+    from .sampling import _ForcedPlan, build_plan, check_tokenizer, draw_noise, plan_arrays, run_loop, step_chunks
+    check_tokenizer(model, vqgan_model)
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     B = int(global_labels.numel())

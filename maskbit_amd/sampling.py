@@ -45,6 +45,13 @@ def build_plan(num_steps: int, num_maskable: int, guidance_scale: float, guidanc
     return scale, temp, mask_len
 
 
+def check_tokenizer(model, vqgan_model) -> None:
+    """A lookup (VQ) tokenizer must hold every code the generator can emit: 2**model.bits <= codebook_size (the reference would fail in the
+    codebook's nn.Embedding, quantizer.py:115).  Raised before any device work.  LFQ tokenizers are not checked (unchanged path)."""
+    if getattr(vqgan_model, "quantizer_type", None) == "lookup" and vqgan_model.codebook_size < 2 ** model.bits:
+        raise ValueError(f"the tokenizer's codebook holds {vqgan_model.codebook_size} entries, the generator emits codes up to 2**{model.bits}")
+
+
 NOISE_CHUNK_BYTES = 1 << 30       # sample() / generate_uint8() draw and feed the Exp(1) noise in step chunks of at most this size
 OVERLAP_CHUNKS = 8                # ... and in at least this many chunks (+ a one-step head): the host draws chunk k+1 while the device runs chunk k
 
@@ -231,6 +238,7 @@ def sample(
         raise TypeError(f"sample() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
     if not isinstance(vqgan_model, ConvVQModel):
         raise TypeError(f"sample() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
+    check_tokenizer(model, vqgan_model)
     device = model.device
     model.eval()
     vqgan_model.eval()

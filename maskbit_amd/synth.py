@@ -162,8 +162,9 @@ def decoder_plan(cfg: TokCfg) -> List[Tuple[str, int, int, bool]]:
     return out
 
 
-def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = False) -> StateDict:
-    """Seeded conv weights randn/sqrt(fan_in), GN gamma ~ 1, with the reference's key names."""
+def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = False, lfq_buffers: bool = True) -> StateDict:
+    """Seeded conv weights randn/sqrt(fan_in), GN gamma ~ 1, with the reference's key names.  ``lfq_buffers=False``: without the LFQ
+    quantizer's derived buffers (a lookup tokenizer's codebook comes from make_vq_codebook instead)."""
     g = torch.Generator().manual_seed(seed)
 
     def conv(co, ci, k):
@@ -213,6 +214,16 @@ def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = Fals
             res_block(f"encoder.mid.res_blocks.{r}", c, c)
         sd["encoder.norm_out.weight"] = vec(c, 1.0); sd["encoder.norm_out.bias"] = vec(c)
         sd["encoder.conv_out.weight"] = conv(cfg.token_size, c, 1); sd["encoder.conv_out.bias"] = vec(cfg.token_size)
-        sd["quantize.bits_to_indices"] = (1 << torch.arange(cfg.token_size)).to(torch.int32)
-        sd["quantize.codebook"] = _index_to_bits(torch.arange(1 << cfg.token_size), cfg.token_size)
+        if lfq_buffers:
+            sd["quantize.bits_to_indices"] = (1 << torch.arange(cfg.token_size)).to(torch.int32)
+            sd["quantize.codebook"] = _index_to_bits(torch.arange(1 << cfg.token_size), cfg.token_size)
     return sd
+
+
+def make_vq_codebook(codebook_size: int, token_size: int, seed: int, mean, std) -> Tensor:
+    """Seeded lookup-quantizer codebook [C, K] = randn * std + mean (per channel): entries at the scale of the encoder's latents, so that the
+    nearest-entry search is not trivial (the reference's uniform(+-1/C) init puts every entry next to the origin)."""
+    g = torch.Generator().manual_seed(seed)
+    mean = torch.as_tensor(mean, dtype=torch.float32).reshape(1, -1)
+    std = torch.as_tensor(std, dtype=torch.float32).reshape(1, -1)
+    return torch.randn(codebook_size, token_size, generator=g) * std + mean
