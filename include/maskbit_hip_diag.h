@@ -63,13 +63,10 @@ int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, i
  * (N - 1) % 64 == 0 beyond 288. */
 /* out4l / out4l_scale (optional, both or neither; precision 4): the same for the fp16 lo halves o_c - fp16(o_c) of the conditional outputs. */
 int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_scale, void* out4l, void* out4l_scale, int pairs, int N, int d, int heads, mb_stream stream);
-/* Study knob of the weight-correction passes (precision >= 2): they run in trunk layers >= from_layer (default 0 = every layer; depth = none; guided
- * forward) and on the GEMMs of gemm_mask (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down; default 15; both forwards).  No subset keeps the default's
- * parity margin (profiles/r04_gemm_minitiles.md section 4): the product never calls this. */
-int mb_gen_set_wcorr(mb_gen* g, int from_layer, int gemm_mask);
-/* The same kind of study knob for the ACTIVATION-LO sets of precision >= 3: trunk layers >= from_layer, GEMMs of gemm_mask (same bits).  A handle is created
- * with the operands of its precision's own coverage (3: FFN-up, layers >= depth / 2; 4: every GEMM of every layer); the knob can only narrow that. */
-int mb_gen_set_alo(mb_gen* g, int from_layer, int gemm_mask);
+/* Which GEMMs of the guided forward carry the ACTIVATION-LO sets of precision >= 3 (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down; every layer).  A handle is
+ * created with the operands of its precision's own coverage (3: out-proj + FFN-up = 6; 4: + FFN-down = 14) and runs that; this can only narrow it.  The
+ * product never calls this. */
+int mb_gen_set_alo(mb_gen* g, int gemm_mask);
 /* Persistent kernels launch one workgroup per CU.  On a stream created with a CU mask (hipExtStreamCreateWithCUMask) fewer CUs serve the launch:
  * n = the CUs the following launches should size their grids for, 0 = the device's count (default).  Process-wide, not thread-safe. */
 int mb_set_cu_count(int n);

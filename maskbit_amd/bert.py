@@ -38,7 +38,6 @@ PREC_AUTO, PREC_FP16, PREC_DIFF, PREC_WCORR, PREC_ALO, PREC_ALO_ALL = -1, 0, 1, 
 ESCALATE_KURTOSIS = 4.5
 ESCALATE_CHANNEL_RATIO = 6.0
 DEFAULT_PRECISION = PREC_AUTO
-DEFAULT_WCORR_MASK = 15
 
 
 def pair_capable(seq_len: int, hidden: int, mlp: int, prenorm: bool) -> bool:
@@ -104,14 +103,6 @@ class LFQBert(BaseModel):
         # Precision mode of the device engine (not a reference argument; see PREC_* above).  Default from MASKBIT_AMD_PRECISION; may be changed before a
         # call (the engine is rebuilt and the checkpoint repacked).
         self.precision = int(os.environ.get("MASKBIT_AMD_PRECISION", str(DEFAULT_PRECISION)))
-        # study knobs (mb_gen_set_wcorr, include/maskbit_hip_diag.h): first trunk layer that carries the weight-correction pass (0 = all, the default; depth // 2 = the second half of the trunk:
-        # half the cost, 7.6e-4 instead of 4.8e-4 over the three 12-bit / 64-step runs, no use on the 14-bit ones -- profiles/r03_parity.md)
-        self.wcorr_from = int(os.environ.get("MASKBIT_AMD_WFROM", "0"))
-        # ... and which GEMMs of a layer carry them: 1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down (15 = all, the default)
-        self.wcorr_mask = int(os.environ.get("MASKBIT_AMD_WMASK", str(DEFAULT_WCORR_MASK)))
-        # ... and (mb_gen_set_alo) which GEMMs / from which layer on carry the activation-lo set of precision >= 3; None = the precision's own coverage
-        self.alo_mask = int(os.environ["MASKBIT_AMD_ALO_MASK"]) if "MASKBIT_AMD_ALO_MASK" in os.environ else None
-        self.alo_from = int(os.environ.get("MASKBIT_AMD_ALO_FROM", "0"))
         self._engine_split = None
         self._wstats = None               # (weight signature, statistics) of the last weight_statistics() call
         if not self.embed_tables:
@@ -130,8 +121,6 @@ class LFQBert(BaseModel):
         self._engine_split = self.resolved_precision()
         h = C.c_void_p()
         _lib.check(_lib.load().mb_gen_create(C.byref(cfg), capacity, C.byref(h)), "mb_gen_create")
-        self._engine_wfrom = None
-        self._engine_alo = None
         return h
 
     @torch.no_grad()
@@ -201,13 +190,6 @@ class LFQBert(BaseModel):
             h = self._ensure_engine(max(min_seqs, have, 16))
         finally:
             self._sig_hint = None
-        wf = (max(0, min(int(self.wcorr_from), self.depth)), int(self.wcorr_mask) & 15)
-        if getattr(self, "_engine_wfrom", None) != wf:
-            _lib.check(_lib.load().mb_gen_set_wcorr(h, wf[0], wf[1]), "mb_gen_set_wcorr")
-            self._engine_wfrom = wf
-        if self.alo_mask is not None and getattr(self, "_engine_alo", None) != (int(self.alo_from), int(self.alo_mask)):
-            _lib.check(_lib.load().mb_gen_set_alo(h, int(self.alo_from), int(self.alo_mask) & 15), "mb_gen_set_alo")
-            self._engine_alo = (int(self.alo_from), int(self.alo_mask))
         return h
 
     def saturation_count(self, reset: bool = True) -> int:

@@ -28,19 +28,14 @@ def needs_build(lib: str = LIB) -> bool:
     return any(os.path.getmtime(p) > t for p in deps)
 
 
-def build(force: bool = False, verbose: bool = False, defs: str = "", out: str = "") -> str:
-    """The product library (no arguments), or -- `defs` = extra -D flags, `out` = another output path -- an A/B build for the tools (tools/gemm_ab.py,
-    tools/forward_ab.py).  The timing-only switches (MB_NO_GELU, MB_MINI_NO_*, ...) produce wrong results by design, so a build with extra flags NEVER
-    lands on the product path: it needs an `out` of its own (the environment variable MASKBIT_AMD_BUILD_DEFS of earlier rounds is gone)."""
-    if defs and not out:
-        raise ValueError("an A/B build (extra -D flags) needs an output path of its own: it must not replace the product library")
-    lib = os.path.abspath(out) if out else LIB
-    if not force and not defs and not needs_build(lib):
-        return lib
+def build(force: bool = False, verbose: bool = False) -> str:
+    """The product library: compiled unless it is newer than every source (`force`: always)."""
+    if not force and not needs_build():
+        return LIB
     objs = []
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", *defs.split()]
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
     procs = []
-    bdir = os.path.join(HERE, "build") if not out else lib + ".objs"
+    bdir = os.path.join(HERE, "build")
     os.makedirs(bdir, exist_ok=True)
     for src in SOURCES:
         obj = os.path.join(bdir, src.replace(".hip", ".o"))
@@ -55,11 +50,11 @@ def build(force: bool = False, verbose: bool = False, defs: str = "", out: str =
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
         if verbose and out.strip():
             print(out)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", lib]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}")
-    return lib
+    return LIB
 
 
 if __name__ == "__main__":

@@ -19,16 +19,13 @@
 // even mask, so the two slots of a 32-byte tr-read segment stay adjacent) on the DMA source address
 // and on the reads.  The tr reads are inline asm (no builtin), software-pipelined one k-block ahead
 // with counted lgkmcnt waits.
-#include <cstdlib>
 #include <type_traits>
 
 #include "mb_kernels.h"
 
 namespace mb {
 
-#ifndef MB_ATT_SDEPTH
-#define MB_ATT_SDEPTH 3          // key tiles whose K fragments may be in flight ahead of their score MFMAs
-#endif
+constexpr int ATT_SDEPTH = 3;            // key tiles whose K fragments may be in flight ahead of their score MFMAs
 constexpr int ATT_NKT = 18;              // key tiles of 16 -> up to 288 keys
 constexpr int ATT_NP = ATT_NKT * 16;     // padded key count
 constexpr int ATT_NW = 4;                // waves per workgroup (6 waves x 3 tiles measured slower: 104 vs 89 us; so did two query
@@ -36,16 +33,6 @@ constexpr int ATT_NW = 4;                // waves per workgroup (6 waves x 3 til
 constexpr int ATT_MAXQT = (ATT_NKT + ATT_NW - 1) / ATT_NW;   // q-tiles per wave
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-// Timeline instrumentation (tools/att_trace.py builds its own copy with -DMB_ATT_TRACE; never in the product library): wave 0 of every workgroup
-// stamps the 100 MHz wall clock -> trace[workgroup][32]: 0 start, 1 loads issued, 2 K / V / Q landed, then per query tile 3+4i .. 6+4i = after the
-// score MFMAs, the softmax, the PV MFMAs, the stores.
-#ifdef MB_ATT_TRACE
-__device__ long long* g_att_trace = nullptr;
-#define MB_ATRACE(k) do { if (g_att_trace && tid == 0 && (k) < 32) g_att_trace[((size_t)blockIdx.x + ((AUX == 4 && pass == 1) ? gridDim.x : 0)) * 32 + (k)] = wall_clock64(); } while (0)
-#else
-#define MB_ATRACE(k) do { } while (0)
-#endif
 
 // e2m1 of a lane's output tile o[4][4] (row q = lane & 15; values dh = 16 nt + 4 g + r, g = lane >> 4) * inv, scaled by `mul`, exchanged between the row's
 // four lane groups so that the lane ends up with bytes [8 (g & 1) + 16 (g >> 1), +8) of the row's 32-byte (64-value) block: dh tile nt's 8 bytes live in
@@ -125,7 +112,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
   for (int pass = 0; pass < NPASS; ++pass) {
   const int sq = sq0 + (AUX == 4 ? pass * sq_off : sq_off);
   const h16* base = qkv + (size_t)sq * N * rs + h * DH;
-  MB_ATRACE(0);
   if (AUX == 4 && pass > 0) __syncthreads();                         // every wave is done with the first pass's K / V image
 
   auto kswz = [](int row) { return SL == 8 ? ((row >> 1) & 7) : ((0 - (row >> 2)) & 3); };
@@ -155,10 +141,8 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
   // (AUX 4 runs at the VGPR limit: it fetches the next tile's Q fragments one tile ahead instead of all up front)
 #pragma unroll
   for (int i = 0; i < (AUX == 4 ? 1 : ATT_MAXQT); ++i) q_fetch(i);
-  MB_ATRACE(1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  MB_ATRACE(2);
 
   // per-lane constant parts of the fragment addresses
   const int koff = l15 * ROW;                                       // K fragment: row kt*16 + l15
@@ -177,10 +161,9 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
     if (qt >= nqt) break;
     // ---- S^T tiles: s[kt][r] = S[q = l15][key = kt*16 + g*4 + r]
     f32x4 s[ATT_NKT];
-#ifndef MB_ATT_NOSPIPE
     // groups of GK key tiles; the K fragments of group n+1 are requested before the MFMAs of group n, and inside a group all first k-steps go
     // before the second ones (no MFMA waits for the one issued just before it)
-    constexpr int GK = MB_ATT_SDEPTH, NG = ATT_NKT / GK;
+    constexpr int GK = ATT_SDEPTH, NG = ATT_NKT / GK;
     static_assert(ATT_NKT % GK == 0, "whole groups");
     h16x8 kfr[2][GK][KS];
     auto k_fetch = [&](h16x8 (&dst)[GK][KS], int grp) {
@@ -206,24 +189,9 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
         }
       __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#pragma unroll
-    for (int kt = 0; kt < ATT_NKT; ++kt) {
-      s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int row = kt * 16 + l15;
-      if (kt == ATT_NKT - 1 && kt * 16 >= N) continue;      // the padding tile holds no key at N = 257
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const h16x8 kf = *(const h16x8*)(Ks + kt * 16 * ROW + koff + (((ks * 4 + g) ^ kswz(row)) * 16));
-        s[kt] = MB_MFMA_16x16x32(kf, qf[i][ks], s[kt]);
-      }
-      if (kt % MB_ATT_SDEPTH == MB_ATT_SDEPTH - 1) __builtin_amdgcn_sched_barrier(0);   // bound the fragment prefetch depth (VGPR budget)
-    }
-#endif
     if (AUX == 4 && i + 1 < ATT_MAXQT) q_fetch(i + 1);
     // (round 3, measured and removed: pulling the twin sequence's K / V rows towards the L2 during the first pass -- one dword per row as LDS-DMA into the
     // padding key tile -- made the launch SLOWER, 90-91 us against 85-88: the second pass's staging is not waiting for HBM.)
-    MB_ATRACE(3 + 4 * i);
     // ---- softmax over keys (fp32); only the last two key tiles can hold keys >= N
     float mx = -INFINITY;
 #pragma unroll
@@ -249,7 +217,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
     sum = rows_sum(sum);
     float inv = 1.0f / sum;
     asm volatile("" : "+v"(inv));          // every cross-lane op of the softmax has retired before the asm LDS reads start
-    MB_ATRACE(4 + 4 * i);
     // ---- O^T = V^T P^T ; V^T fragments by transpose reads, one k-block ahead
     f32x4 o[NT];
 #pragma unroll
@@ -308,7 +275,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
     step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 4>{});
     step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 8>{});
     static_assert(NKB <= 10, "add steps");
-    MB_ATRACE(5 + 4 * i);
     // ---- o[nt][r] = O[q = l15][dh = nt*16 + g*4 + r]
     const int q = qt * 16 + l15;
     if constexpr ((AUX == 4 || AUX == 5) && DH == 64) {
@@ -351,7 +317,6 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
         *(h16x4*)(out + ooff + nt * 16 + g * 4) = hi;
       }
     }
-    MB_ATRACE(6 + 4 * i);
   }
   }                                      // pass
 }
@@ -621,10 +586,7 @@ int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d,
   if (dh != 64 && dh != 32) return -1;
   if ((out4l || out4ls) && (!out4 || !out4s || !out4l || !out4ls)) return -1;   // the lo copy rides with the value copy
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-  // experiment switch (tools/att_stream_ab.py; never set by the product): the streaming kernel for 257-token sequences too -- 64 queries per workgroup,
-  // 144 VGPRs, K / V in 128-key blocks: more workgroups and waves in flight per CU against a head's K / V re-read by every 64-query chunk
-  static const bool force_stream = getenv("MASKBIT_AMD_ATT_STREAM") && atoi(getenv("MASKBIT_AMD_ATT_STREAM")) != 0;
-  if (N > ATT_NP || (force_stream && (N - 1) % 64 == 0)) {     // the 1024 + 1-token models: streaming kernel, both streams of a pair in one workgroup
+  if (N > ATT_NP) {                                           // the 1024 + 1-token models: streaming kernel, both streams of a pair in one workgroup
     if (out4 && (dh != 64 || (N - 1) % 64)) return -1;
     const int nchunk = ((N + 15) / 16 + 3) / 4;
     dim3 grid(P * heads * nchunk), block(256);
@@ -641,12 +603,3 @@ int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d,
 }
 
 }  // namespace mb
-
-#ifdef MB_ATT_TRACE
-extern "C" int mb_debug_att_trace(long long* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(mb::g_att_trace), &p, sizeof(p)); }
-#endif
-#if defined(MB_ATT_TRACE) || defined(MB_ATT_VARIANT)      // experimental builds of this file alone (tools/att_trace.py)
-extern "C" int mb_debug_attention_pair(const void* qkv, void* out, int P, int N, int d, int heads, void* stream) {
-  return mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out, P, N, d, heads, nullptr, nullptr);
-}
-#endif

@@ -13,8 +13,6 @@
 // reduction (no float atomics), so outputs are bit-stable run to run.  Level one lives in the epilogue of the conv that PRODUCES the tensor
 // (one (sum, sumsq) pair per 8x16-pixel tile and group, written next to the tile), level two in gn_finalize_kernel before the consuming conv;
 // only tensors that no conv of this file produced (the encoder's average-pooled ones) still take the separate sweep (gn_partial_kernel).
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -42,19 +40,7 @@ struct ConvArgs {
   unsigned* sat;         // counts output groups of 4 whose value left the fp16 range and was clamped (mb_dec_saturation_count)
   float* gn_part;        // or null: GroupNorm partial statistics of the OUTPUT, [B][pixel tiles per image][32 groups][sum, sumsq] -- the consumer's
                          // GroupNorm then needs no sweep over the tensor (its fp16-stored values are what is summed, as that sweep did)
-#ifdef MB_CONV_TRACE
-  long long* trace;      // tools/dec_trace.py: [workgroup][16] wall-clock stamps of one selected launch
-#endif
 };
-
-// Timeline instrumentation (tools/dec_trace.py builds its own copy with -DMB_CONV_TRACE; never in the product library): thread 0 of every workgroup
-// stamps the 100 MHz wall clock: 0 start; per input-channel chunk c < 3: 1+4c halo free (barrier passed), 2+4c halo staged by this wave, 3+4c weights +
-// halo visible (barrier passed), 4+4c the chunk's last tap done; 15 end of the epilogue.
-#ifdef MB_CONV_TRACE
-#define MB_CTRACE(k) do { if (a.trace && tid == 0 && (k) < 16) a.trace[(size_t)blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
-#else
-#define MB_CTRACE(k) do { } while (0)
-#endif
 
 __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
@@ -172,19 +158,15 @@ __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
     for (int j = 0; j < MJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int T = (Cin / CK) * NTAP;
-  MB_CTRACE(0);
   stage_w(0, 0);
   for (int t = 0; t < T; ++t) {
     const int chunk = t / NTAP, tap = t - chunk * NTAP;
     if (tap == 0) {
       __syncthreads();                      // all waves are done with the previous chunk's halo
-      MB_CTRACE(1 + 4 * chunk);
       stage_halo(chunk);
-      MB_CTRACE(2 + 4 * chunk);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                        // weight tile t landed, halo visible
-    if (tap == 0) MB_CTRACE(3 + 4 * chunk);
     if (t + 1 < T) stage_w(t + 1, (t + 1) & 1);
     const int dy = tap / KS, dx = tap - dy * KS;
     const char* wb = wt + (t & 1) * WT_BYTES + wn * NI * 16 * 128;
@@ -204,7 +186,6 @@ __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
         for (int j = 0; j < MJ; ++j)
           acc[i][j] = MB_MFMA_16x16x32(wf[i], xf[j], acc[i][j]);
     }
-    if (tap == NTAP - 1) MB_CTRACE(4 + 4 * chunk);
   }
 
   // ---- epilogue: lane holds out[pixel (y = wm*MJ+j, x = l15)][cout = ..+g*4 .. +3]
@@ -312,7 +293,6 @@ __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
       }
     }
   }
-  MB_CTRACE(15);
 }
 
 // ---- GroupNorm statistics: partial (sum, sumsq) per (image, pixel chunk, group) -----------------
@@ -557,27 +537,17 @@ bool init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout
   return ok;
 }
 
-#ifdef MB_CONV_TRACE
-static long long* g_conv_trace = nullptr;
-static int g_conv_trace_sel = -1, g_conv_trace_n = 0;
-#endif
 void launch_conv(hipStream_t s, mb_dec* d, const Conv& c, const h16* in, const float2* gn, const h16* residual, h16* out,
                  float* img, uint8_t* u8, int B, int H, int W, bool final_, bool stats = true) {
   // GroupNorm partials of the output ride in the epilogue when a GroupNorm will read it (stats) and its groups are whole lane groups of a tile
   const int cpg = c.cout / 32;
   const bool part = !final_ && stats && c.cout % 128 == 0 && (cpg == 4 || cpg == 8 || cpg == 16);
   ConvArgs a{in, gn, c.w, c.has_bias ? c.b : nullptr, residual, out, img, u8, B, H, W, c.cin_pad, c.cout, c.cout_pad, c.sat, part ? d->gn_part : nullptr};
-#ifdef MB_CONV_TRACE
-  a.trace = (g_conv_trace && g_conv_trace_n++ == g_conv_trace_sel) ? g_conv_trace : nullptr;
-  if (a.trace) printf("conv launch %d: %s  %dx%d  %d -> %d  ks %d%s\n", g_conv_trace_sel, c.name.c_str(), H, W, c.cin_pad, c.cout, c.ks, c.up ? " up" : "");
-#endif
   d->gn_of = part ? (const void*)out : nullptr;
   const int bn = final_ ? 16 : 128;
   // 16-row tiles (8 waves) for the 3x3 convolutions from 32 x 32 maps on; 8-row tiles below (a 16 x 16 map would be one tile per image).  The choice
   // must not depend on the batch: the GroupNorm partial sums are per tile, and results are bit-identical across batch sizes.
-  static const int th_force = getenv("MASKBIT_AMD_CONV_TH") ? atoi(getenv("MASKBIT_AMD_CONV_TH")) : 0;   // A/B switch (experiments; read once)
-  bool th16 = !final_ && c.ks == 3 && H % 16 == 0 && H >= 32;
-  if (th_force == 8) th16 = false;
+  const bool th16 = !final_ && c.ks == 3 && H % 16 == 0 && H >= 32;
   const int th = th16 ? 16 : TH8;
   d->gn_ntile = (H / th) * (W / TW);
   dim3 grid((unsigned)((size_t)B * (H / th) * (W / TW) * (c.cout_pad / bn))), block(32 * th);
@@ -904,7 +874,3 @@ int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* 
 }
 
 }  // namespace mb
-
-#ifdef MB_CONV_TRACE
-extern "C" int mb_debug_conv_trace(long long* p, int sel) { mb::g_conv_trace = p; mb::g_conv_trace_sel = sel; mb::g_conv_trace_n = 0; return 0; }
-#endif

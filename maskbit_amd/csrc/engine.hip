@@ -121,7 +121,7 @@ struct mb_gen {
   // in the guided forward's FFN-up GEMM: xl4 / xl4s = e2m1 of their lo halves, w4 / w4s = e2m1 of the (fp16) weight net.0.
   bool pair_ok = false, mini_ok = false;
   uint8_t *x4 = nullptr, *x4s = nullptr, *xl4 = nullptr, *xl4s = nullptr;
-  std::vector<uint8_t*> w4, w4s;                                                         // [4 * layer + {qkv, o, 1, 2}]: precision 3: net.0 of the late layers only; precision 4: all
+  std::vector<uint8_t*> w4, w4s;                                                         // [4 * layer + {qkv, o, 1, 2}]: the GEMMs of alo_mask_built only
   float* logits_tmp = nullptr;                          // guided forwards over more pairs than one pass holds
   // The two head GEMMs run hi + lo inputs against hi + lo WEIGHTS in every mode (GemmArgs.W2: three sweeps): their rounding reaches the logits
   // un-averaged -- fp16 head weights alone were a quarter of the sampled-logit error variance left after the trunk's weight correction
@@ -136,15 +136,12 @@ struct mb_gen {
   // loop state for mb_sample
   // the run mb_sample is in the middle of (step chunks): samples, total steps, guidance flag, the step the next chunk must begin with (-1: no run)
   int loop_B = 0, loop_steps = 0, loop_guided = 0, loop_next = -1;
-  int wcorr_from = 0;                                   // precision >= 2: first trunk layer that carries the correction passes (mb_gen_set_wcorr)
-  int wcorr_mask = 15;                                  // ... and which GEMMs of a layer: 1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down
-  // precision >= 3: which GEMMs (same bits) of which layers (>= alo_from) carry the activation-lo set.  Coverage measured on the reference's own runs in round 6
+  // precision >= 3: which GEMMs carry the activation-lo set (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down).  Coverage measured on the reference's own runs in round 6
   // (profiles/r06_coverage.md: four 14-bit / 256-step runs, four 12-bit runs, three trained-like runs; mismatches / guided-forward time of 64 pairs):
   //   none 595 / 263 / 271 at 29.9 ms;  FFN-up of layers >= depth / 2 (round 5's precision 3) 506 / 222 / 276 at 30.5;  out-proj + FFN-up 384 / 186 / 219 at 31.6;
   //   out-proj + FFN-up + FFN-down 241 / 115 / 203 at 33.4;  all four 228 / 116 / 200 at 34.3 -- the QKV set buys nothing (as round 5 found for precision 3).
-  // precision 3 = out-proj + FFN-up of every layer; precision 4 = + FFN-down.  mb_gen_set_alo (study knob) selects within what the handle was created with
-  // (precision 4 builds the QKV operands too, for such studies).
-  int alo_mask = 0, alo_from = 0, alo_mask_built = 0, alo_from_built = 0;
+  // precision 3 = out-proj + FFN-up of every layer (6); precision 4 = + FFN-down (14).  mb_gen_set_alo (diagnostic) narrows within what the handle was created with.
+  int alo_mask = 0, alo_mask_built = 0;
   const int64_t* cfg_labels_ready = nullptr;            // gen_forward_cfg: lab_cfg / drop_cfg already hold [labels | labels] / [0 | 1] for this many pairs
   int cfg_ready_B = 0;
   int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
@@ -216,10 +213,9 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
   h16* const xlo_qkv = xlo_all ? g->x_lo : nullptr;
   // the LayerNorms write the MX-fp4 copy (+ scale bytes) only when a GEMM of THIS forward reads it (the buffers also exist for the pair forward)
   Fp4Rows f4x;
-  if (wm && (g->wcorr_mask & 5)) { f4x.x4 = g->x4; f4x.x4s = g->x4s; f4x.nseq = nb; f4x.seq_rows = N; }
-  const bool wo4 = wm && (g->wcorr_mask & 2);
+  if (wm) { f4x.x4 = g->x4; f4x.x4s = g->x4s; f4x.nseq = nb; f4x.seq_rows = N; }
   auto lo_set = [&](GemmArgs& ga, const uint8_t* a4, const uint8_t* a4s, int widx) {
-    if (!wm || !((g->wcorr_mask >> (widx & 3)) & 1)) return;
+    if (!wm) return;
     ga.nlo = 1; ga.lo[0] = {a4, a4s, g->w4lo[widx], g->w4los[widx]};
   };
   // QKV / FFN-up: consume the LayerNorm output
@@ -227,7 +223,7 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     GemmArgs ga{g->x_h16, W, bias, nullptr, nullptr, out, M, Nout, d, 0};
     if (wm) ga.seq_rows = N;
     lo_set(ga, g->x4, g->x4s, widx);
-    if (wm && epi == EPI_GELU_H16 && (g->wcorr_mask & 8)) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
+    if (wm && epi == EPI_GELU_H16) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
     if (((widx & 3) == 2 || xlo_all) && xlo_layer(widx >> 2)) { ga.K = 2 * d; ga.A2 = g->x_lo; ga.kw = d; }   // FFN-up only with the correction (see above)
     ga.sat = g->sat;
     gemm_rc |= gemm_tn(s, epi, ga, wm ? 257 : 0);
@@ -256,7 +252,7 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     // x = x + FFN(LN(x)): the buffer holds x itself, every LayerNorm only produces the GEMM operand, the residual GEMMs add the buffer's own rows.
     if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, L.ln1g, L.ln1b, 1e-12f, nullptr, g->x_h16, nullptr, M, d, xlo_qkv, f4x); }
     { ProfScope p("gemm_qkv", s, true); xgemm(EPI_H16, L.wqkv, L.bqkv, g->qkv, 3 * d, 4 * l); }
-    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wo4 ? g->att4 : nullptr, wo4 ? g->att4s : nullptr); }
+    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wm ? g->att4 : nullptr, wm ? g->att4s : nullptr); }
     attn_rc |= attn_maps(l);
     { ProfScope p("gemm_attn_out", s, true);
       const bool re = !c.prenorm && l > 0;
@@ -291,9 +287,8 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
   const int d = c.hidden, f = c.mlp, N = g->N, nb = 2 * B, M = nb * N, P = B * N;
   int rc = 0;
   // measured (profiles/r03_parity.md): the correction pass in layers >= depth / 2 alone buys about 60 % of the gain on the 12-bit runs for half of
-  // the cost and next to nothing on the 14-bit one (and per GEMM type no subset is a cheaper "precise": section 5 there) -- a study knob
-  // (mb_gen_set_wcorr, include/maskbit_hip_diag.h), not the default
-  const int wfrom = g->wcorr_from;
+  // the cost and next to nothing on the 14-bit one (and per GEMM type no subset is a cheaper "precise": section 5 there) -- so it runs on every GEMM
+  // of every layer
   // The activation-lo sets of precision >= 3.  Rounds 4-5 knew the LayerNorm outputs' set only: over FOUR 14-bit / 256-step reference runs (1 002 744
   // positions; profiles/r05_coverage.md) QKV + FFN-up in all layers 496 mismatches, FFN-up alone 491-493, QKV alone 555, neither 625 -- the QKV set buys
   // nothing --, and round 5 ran it in FFN-up of the layers >= depth / 2 (531).
@@ -302,13 +297,13 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
   // precision 4 (what heavy-tailed checkpoints need) = + FFN-down.  With exact weights the fp16 rounding of those three operands alone costs 7e-4 of
   // token mismatch on the early steps of a trained-like run (a third each); emulated on that run (tests/diag/error_budget.py EB_STUDY=r6): rms error
   // of the sampled logits' top-2 gap 0.0062 -> 0.0031 with the three sets (and the per-(row, 128 columns) weight-error scales).
-  // (which GEMMs of which layers: mb_gen::alo_mask / alo_from -- bit 0 QKV, 1 out-proj, 2 FFN-up, 3 FFN-down)
-  auto alo_on = [&](int gemm, int l) { return wmode && c.precision >= 3 && l >= wfrom && l >= g->alo_from && ((g->alo_mask >> gemm) & 1) && ((g->wcorr_mask >> gemm) & 1); };
-  auto f4_for = [&](int consumer_layer, bool feeds_ffn = false) {   // what the producer of layer `consumer_layer`'s LayerNorm operand also writes
+  // (which GEMMs: mb_gen::alo_mask -- bit 0 QKV, 1 out-proj, 2 FFN-up, 3 FFN-down)
+  auto alo_on = [&](int gemm) { return wmode && c.precision >= 3 && ((g->alo_mask >> gemm) & 1); };
+  auto f4_for = [&](bool feeds_ffn = false) {   // what the producer of a LayerNorm operand also writes
     Fp4Rows f;
-    if (wmode && consumer_layer >= wfrom && (g->wcorr_mask & 5)) {
+    if (wmode) {
       f.x4 = g->x4; f.x4s = g->x4s; f.nseq = B; f.seq_rows = N;
-      if (alo_on(feeds_ffn ? 2 : 0, consumer_layer)) { f.xl4 = g->xl4; f.xl4s = g->xl4s; }   // (the lo halves' e2m1 copy: only the LayerNorm in front of a GEMM that carries the set)
+      if (alo_on(feeds_ffn ? 2 : 0)) { f.xl4 = g->xl4; f.xl4s = g->xl4s; }   // (the lo halves' e2m1 copy: only the LayerNorm in front of a GEMM that carries the set)
     }
     return f;
   };
@@ -320,7 +315,6 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     ga.pair_rows = P;
     ga.seq_rows = N;
     if (epi != EPI_RES_F32) ga.sat = g->sat;
-    if (lo && !((g->wcorr_mask >> (widx & 3)) & 1)) lo = 0;
     if (lo) {
       ga.nlo = lo; ga.lo[0] = {a4, a4s, g->w4lo[widx], g->w4los[widx]};
       if (lo == 2) ga.lo[1] = {al4, al4s, g->w4[widx], g->w4s[widx]};
@@ -332,53 +326,51 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     // (tokens / labels / drop are laid out [B conditional | B twins]; the twins repeat the conditional tokens and labels with the drop flag set)
     EmbedArgs e{tokens, labels, nullptr, g->w_in, g->b_in, g->class_emb, g->pos, g->ln0g, g->ln0b,
                 g->y_f32, g->x_h16, B, c.seq, c.splits, g->gbits, d, c.nclass, g->tables};
-    e.f4 = f4_for(0);
+    e.f4 = f4_for();
     if (embed_pair(s, e)) {         // shapes the fused kernel does not serve: the two-kernel path
       e.drop = drop; e.nb = nb; e.f4 = Fp4Rows{};
       embed_ln(s, e);
-      rc |= pairify_rows(s, g->y_f32, g->x_h16, P, d, f4_for(0));        // y_f32 holds the embedding LayerNorm's fp32 rows here
+      rc |= pairify_rows(s, g->y_f32, g->x_h16, P, d, f4_for());        // y_f32 holds the embedding LayerNorm's fp32 rows here
     }
   }
   // pre-norm: the first sub-layer normalises the embedding rows again (LayerNorm 1 of layer 0); post-norm: the embedding's own pair operands feed QKV
   if (c.prenorm && c.depth > 0) {
     ProfScope p("layernorm", s, true);
-    rc |= layernorm_pair(s, g->y_f32, g->layers[0].ln1g, g->layers[0].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for(0));
+    rc |= layernorm_pair(s, g->y_f32, g->layers[0].ln1g, g->layers[0].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for());
   }
   for (int l = 0; l < c.depth; ++l) {
     const mb_gen::Layer& L = g->layers[l];
-    const bool wl = wmode && l >= wfrom;
-    const int xlo_mode = wl ? (alo_on(2, l) ? 2 : 1) : 0;
+    const int xlo_mode = wmode ? (alo_on(2) ? 2 : 1) : 0;
     { ProfScope p("gemm_qkv", s, true);
-      GemmArgs ga = pgemm(EPI_H16, g->x_h16, L.wqkv, L.bqkv, g->qkv, nullptr, 3 * d, d, 4 * l, wl ? (alo_on(0, l) ? 2 : 1) : 0, g->x4, g->x4s, g->xl4, g->xl4s);
+      GemmArgs ga = pgemm(EPI_H16, g->x_h16, L.wqkv, L.bqkv, g->qkv, nullptr, 3 * d, d, 4 * l, wmode ? (alo_on(0) ? 2 : 1) : 0, g->x4, g->x4s, g->xl4, g->xl4s);
       rc |= gemm_tn(s, EPI_H16, ga, 257); }
-    const bool wo4 = wl && (g->wcorr_mask & 2), wh4 = wl && (g->wcorr_mask & 8);
-    const bool lo_o = wo4 && alo_on(1, l), lo_h = wh4 && alo_on(3, l);      // the producers also write the lo halves' e2m1 copies for a consumer that carries the set
-    { ProfScope p("attention", s, true); rc |= attention_pair(s, g->qkv, g->att, B, N, d, c.heads, wo4 ? g->att4 : nullptr, wo4 ? g->att4s : nullptr,
+    const bool lo_o = alo_on(1), lo_h = alo_on(3);      // the producers also write the lo halves' e2m1 copies for a consumer that carries the set
+    { ProfScope p("attention", s, true); rc |= attention_pair(s, g->qkv, g->att, B, N, d, c.heads, wmode ? g->att4 : nullptr, wmode ? g->att4s : nullptr,
                                                               lo_o ? g->attl4 : nullptr, lo_o ? g->attl4s : nullptr); }
     { ProfScope p("gemm_attn_out", s, true);
-      GemmArgs ga = pgemm(EPI_RES_F32, g->att, L.wo, L.bo, nullptr, g->y_f32, d, d, 4 * l + 1, wl ? (alo_on(1, l) ? 2 : 1) : 0, g->att4, g->att4s, g->attl4, g->attl4s);
+      GemmArgs ga = pgemm(EPI_RES_F32, g->att, L.wo, L.bo, nullptr, g->y_f32, d, d, 4 * l + 1, wmode ? (alo_on(1) ? 2 : 1) : 0, g->att4, g->att4s, g->attl4, g->attl4s);
       if (l > 0 && !c.prenorm) { ga.ln_stats = g->ln_stats; ga.ln_g = g->layers[l - 1].ln2g; ga.ln_b = g->layers[l - 1].ln2b; }
       rc |= gemm_tn(s, EPI_RES_F32, ga, 257); }
     // post-norm: LayerNorm 1 follows the attention block; pre-norm: LayerNorm 2 precedes the FFN (same place in the launch order, other parameters;
     // the stream buffer then holds the raw residual and no GEMM re-derives a LayerNorm from the statistics)
     { ProfScope p("layernorm", s, true);
-      rc |= layernorm_pair(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, g->x_h16, c.prenorm ? nullptr : g->ln_stats, P, d, f4_for(l, true)); }
+      rc |= layernorm_pair(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, g->x_h16, c.prenorm ? nullptr : g->ln_stats, P, d, f4_for(true)); }
     { ProfScope p("gemm_ffn_up", s, true);
       GemmArgs ga = pgemm(EPI_GELU_H16, g->x_h16, L.w1, L.b1, g->h, nullptr, f, d, 4 * l + 2, xlo_mode, g->x4, g->x4s, g->xl4, g->xl4s);
-      if (wh4) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
+      if (wmode) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
       if (lo_h) { ga.out4l = g->hl4; ga.out4l_scale = g->hl4s; }
       rc |= gemm_tn(s, EPI_GELU_H16, ga, 257); }
     { ProfScope p("gemm_ffn_down", s, true);
-      GemmArgs ga = pgemm(EPI_RES_F32, g->h, L.w2, L.b2, nullptr, g->y_f32, d, f, 4 * l + 3, wl ? (alo_on(3, l) ? 2 : 1) : 0, g->h4, g->h4s, g->hl4, g->hl4s);
+      GemmArgs ga = pgemm(EPI_RES_F32, g->h, L.w2, L.b2, nullptr, g->y_f32, d, f, 4 * l + 3, wmode ? (alo_on(3) ? 2 : 1) : 0, g->h4, g->h4s, g->hl4, g->hl4s);
       if (!c.prenorm) { ga.ln_stats = g->ln_stats; ga.ln_g = L.ln1g; ga.ln_b = L.ln1b; }
       rc |= gemm_tn(s, EPI_RES_F32, ga, 257); }
     { ProfScope p("layernorm", s, true);
       if (c.prenorm) {            // the next layer's LayerNorm 1 (bert.py:49-59, 106-123), or norm_after_transformer in front of the head
         if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo);
-        else rc |= layernorm_pair(s, g->y_f32, g->layers[l + 1].ln1g, g->layers[l + 1].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for(l + 1));
+        else rc |= layernorm_pair(s, g->y_f32, g->layers[l + 1].ln1g, g->layers[l + 1].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for());
       }
       else if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, g->x_lo);   // feeds the head: plain hi (+ lo) rows
-      else rc |= layernorm_pair(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, g->x_h16, g->ln_stats, P, d, f4_for(l + 1)); }
+      else rc |= layernorm_pair(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, g->x_h16, g->ln_stats, P, d, f4_for()); }
   }
   rc |= head_gemms(g, logits, M, s);
   hipError_t e = hipGetLastError();
@@ -639,8 +631,8 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   g->mini_ok = c.precision >= 2 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && c.hidden / c.heads == 64;   // (FFN-up's N = mlp: whole 256-column tiles)
   // differential CFG forward: 257-token sequences (pair tiles = 2 x 128 tokens + the class pair), vector LayerNorm widths, plain fp16 operands
   // (round 5: also the 1024 + 1-token models of 512 x 512 images -- a pair tile is 128 tokens of a sequence pair whatever the sequence length)
-  if (c.precision == 3) { g->alo_mask = g->alo_mask_built = 6; }              // out-proj + FFN-up, every layer
-  if (c.precision >= 4) { g->alo_mask = 14; g->alo_mask_built = 15; }         // + FFN-down (the QKV operands exist for coverage studies only)
+  if (c.precision == 3) g->alo_mask = g->alo_mask_built = 6;                 // out-proj + FFN-up, every layer
+  if (c.precision >= 4) g->alo_mask = g->alo_mask_built = 14;                // + FFN-down
   g->pair_ok = c.precision >= 1 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && g->chunk_seqs >= 2 &&
                (c.precision == 1 || g->mini_ok);
   if (g->mini_ok) {
@@ -780,18 +772,11 @@ int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* s
   return 0;
 }
 
-int mb_gen_set_alo(mb_gen* g, int from_layer, int gemm_mask) {
-  if (!g || from_layer < 0 || from_layer > g->c.depth || gemm_mask < 0 || gemm_mask > 15) return fail(-1, "mb_gen_set_alo: layer outside [0, depth] or mask outside [0, 15]");
-  if ((gemm_mask & ~g->alo_mask_built) || (gemm_mask && from_layer < g->alo_from_built))
-    return fail(-1, "mb_gen_set_alo: the handle was created (precision %d) with the activation-lo operands of GEMM mask %d from layer %d on only", g->c.precision, g->alo_mask_built, g->alo_from_built);
-  g->alo_mask = gemm_mask; g->alo_from = from_layer;
-  return 0;
-}
-
-int mb_gen_set_wcorr(mb_gen* g, int from_layer, int gemm_mask) {
-  if (!g || from_layer < 0 || from_layer > g->c.depth || gemm_mask < 0 || gemm_mask > 15) return fail(-1, "mb_gen_set_wcorr: layer outside [0, depth] or mask outside [0, 15]");
-  g->wcorr_from = from_layer;
-  g->wcorr_mask = gemm_mask;
+int mb_gen_set_alo(mb_gen* g, int gemm_mask) {
+  if (!g || gemm_mask < 0 || gemm_mask > 15) return fail(-1, "mb_gen_set_alo: mask outside [0, 15]");
+  if (gemm_mask & ~g->alo_mask_built)
+    return fail(-1, "mb_gen_set_alo: the handle was created (precision %d) with the activation-lo operands of GEMM mask %d only", g->c.precision, g->alo_mask_built);
+  g->alo_mask = gemm_mask;
   return 0;
 }
 

@@ -30,7 +30,7 @@
 // 9 / 17 / 34 us per tile (fp16 / GELU / fp32+residual epilogue) next to a 26 us K = 1024 main loop.
 // (Tried and rejected, twice: starting half of the CUs 4 - 24 us late to de-synchronise those bursts -- slower by the delay itself, in every
 // epilogue form: the epilogue is bound per CU, like the main loop, not by aggregate HBM bandwidth.  Also rejected: 16 residual loads in flight per
-// lane instead of 4 in the fp32+residual epilogue -- same span per tile (tools/ht_trace.py), 23 - 60 spilled VGPRs; and the bias vector parked in
+// lane instead of 4 in the fp32+residual epilogue -- same span per tile, 23 - 60 spilled VGPRs; and the bias vector parked in
 // LDS instead of fetched per tile -- 0.2 us of a 32 us tile: "pass 1" is bound by the issue of the next tile's 128 KiB prologue DMA; and, for
 // GELU tiles, the second wave group doing its arithmetic first and issuing its share of that DMA afterwards -- 1 % slower.
 // The fp32 + residual output pass is bound per CU AND chip-wide at once: with 256 / 128 / 64 workgroups running it takes 22.5 / 20.4 / 16.8 us per
@@ -38,18 +38,13 @@
 // the free LDS by LDS-DMA instead of registers -- 16 KiB in flight per wave, the next tile's prologue deferred -- left a tile at 18.6 us on 64
 // workgroups and 108 us per launch on 256: not a latency problem.)
 #include <algorithm>
-#include <cstdlib>
 
 #include "mb_kernels.h"
 
 namespace mb {
 
 // 16-byte slot swizzle of a 128-byte LDS row (DMA source address and fragment read): slot ^ MB_SWZ(row)
-#ifdef MB_SWZ_ROW
-#define MB_SWZ(r) ((r) & 7)
-#else
 #define MB_SWZ(r) (((r) >> 1) & 7)
-#endif
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -69,14 +64,6 @@ typedef h16 h16x16 __attribute__((ext_vector_type(16)));
 // epilogue emits out_c = f(acc_c), out_u = f(acc_c + acc_delta): the rounding error of the conditional operand is common to both
 // streams and cancels in (c - u), which is what the guidance scale multiplies.  The class-token m-tile carries two rows (lane rows 0 / 1 =
 // class row of c / its difference row); both tiles of a sequence pair compute it, the second one stores it.
-// Timeline instrumentation (tools/ht_trace.py builds its own copy with -DMB_HT_TRACE; never in the product library): wave 0 of every workgroup
-// stamps the 100 MHz wall clock at the phase boundaries of its first 8 tiles -> trace[workgroup][tile][8].
-#ifdef MB_HT_TRACE
-__device__ long long* g_ht_trace = nullptr;
-#define MB_TRACE(k) do { if (g_ht_trace && tid == 0 && trace_it < 8) g_ht_trace[((size_t)blockIdx.x * 8 + trace_it) * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define MB_TRACE(k) do { } while (0)
-#endif
 
 // XP = 6 (round 4): MX-fp4 correction passes as MINI-TILES between the fp16 K-tiles (GemmArgs.lo / nlo).  A mini-tile = 128 token rows (pair
 // tiles: the conditional rows; plain tiles: one 128-row half of the sequence) x the tile's 256 weight rows x 128 K-elements = 8 + 16 KiB in a
@@ -176,20 +163,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
     // X: the class-token row of this sequence, 8 identical source rows (only LDS row 0 is ever consumed)
     p.offX = (uint32_t)(PAIR ? p.cls + ((lane_o >> 3) == 1 ? a.pair_rows : 0) : min(p.cls, a.M - 1)) * (uint32_t)KA + ((lane_o & 7) ^ MB_SWZ(lane_o >> 3)) * 8;
   };
-  // trace builds, modes 3 / 4: the K loop's DMA is dropped / re-reads K-tiles 0 and 1 (always L2 hits) -- what the loop costs without (slow) memory
-#if defined(MB_HT_TRACE) && MB_HT_TRACE == 3
-#define MB_TRACE_DMA(t) if ((t) >= 2) return
-#elif defined(MB_HT_TRACE) && MB_HT_TRACE == 4
-#define MB_TRACE_DMA(t) t &= 1
-#else
-#define MB_TRACE_DMA(t)
-#endif
   auto dma_x = [&](const Plan& p, int t) {
-    MB_TRACE_DMA(t);
     if (SEQ && wave == 7) MB_GLDS16_AUX((t < nka ? a.A : Alo) + p.offX + (t < nka ? t : t - nka) * 64, smem + (t & 1) * PAR_BYTES + 2 * AH_BYTES + 2 * BH_BYTES, AUX);
   };
   auto dma_a = [&](const Plan& p, int t, int h) {
-    MB_TRACE_DMA(t);
     char* buf = smem + (t & 1) * PAR_BYTES + h * AH_BYTES;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -200,7 +177,6 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   };
   auto dma_b = [&](const Plan& p, int t, int h) {
     if (HN && h == 1) return;                          // half-column tiles stage one B half (in the B0 slot)
-    MB_TRACE_DMA(t);
     char* buf = smem + (t & 1) * PAR_BYTES + 2 * AH_BYTES + h * BH_BYTES;
 #pragma unroll
     for (int j = 0; j < (QN ? 1 : 2); ++j) {
@@ -310,15 +286,6 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   __builtin_amdgcn_sched_barrier(0);                                                                \
   __builtin_amdgcn_s_barrier();
 #define MB_MMA(AH, BH) MB_MMA_DO(AH, BH) MB_MMA_END
-  // experiment (round 6, -DMB_MERGE_PHASES): FOUR barrier crossings per K-tile instead of eight -- the barrier pairs between phases 0 / 1 and between phases
-  // 2 / 3 left out, so a wave group's slots are [L0] [M0 L1 M1] [L2] [M2 L3 M3]; the partner group stays one barrier behind
-#ifdef MB_MERGE_PHASES
-#define MB_MID_END __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0);
-#define MB_MID_SYNC() __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(1);
-#else
-#define MB_MID_END MB_MMA_END
-#define MB_MID_SYNC() MB_SYNC_L()
-#endif
   // one mini-tile: 4 m-tiles of accumulator half AH x 4 n-tiles, one scaled MFMA of K = 128 each; op_sel picks the n-tile's / m-tile's scale byte
 #define MB_MINI_ONE(AH, N, I)                                                                       \
   acc[N][(AH) * MH + (I)] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(                        \
@@ -363,9 +330,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                        // K-tiles 0 and 1 of the first tile are in LDS for everyone
 
-  [[maybe_unused]] int trace_it = 0;
   while (true) {
-    MB_TRACE(0);
     f32x4 acc[4][MT];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -373,35 +338,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 acce[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};   // SEQ: class row x this wave row's 2 n-tiles
     // every tile of a sequence (pair) stages the class row(s), only the last one stores them -- the others skip their MFMAs
-#ifdef MB_NO_CLS                                            /* experiment (timing only): what the class-token rows' MFMAs and fragment reads cost */
-    const bool cls_on = false;
-#else
     const bool cls_on = __builtin_amdgcn_readfirstlane(cur.q) == TPS - 1;
-#endif
     h16x16 xa[MH], wb[2][2];      // wb[0] (the B0 fragments) is kept from phase 0 to phase 3: every operand fragment is read once per K-tile
 
     if (grp == 1) __builtin_amdgcn_s_barrier();        // stagger: group 1 runs one barrier behind
-  // trace builds only (tools/ht_trace.py, HT_DEFS): leave parts of the mini-tile machinery out -- results are garbage, timing only
-#ifdef MB_MINI_NO_PHASE
-#define MB_MINI_PHASE_ON false
-#else
-#define MB_MINI_PHASE_ON true
-#endif
-#ifdef MB_MINI_NO_DMA
-#define MB_MINI_X_DMA(...)
-#else
-#define MB_MINI_X_DMA(...) __VA_ARGS__
-#endif
-#ifdef MB_MINI_NO_READ
-#define MB_MINI_X_READ(...) _Pragma("unroll") for (int n = 0; n < 4; ++n) { mwb[n] = i32x4{lo_, lo_, lo_, lo_}; mxa[n] = i32x4{lo_, lo_, lo_, lo_}; }
-#else
-#define MB_MINI_X_READ(...) __VA_ARGS__
-#endif
-#ifdef MB_MINI_NO_MMA
-#define MB_MINI_X_MMA(...) asm volatile("" :: "v"(mwb[0]), "v"(mwb[1]), "v"(mwb[2]), "v"(mwb[3]), "v"(mxa[0]), "v"(mxa[1]), "v"(mxa[2]), "v"(mxa[3]), "v"(mwsel), "v"(mxs));
-#else
-#define MB_MINI_X_MMA(...) __VA_ARGS__
-#endif
 #define MB_KTILE MB_KTILE_(0)
 #define MB_KTILE_(MAH)              /* MAH: plain tiles with mini-tiles: the accumulator half this K loop's mini-tiles update (compile time) */ \
     {                                                                                                    \
@@ -418,23 +358,23 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       if (SEQ && wm == 0 && cls_on) { xe = frag_set(xe, *(const h16x8*)(par + xo[0]), 0); xe = frag_set(xe, *(const h16x8*)(par + xo[1]), 1); } \
       MB_SYNC_L() \
       if (SEQ && wm == 0 && cls_on) { _Pragma("unroll") for (int n = 0; n < (QN ? 1 : 2); ++n) acce[n] = mma_tile(acce[n], wb[0][n], xe); } \
-      MB_MMA_DO(0, 0) MB_MID_END \
+      MB_MMA_DO(0, 0) MB_MMA_END \
       /* ---- phase 1: (A0, B1) [+ class row x B1 for wave row 1]; refill A1 of the other parity with K-tile t+1 */ \
       if constexpr (!HN) { MB_LOAD_B(1) } \
       if (!HN && SEQ && wm == 1 && cls_on) { xe = frag_set(xe, *(const h16x8*)(par + xo[0]), 0); xe = frag_set(xe, *(const h16x8*)(par + xo[1]), 1); } \
       /* MINI: the next mini-tile's scale dword and A part go out first (older than everything the phase-3 wait leaves in flight) */ \
       const bool mini_issue = MINI && t >= 1 && (mini_every || !(t & 1)); \
       const int mini_j = mini_every ? t : (t >> 1); \
-      if (MINI && mini_issue) { mini_scale_issue(cur, mini_j); MB_MINI_X_DMA(mini_dma_a(cur, mini_j);) } \
+      if (MINI && mini_issue) { mini_scale_issue(cur, mini_j); mini_dma_a(cur, mini_j); } \
       if (n1) dma_a(cur, t + 1, 1); \
-      MB_MID_SYNC() \
+      MB_SYNC_L() \
       if (!HN && SEQ && wm == 1 && cls_on) { _Pragma("unroll") for (int n = 0; n < 2; ++n) acce[n] = mma_tile(acce[n], wb[1][n], xe); } \
       if constexpr (!HN) { MB_MMA_DO(0, 1) } MB_MMA_END \
       /* ---- phase 2: (A1, B1); refill A0 of this parity with K-tile t+2 */ \
       MB_LOAD_A(1) \
-      if (MINI && mini_issue) { MB_MINI_X_DMA(mini_dma_b(cur, mini_j);) } \
+      if (MINI && mini_issue) { mini_dma_b(cur, mini_j); } \
       if (n2) dma_a(cur, t + 2, 0); \
-      MB_SYNC_L() if (!HN) { MB_MMA_DO(1, 1) } MB_MID_END \
+      MB_SYNC_L() if (!HN) { MB_MMA_DO(1, 1) } MB_MMA_END \
       /* ---- phase 3: (A1, B0), B0 still in registers: no LDS reads; refill B1, X and B0 of this parity with K-tile t+2; K-tile t+1 must have landed. */ \
       /* In K-tile 0 nothing is waited for: K-tile 1 arrived with the prologue, and the previous tile's output */ \
       /* stores stay in flight until the wait of K-tile 1. */ \
@@ -461,22 +401,21 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
           else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); \
         } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
       } \
-      MB_MID_SYNC() MB_MMA_DO(1, 0) MB_MMA_END \
+      MB_SYNC_L() MB_MMA_DO(1, 0) MB_MMA_END \
       /* ---- phase 4 (MINI): the mini-tile that landed under this (or the previous) K-tile's wait x the accumulators of its 128 token rows */ \
       if constexpr (MINI) { \
-        if (MB_MINI_PHASE_ON && (mini_every || (t & 1))) { \
+        if (mini_every || (t & 1)) { \
           const int mj = mini_every ? t : (t >> 1); \
           int lo_ = lane; \
           asm volatile("" : "+v"(lo_)); \
           const int mfo = (lo_ & 15) * 64 + (((lo_ >> 4) ^ ((lo_ >> 1) & 3)) * 16); \
           const char* mbuf = smem + MINI_OFF; \
           i32x4 mxa[4], mwb[4]; \
-          MB_MINI_X_READ( \
           _Pragma("unroll") for (int n = 0; n < NTW; ++n) mwb[n] = *(const i32x4*)(mbuf + MINI_A + (wn * (64 / NS) + n * 16) * 64 + mfo); \
-          _Pragma("unroll") for (int i = 0; i < 4; ++i) mxa[i] = *(const i32x4*)(mbuf + (wm * 64 + i * 16) * 64 + mfo); ) \
+          _Pragma("unroll") for (int i = 0; i < 4; ++i) mxa[i] = *(const i32x4*)(mbuf + (wm * 64 + i * 16) * 64 + mfo); \
           const int mwsel = HN ? (int)((uint32_t)mws >> ((32 / NS) * cur.hb)) : mws;   /* (column-split tiles: the bytes of this tile's n-tiles) */ \
           MB_SYNC_L() \
-          MB_MINI_X_MMA(if constexpr (QN) { MB_MINI_MMA_QN(MAH) } else if constexpr (HN) { MB_MINI_MMA_HN(MAH) } else { MB_MINI_MMA(MAH) }) \
+          if constexpr (QN) { MB_MINI_MMA_QN(MAH) } else if constexpr (HN) { MB_MINI_MMA_HN(MAH) } else { MB_MINI_MMA(MAH) } \
           /* (v_mfma_scale results must not be read by a VALU copy too early, see the class-row blocks above) */ \
           asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); \
           MB_MMA_END \
@@ -494,11 +433,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
     }
 #undef MB_KTILE
 #undef MB_KTILE_
-#undef MB_MINI_X_DMA
-#undef MB_MINI_X_READ
-#undef MB_MINI_X_MMA
     if (grp == 0) __builtin_amdgcn_s_barrier();        // balance the barrier count of the two groups
-    MB_TRACE(1);
 
     const float* __restrict__ resp = a.residual;
     float* __restrict__ out32 = a.out_f32;
@@ -609,13 +544,11 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
         }
       }
     }
-    MB_TRACE(2);
     // The next tile's first K-tiles must be in LDS before anyone reads them.  Every wave waits for ITS share of that DMA here, while nothing of this
     // tile is stored yet (so the wait does not cover store acknowledgements), then issues its stores, and the workgroup barrier comes AFTER the stores
     // (round 3; it used to stand here): with the GELU epilogue the two waves of a SIMD finish their arithmetic 3.8 us apart, and the leading
     // group's stores now go out under the trailing group's arithmetic instead of after it.
     if (has_next) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MB_TRACE(3);
     if constexpr (SEQ && EPI == EPI_GELU_H16) {
       if (a.out4) {
         // e2m1 copy of the (conditional) GELU outputs for the next GEMM's weight-correction mini-tiles: this wave's 64 columns of a row are one scale
@@ -624,17 +557,14 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
         const uint32_t blk = (uint32_t)(n0 >> 6) + wn;
         const uint32_t nsq = (uint32_t)(PAIR ? a.pair_rows : a.M) / (uint32_t)SQ;
         const uint32_t ngrp = (uint32_t)TPS * (PAIR ? 2 : 4);
-        // a lane's four n-tiles are 2 bytes each (4 columns): as 2-byte stores they cost 13.6 us of a 372 us FFN-up launch (A/B, MB_NO_OUT4_STORE).
+        // a lane's four n-tiles are 2 bytes each (4 columns): as 2-byte stores they cost 13.6 us of a 372 us FFN-up launch (measured A/B).
         // Two lane exchanges give every lane 8 CONSECUTIVE bytes of the row's 32-byte block instead: the odd / even lane-row swap of the fp16
         // stores (n-tiles 2pr <-> 2pr + 1: a lane then holds 8 columns of one n-tile), then the lane halves (g <-> g ^ 2: the neighbouring 8 columns)
-        auto emit4 = [&](uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint8_t* dst, uint32_t row, [[maybe_unused]] float mul) {
+        auto emit4 = [&](uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint8_t* dst, uint32_t row) {
           const auto sw = __builtin_amdgcn_permlane16_swap((p0 & 0xffffu) | (p2 << 16), (p1 & 0xffffu) | (p3 << 16), false, false);
           const uint32_t q0 = __builtin_amdgcn_perm(sw[1], sw[0], 0x05040100u);      // 32-column group 0: this lane's 4 columns | its neighbour's
           const uint32_t q1 = __builtin_amdgcn_perm(sw[1], sw[0], 0x07060302u);      // 32-column group 1
           const auto sx = __builtin_amdgcn_permlane32_swap(q0, q1, false, false);    // lanes < 32: group 0 of lanes g, g + 2; lanes >= 32: group 1 of g - 2, g
-#ifdef MB_NO_OUT4_STORE                                     /* experiment (timing only): what the stores of the e2m1 copy cost */
-          if (mul == 12345.0f)
-#endif
           *(uint2*)(dst + (size_t)row * 2 * a.N + ((n0 + wn * 64) >> 1) + (ge >> 1) * 16 + (ge & 1) * 8) = make_uint2(sx[0], sx[1]);
         };
 #pragma unroll
@@ -654,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
             sc4 |= fp4_scale_byte_nosat(am) << (8 * ii);
             emit4(fp4_pack4(acc[0][i][0], acc[0][i][1], acc[0][i][2], acc[0][i][3], mul), fp4_pack4(acc[1][i][0], acc[1][i][1], acc[1][i][2], acc[1][i][3], mul),
                   fp4_pack4(acc[2][i][0], acc[2][i][1], acc[2][i][2], acc[2][i][3], mul), fp4_pack4(acc[3][i][0], acc[3][i][1], acc[3][i][2], acc[3][i][3], mul),
-                  a.out4, row, mul);
+                  a.out4, row);
             if (a.out4l) {                                   // (precision 4) the fp16 lo halves of the same values: what the fp16 store below rounds away
               f32x4 l[4];
               float aml = 0.f;
@@ -666,7 +596,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
               const float mull = fp4_scale_mul_nosat(aml);
               sl4 |= fp4_scale_byte_nosat(aml) << (8 * ii);
               emit4(fp4_pack4(l[0][0], l[0][1], l[0][2], l[0][3], mull), fp4_pack4(l[1][0], l[1][1], l[1][2], l[1][3], mull),
-                    fp4_pack4(l[2][0], l[2][1], l[2][2], l[2][3], mull), fp4_pack4(l[3][0], l[3][1], l[3][2], l[3][3], mull), a.out4l, row, mull);
+                    fp4_pack4(l[2][0], l[2][1], l[2][2], l[2][3], mull), fp4_pack4(l[3][0], l[3][1], l[3][2], l[3][3], mull), a.out4l, row);
             }
           }
           const uint32_t gq = PAIR ? (uint32_t)tq * 2 + wm : (uint32_t)tq * 4 + wm * 2 + hh;
@@ -804,14 +734,6 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       if ((EPI == EPI_H16 || EPI == EPI_GELU_H16) && a.sat && (satnan || !(satm <= MB_H16_MAX))) atomicAdd(a.sat, 1u);   // (a NaN counts too)
     }
     if (has_next) __builtin_amdgcn_s_barrier();        // everyone's share of the next tile's K-tiles 0 and 1 has landed (each wave waited above)
-    MB_TRACE(4);
-#ifdef MB_HT_TRACE
-#if MB_HT_TRACE >= 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (mode 2 only: when the stores are acknowledged; changes the overlap with the next tile)
-    MB_TRACE(5);
-#endif
-    ++trace_it;
-#endif
     if (!has_next) break;
     cur = nxt;
     vb = nvb;
@@ -828,7 +750,6 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
 #undef MB_MINI_MMA_QN
 }
 
-static const int g_col_split = getenv("MASKBIT_AMD_COL_SPLIT") ? atoi(getenv("MASKBIT_AMD_COL_SPLIT")) : 4;   // A/B switch (experiments): largest column split of small-batch tiles (1 = whole tiles only)
 static int g_cu_override = 0;   // mb_set_cu_count: the CUs a persistent grid is sized for (a stream created with a CU mask sees fewer than the device has)
 void set_cu_count(int n) { g_cu_override = n > 0 ? n : 0; }
 static int num_cu_cached() {
@@ -839,9 +760,6 @@ static int num_cu_cached() {
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev);
     if (num_cu <= 0) num_cu = 256;
-#ifdef MB_HT_TRACE
-    if (getenv("MASKBIT_AMD_HT_GRID")) num_cu = atoi(getenv("MASKBIT_AMD_HT_GRID"));   // trace builds: fewer persistent workgroups than CUs
-#endif
   }
   return num_cu;
 }
@@ -857,8 +775,6 @@ static void launch_ht(hipStream_t s, const GemmArgs& a, bool persistent = true) 
   }
   const int sq_rows = a.seq_rows ? a.seq_rows : 257;
   const int tiles_m = PAIR ? (a.pair_rows / sq_rows) * ((sq_rows - 1) / 128) : (SEQ ? (a.M / sq_rows) * ((sq_rows - 1) / 256) : (a.M + BM - 1) / BM), tiles_n = (a.N / 256) * NS;
-  static const bool res_persist = !getenv("MASKBIT_AMD_RES_PERSIST") || atoi(getenv("MASKBIT_AMD_RES_PERSIST")) != 0;   // A/B switch (experiments)
-  if (EPI == EPI_RES_F32 && !res_persist) persistent = false;
   const int grid = persistent ? std::min(tiles_m * tiles_n, num_cu_cached()) : tiles_m * tiles_n;   // persistent: one workgroup per CU walks the tile list
   hipLaunchKernelGGL((gemm_ht_kernel<MT, EPI, XP, SEQ, PAIR, NS>), dim3(grid), dim3(512), LDS, s, a, tiles_m, tiles_n);
 }
@@ -904,8 +820,8 @@ void gemm_ht(hipStream_t s, GemmEpi epi, const GemmArgs& a, int mt) {
       case EPI_RES_F32:
         if (a.pair_rows) launch_ht<8, EPI_RES_F32, 6, true, true>(s, a, persistent);
         // few sequences: quarter- / half-column tiles when whole tiles would leave three quarters / half of the CUs idle (bit-identical results: see the kernel)
-        else if (seq_tiles * (a.N / 256) * 4 <= num_cu_cached() && g_col_split >= 4) launch_ht<8, EPI_RES_F32, 6, true, false, 4>(s, a, persistent);
-        else if (seq_tiles * (a.N / 256) * 2 <= num_cu_cached() && g_col_split >= 2) launch_ht<8, EPI_RES_F32, 6, true, false, 2>(s, a, persistent);
+        else if (seq_tiles * (a.N / 256) * 4 <= num_cu_cached()) launch_ht<8, EPI_RES_F32, 6, true, false, 4>(s, a, persistent);
+        else if (seq_tiles * (a.N / 256) * 2 <= num_cu_cached()) launch_ht<8, EPI_RES_F32, 6, true, false, 2>(s, a, persistent);
         else launch_ht<8, EPI_RES_F32, 6, true>(s, a, persistent);
         break;
       default: break;
@@ -935,7 +851,3 @@ void gemm_ht(hipStream_t s, GemmEpi epi, const GemmArgs& a, int mt) {
 }
 
 }  // namespace mb
-
-#ifdef MB_HT_TRACE
-extern "C" int mb_debug_ht_trace(long long* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(mb::g_ht_trace), &p, sizeof(p)); }
-#endif

@@ -3,28 +3,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// 16-bit storage type of activations and packed weights.  IEEE fp16 by default: the sampler feeds its
-// own output back for 64 steps and classifier-free guidance multiplies logit errors by up to ~8x,
-// so the 8-bit mantissa of bf16 costs ~1e-2 token mismatch against the fp32 reference where fp16's
-// 11 bits give ~1e-3 at the same MFMA rate (measured; DESIGN.md "Precision").  Build with
-// -DMB_HALF_BF16=1 to get the bf16 variant for A/B runs.  Accumulation is always fp32.
-#ifndef MB_HALF_BF16
-#define MB_HALF_BF16 0
-#endif
-#if MB_HALF_BF16
-typedef __bf16 h16;
-#define MB_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-#define MB_H16_MAX 3.3e38f
-#else
+// 16-bit storage type of activations and packed weights: IEEE fp16.  The sampler feeds its own output
+// back for 64 steps and classifier-free guidance multiplies logit errors by up to ~8x, so the 8-bit
+// mantissa of bf16 costs ~1e-2 token mismatch against the fp32 reference where fp16's 11 bits give
+// ~1e-3 at the same MFMA rate (measured; DESIGN.md "Precision").  Accumulation is always fp32.
 typedef _Float16 h16;
 #define MB_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 #define MB_H16_MAX 65504.0f
-#endif
 typedef __attribute__((ext_vector_type(2))) h16 h16x2;
 typedef __attribute__((ext_vector_type(4))) h16 h16x4;
 typedef __attribute__((ext_vector_type(8))) h16 h16x8;
 
-// fp32 -> storage half with saturation instead of +-inf (fp16 only; a no-op clamp for bf16)
+// fp32 -> fp16 with saturation instead of +-inf
 __device__ __forceinline__ h16 to_h(float x) { return (h16)__builtin_amdgcn_fmed3f(x, -MB_H16_MAX, MB_H16_MAX); }
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -79,9 +69,6 @@ __device__ __forceinline__ float rows_sum(float v) {
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
-#ifdef MB_NO_GELU                                           /* experiment (timing only): what the GELU arithmetic of the FFN-up epilogue costs */
-  return x;
-#endif
   const float a0 = fabsf(x.x), a1 = fabsf(x.y);
   const f32x2 t = {__builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, a0, 1.0f)),
                    __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, a1, 1.0f))};

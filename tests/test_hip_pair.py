@@ -182,10 +182,10 @@ def test_pair_attention_e2m1_copy_of_the_conditional_outputs(pairs, N):
 
 
 @pytest.mark.timeout(900)
-def test_activation_lo_coverage_knob_and_mode_identities():
+def test_activation_lo_handle_mask_and_mode_identities():
     """The precision modes are nested selections of the same machinery, bit for bit (full-width two-layer generator, guided forward of 3 pairs):
-    precision 4 with its activation-lo sets switched off (mb_gen_set_alo mask 0) IS precision 2; precision 4 narrowed to out-proj + FFN-up (mask 6) IS precision 3;
-    the knob refuses what the handle was not built with; and mb_sample at precision 4 equals the forward + step composition in which EVERY step of a guided run --
+    precision 4 with its activation-lo sets switched off (mb_gen_set_alo mask 0 on the engine handle) IS precision 2; precision 4 narrowed to out-proj + FFN-up
+    (mask 6) IS precision 3; mb_gen_set_alo refuses what the handle was not built with (QKV at precision 4, FFN-down at precision 3); and mb_sample at precision 4 equals the forward + step composition in which EVERY step of a guided run --
     the zero-scale ones too -- takes the guided forward."""
     from maskbit_amd import _lib
     from maskbit_amd.sampling import build_plan, draw_noise, run_loop
@@ -199,22 +199,23 @@ def test_activation_lo_coverage_knob_and_mode_identities():
     y = torch.tensor([5, 321, 999], device=DEV)
     out = {}
     for prec in (2, 3, 4):
-        m.precision, m.alo_mask = prec, None
+        m.precision = prec
         out[prec] = m.forward_cfg(t, y)
     assert not torch.equal(out[2], out[3]) and not torch.equal(out[3], out[4])
-    m.precision, m.alo_mask, m.alo_from = 4, 0, 0
+    m.precision = 4
+    _lib.check(lib.mb_gen_set_alo(m.engine(3), 0), "mb_gen_set_alo")
     assert torch.equal(m.forward_cfg(t, y), out[2])
-    m.alo_mask = 6
+    _lib.check(lib.mb_gen_set_alo(m.engine(3), 6), "mb_gen_set_alo")
     assert torch.equal(m.forward_cfg(t, y), out[3])
-    m.alo_mask = 14
+    _lib.check(lib.mb_gen_set_alo(m.engine(3), 14), "mb_gen_set_alo")
     assert torch.equal(m.forward_cfg(t, y), out[4])
-    m.alo_mask = 15                                                  # the QKV set: built at precision 4 for coverage studies, not run by default
-    assert not torch.equal(m.forward_cfg(t, y), out[4])
-    m.precision, m.alo_mask = 3, 14                                  # a precision-3 handle holds the operands of out-proj + FFN-up only
+    with pytest.raises(RuntimeError, match="created"):              # a precision-4 handle holds no QKV set
+        _lib.check(lib.mb_gen_set_alo(m.engine(3), 15), "mb_gen_set_alo")
+    m.precision = 3                                                  # a precision-3 handle holds the operands of out-proj + FFN-up only
     with pytest.raises(RuntimeError, match="created"):
-        m.forward_cfg(t, y)
+        _lib.check(lib.mb_gen_set_alo(m.engine(3), 14), "mb_gen_set_alo")
     # mb_sample at precision 4 == composition with the guided forward at every step (cosine annealing: the scale of steps 0 .. 2 is exactly 0)
-    m.precision, m.alo_mask = 4, None
+    m.precision = 4
     N, B = 8, 3
     plan = build_plan(N, 512, 7.1, "cosine", 3.0, 1.0, False, "arccos")
     assert plan[0][0] == 0.0 and plan[0][-1] != 0.0

@@ -1,4 +1,4 @@
-"""Decode time of B images (uint8 path), mean of n calls.  MASKBIT_AMD_CONV_TH=8 / 16 forces the conv tile height (read once per process).
+"""Decode time of B images (uint8 path), mean of n calls.
 usage: [DEC_TIME_LIB=other.so] python tools/dec_time.py [B=64] [n=10]"""
 import os, sys, time
 import torch
@@ -27,4 +27,4 @@ for rep in range(3):
     for _ in range(n): u8 = tok.decode_tokens_uint8(t)
     torch.cuda.synchronize()
     ts.append((time.perf_counter() - t0) / n * 1e3)
-print(f"decode of {B} images, conv tile height {os.environ.get('MASKBIT_AMD_CONV_TH', 'auto')}: {' / '.join(f'{x:.2f}' for x in ts)} ms; checksum {int((u8[1] if isinstance(u8, tuple) else u8).long().sum())}")
+print(f"decode of {B} images: {' / '.join(f'{x:.2f}' for x in ts)} ms; checksum {int((u8[1] if isinstance(u8, tuple) else u8).long().sum())}")
