@@ -1,5 +1,5 @@
 /* libmaskbit_hip.so -- DIAGNOSTIC entry points: single kernels of the engine on caller buffers, for the unit tests (tests/test_hip_gemm.py,
- * test_hip_pair.py) and the tools under tools/.  Nothing here is part of the reference's surface and no host binding of the product needs it:
+ * test_hip_pair.py, test_hip_conv.py) and the tools under tools/.  Nothing here is part of the reference's surface and no host binding of the product needs it:
  * include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered, 0 / negative return, mb_last_error()).
  */
 #ifndef MASKBIT_HIP_DIAG_H
@@ -75,6 +75,30 @@ int mb_set_cu_count(int n);
  * idx int64 [N] = argmin_j ||z - e_j||^2 (ties to the lowest index), dist fp32 [N] (may be NULL) = that squared distance; splits = codebook splits
  * across workgroups (0 = automatic; clamped to [1, min(64, C / 64 rounded up)]). */
 int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream);
+
+/* ---- single tokenizer layers (decoder.hip) on caller buffers, through the handle's own launch_conv / launch_gn / weight repack on a scratch
+ * context.  These four synchronise the stream.
+ * mb_conv_layer: one convolution.  in_h16 = fp16 NHWC [B, Hin, Win, Cin] with the TRUE channel count (padded to 64-channel chunks inside);
+ * (Hin, Win) = (H, W), or (H / 2, W / 2) with `up` (nearest-2x upsampling fused into the 3x3 conv), or (2 H, 2 W) for ks 2 = the stride-2 3x3 TF-"same"
+ * conv (one zero row / column after), run as a 2x2 conv on the space-to-depth input (s2d_kernel; Cin % 16 == 0).  w_oihw = fp32 [Cout, Cin, k, k] with
+ * k = 3 for ks 2 and 3, 1 for ks 1, repacked by the product's kernel; bias fp32 [Cout] or NULL; gn_gamma / gn_beta [Cin] or both NULL: the
+ * GroupNorm(32 groups, eps 1e-6) + SiLU prologue, statistics by the sweep (Cin % 64 == 0; not with ks 2); residual_h16 [B, H, W, Cout] or NULL.
+ * H % 8 == 0, W % 16 == 0.  Outputs: out_h16 [B, H, W, Cout] (Cout % 4 == 0), or with final_layer (ks 3, Cout <= 4) img_nchw fp32 [B, Cout, H, W]
+ * and / or img_nhwc_u8 [B, H, W, Cout] = trunc(clamp(v, 0, 1) * 255).  *saturated (host) = 4-channel groups clamped at +-65504.
+ * out_gn_part (optional, B * tiles * 64 floats) = the GroupNorm partials [B][tile][32 groups][sum, sumsq] the epilogue wrote for the output and
+ * *part_tiles (host) their pixel tiles per image (0: the epilogue wrote none -- Cout % 128 != 0, or channels per group not 4 / 8 / 16).
+ * out_scale_shift (optional, with out_gamma / out_beta [Cout], Cout % 32 == 0) = [B, Cout] (scale, shift) of the OUTPUT's GroupNorm as the next
+ * layer would get them: from the epilogue's partials when there are any, else by the sweep. */
+int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
+                  void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
+                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
+                  mb_stream stream);
+/* GroupNorm statistics of x fp16 [B, HW, C] by the sweep (gn_partial_kernel + gn_finalize_kernel): scale_shift [B, C] pairs with
+ * scale = gamma * rstd, shift = beta - mean * scale; C % 32 == 0, C <= 2048. */
+int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream);
+/* avg_pool2d(2, 2) / space-to-depth of x fp16 [B, H, W, C] -> [B, H/2, W/2, C] / [B, H/2, W/2, 4 C] (channel (py * 2 + px) * C + c); C % 8 == 0. */
+int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
+int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
 
 #ifdef __cplusplus
 }

@@ -315,18 +315,21 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const h16* __restrict__
 #pragma unroll
   for (int e = 0; e < 8; ++e) { red[0][pl * C + slot * 8 + e] = s[e]; red[1][pl * C + slot * 8 + e] = q[e]; }
   __syncthreads();
+  // The upper levels of the reduction add few, large, same-signed terms: in fp32 each of those additions costs up to half an ulp of the TOTAL, and
+  // var = E[x^2] - mean^2 magnifies that by mean^2 / var (4 096 for a group whose |mean| is 64 x its std).  They run in fp64 (a handful of
+  // additions per thread); only the many leaf sums above stay fp32, where the errors are small against the total and average out.
   for (int c = tid; c < C; c += 256) {               // fixed-order sum over pixel lanes
-    float ts = 0.f, tq = 0.f;
-    for (int l = 0; l < npl; ++l) { ts += red[0][l * C + c]; tq += red[1][l * C + c]; }
-    red[0][c] = ts; red[1][c] = tq;                  // row 0 of the scratch is only read by thread c here
+    double ts = 0.0, tq = 0.0;
+    for (int l = 0; l < npl; ++l) { ts += (double)red[0][l * C + c]; tq += (double)red[1][l * C + c]; }
+    red[0][c] = (float)ts; red[1][c] = (float)tq;    // row 0 of the scratch is only read by thread c here
   }
   __syncthreads();
   if (tid < 32) {
     const int cpg = C / 32;
-    float ts = 0.f, tq = 0.f;
-    for (int e = 0; e < cpg; ++e) { ts += red[0][tid * cpg + e]; tq += red[1][tid * cpg + e]; }
+    double ts = 0.0, tq = 0.0;
+    for (int e = 0; e < cpg; ++e) { ts += (double)red[0][tid * cpg + e]; tq += (double)red[1][tid * cpg + e]; }
     float* o = part + (((size_t)b * nchunk + chunk) * 32 + tid) * 2;
-    o[0] = ts; o[1] = tq;
+    o[0] = (float)ts; o[1] = (float)tq;
   }
 }
 
@@ -334,24 +337,26 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
                                                            const float* __restrict__ beta, float2* __restrict__ out, int HW, int C, int nchunk) {
   // 256 threads = 32 groups x 8 chunk lanes: lane l sums chunks l, l+8, ... in order, then the 8 lanes are summed in order (fixed association:
   // bit-stable run to run whatever produced the partials)
-  __shared__ float red[2][8][32];
+  // The per-tile partials are combined, and the variance formed, in fp64: E[x^2] - mean^2 cancels mean^2 / var leading digits (12 bits for a group whose
+  // |mean| is 64 x its std -- trained decoders show such groups), and fp32 sums of up to 256 same-signed partials alone lose 2 - 3 bits of the 24.
+  __shared__ double red[2][8][32];
   __shared__ float2 ms[32];
   const int b = blockIdx.x, grp = threadIdx.x & 31, l = threadIdx.x >> 5;
   const int cpg = C / 32;
-  float ts = 0.f, tq = 0.f;
+  double ts = 0.0, tq = 0.0;
   for (int k = l; k < nchunk; k += 8) {
     const float* o = part + (((size_t)b * nchunk + k) * 32 + grp) * 2;
-    ts += o[0]; tq += o[1];
+    ts += (double)o[0]; tq += (double)o[1];
   }
   red[0][l][grp] = ts; red[1][l][grp] = tq;
   __syncthreads();
   if (threadIdx.x < 32) {
-    ts = 0.f; tq = 0.f;
+    ts = 0.0; tq = 0.0;
     for (int k = 0; k < 8; ++k) { ts += red[0][k][grp]; tq += red[1][k][grp]; }
-    const float n = (float)HW * (float)cpg;
-    const float mean = ts / n;
-    const float var = fmaxf(tq / n - mean * mean, 0.f);
-    ms[grp] = make_float2(mean, rsqrtf(var + 1e-6f));
+    const double n = (double)HW * (double)cpg;
+    const double mean = ts / n;
+    const double var = fmax(tq / n - mean * mean, 0.0);
+    ms[grp] = make_float2((float)mean, (float)(1.0 / sqrt(var + 1e-6)));
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -468,6 +473,14 @@ struct Conv {
 struct Norm { std::string name; int c = 0; float *g = nullptr, *b = nullptr; };
 struct ResBlock { Norm n1, n2; Conv c1, c2, sc; bool has_sc = false; };
 struct Stage { std::vector<ResBlock> blocks; Conv up; bool has_up = false; };   // `up`: upsample_conv (decoder) / down_conv (encoder)
+// GroupNorm scratch of one stream of layers: what launch_conv leaves for launch_gn.  A handle owns one; the single-layer diagnostic entries
+// (include/maskbit_hip_diag.h) build one on scratch buffers, so that they run the same two helpers.
+struct GnCtx {
+  float* part = nullptr;         // [B][tiles or chunks][32 groups][sum, sumsq]
+  float2* ss = nullptr;          // [B][C] (scale, shift) of the last launch_gn
+  const void* of = nullptr;      // the tensor whose per-tile GroupNorm partials the last conv left in `part` (null: none) ...
+  int ntile = 0;                 // ... and the number of pixel tiles per image they cover
+};
 
 }  // namespace mb
 
@@ -493,10 +506,7 @@ struct mb_dec {
   float* vq_ps = nullptr;        // [VQ_SPLIT_MAX][Npad] per-split best score ...
   int* vq_pi = nullptr;          // ... and its entry
   unsigned* sat = nullptr;  // device counter: fp16 clamps in the conv epilogues since the last read
-  float* gn_part = nullptr;
-  float2* gn_ss = nullptr;
-  const void* gn_of = nullptr;   // the tensor whose per-tile GroupNorm partials the last conv left in gn_part (null: none) ...
-  int gn_ntile = 0;              // ... and the number of pixel tiles per image they cover
+  mb::GnCtx gn;
   std::vector<void*> owned;
 };
 
@@ -513,12 +523,37 @@ bool dalloc(mb_dec* d, T** p, size_t n, std::string& err) {
   return true;
 }
 
-bool init_conv(mb_dec* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool bias, bool up, bool final_,
-               std::string& err) {
-  c.name = name; c.cin = cin; c.cout = cout; c.cout_w = cout; c.ks = ks; c.has_bias = bias; c.up = up; c.sat = d->sat;
+// channel padding of a convolution: input channels to whole 64-channel chunks, output channels to whole 128-channel (final layer: 16-channel) tiles
+void shape_conv(Conv& c, int cin, int cout, int ks, bool bias, bool up, bool final_) {
+  c.cin = cin; c.cout = cout; c.cout_w = cout; c.ks = ks; c.has_bias = bias; c.up = up;
   c.cin_pad = (cin + CK - 1) / CK * CK;
   c.cout_pad = final_ ? 16 : (cout + 127) / 128 * 128;
-  if (!dalloc(d, &c.w, (size_t)ks * ks * c.cout_pad * c.cin_pad, err)) return false;
+}
+// DownsamplingStage.down_conv: 3x3, stride 2, bias (autoencoder.py:165), run as a 2x2 conv on the space-to-depth input
+void shape_down_conv(Conv& c, int ch) {
+  c.cin = ch; c.cout = ch; c.cout_w = ch; c.ks = 2; c.has_bias = true; c.down = true;
+  c.cin_pad = 4 * ch; c.cout_pad = (ch + 127) / 128 * 128;
+}
+size_t conv_weight_elems(const Conv& c) { return (size_t)c.ks * c.ks * c.cout_pad * c.cin_pad; }
+// checkpoint weights (fp32 OIHW, device) -> the kernel's [tap][Cout_pad][Cin_pad] h16
+void repack_weights(hipStream_t s, const Conv& c, const float* data) {
+  if (c.down) hipLaunchKernelGGL(repack_down_kernel, dim3(512), dim3(256), 0, s, data, c.w, c.cout_w, c.cin, c.cout_pad);
+  else hipLaunchKernelGGL(repack_conv_kernel, dim3(512), dim3(256), 0, s, data, c.w, c.cout_w, c.cin, c.ks, c.cout_pad, c.cin_pad);
+}
+void launch_s2d(hipStream_t s, const h16* x, h16* y, int B, int H, int W, int C) {
+  const size_t n8 = (size_t)B * H * W * (C / 8);
+  hipLaunchKernelGGL(s2d_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 + 255) / 256)), dim3(256), 0, s, x, y, B, H, W, C);
+}
+void launch_avgpool2(hipStream_t s, const h16* x, h16* y, int B, int H, int W, int C) {
+  const size_t n8 = (size_t)B * H * W * (C / 8);
+  hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 / 4 + 255) / 256)), dim3(256), 0, s, x, y, B, H, W, C);
+}
+
+bool init_conv(mb_dec* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool bias, bool up, bool final_,
+               std::string& err) {
+  c.name = name; c.sat = d->sat;
+  shape_conv(c, cin, cout, ks, bias, up, final_);
+  if (!dalloc(d, &c.w, conv_weight_elems(c), err)) return false;
   if (bias) {
     if (!dalloc(d, &c.b, (size_t)c.cout_pad, err)) return false;
     (void)hipMemset(c.b, 0, c.cout_pad * sizeof(float));
@@ -537,19 +572,19 @@ bool init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout
   return ok;
 }
 
-void launch_conv(hipStream_t s, mb_dec* d, const Conv& c, const h16* in, const float2* gn, const h16* residual, h16* out,
+void launch_conv(hipStream_t s, GnCtx* gc, const Conv& c, const h16* in, const float2* gn, const h16* residual, h16* out,
                  float* img, uint8_t* u8, int B, int H, int W, bool final_, bool stats = true) {
   // GroupNorm partials of the output ride in the epilogue when a GroupNorm will read it (stats) and its groups are whole lane groups of a tile
   const int cpg = c.cout / 32;
   const bool part = !final_ && stats && c.cout % 128 == 0 && (cpg == 4 || cpg == 8 || cpg == 16);
-  ConvArgs a{in, gn, c.w, c.has_bias ? c.b : nullptr, residual, out, img, u8, B, H, W, c.cin_pad, c.cout, c.cout_pad, c.sat, part ? d->gn_part : nullptr};
-  d->gn_of = part ? (const void*)out : nullptr;
+  ConvArgs a{in, gn, c.w, c.has_bias ? c.b : nullptr, residual, out, img, u8, B, H, W, c.cin_pad, c.cout, c.cout_pad, c.sat, part ? gc->part : nullptr};
+  gc->of = part ? (const void*)out : nullptr;
   const int bn = final_ ? 16 : 128;
   // 16-row tiles (8 waves) for the 3x3 convolutions from 32 x 32 maps on; 8-row tiles below (a 16 x 16 map would be one tile per image).  The choice
   // must not depend on the batch: the GroupNorm partial sums are per tile, and results are bit-identical across batch sizes.
   const bool th16 = !final_ && c.ks == 3 && H % 16 == 0 && H >= 32;
   const int th = th16 ? 16 : TH8;
-  d->gn_ntile = (H / th) * (W / TW);
+  gc->ntile = (H / th) * (W / TW);
   dim3 grid((unsigned)((size_t)B * (H / th) * (W / TW) * (c.cout_pad / bn))), block(32 * th);
   if (final_) hipLaunchKernelGGL((conv_kernel<1, 1, 3, false, true>), grid, block, 0, s, a);
   else if (c.ks == 1) hipLaunchKernelGGL((conv_kernel<4, 2, 1, false, false>), grid, block, 0, s, a);
@@ -560,29 +595,29 @@ void launch_conv(hipStream_t s, mb_dec* d, const Conv& c, const h16* in, const f
   else hipLaunchKernelGGL((conv_kernel<4, 2, 3, false, false>), grid, block, 0, s, a);
 }
 
-void launch_gn(hipStream_t s, mb_dec* d, const Norm& n, const h16* x, int B, int HW) {
-  int nchunk = d->gn_ntile;
-  if (d->gn_of != (const void*)x) {                   // not the tensor the last conv summed (average-pooled tensors of the encoder): sweep it
+void launch_gn(hipStream_t s, GnCtx* gc, const Norm& n, const h16* x, int B, int HW) {
+  int nchunk = gc->ntile;
+  if (gc->of != (const void*)x) {                   // not the tensor the last conv summed (average-pooled tensors of the encoder): sweep it
     nchunk = HW / 256; if (nchunk < 1) nchunk = 1; if (nchunk > GN_MAXCHUNK) nchunk = GN_MAXCHUNK;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, d->gn_part, HW, n.c, nchunk);
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, gc->part, HW, n.c, nchunk);
   }
-  d->gn_of = nullptr;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, d->gn_part, n.g, n.b, d->gn_ss, HW, n.c, nchunk);
+  gc->of = nullptr;
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, gc->part, n.g, n.b, gc->ss, HW, n.c, nchunk);
 }
 
 // x (buffer index xi) -> returns the buffer index holding the block output
 int run_block(hipStream_t s, mb_dec* d, const ResBlock& rb, int xi, int B, int H, int W) {
   const int t1 = (xi + 1) % 3, t2 = (xi + 2) % 3;
-  launch_gn(s, d, rb.n1, d->buf[xi], B, H * W);
-  launch_conv(s, d, rb.c1, d->buf[xi], d->gn_ss, nullptr, d->buf[t1], nullptr, nullptr, B, H, W, false);
-  launch_gn(s, d, rb.n2, d->buf[t1], B, H * W);
+  launch_gn(s, &d->gn, rb.n1, d->buf[xi], B, H * W);
+  launch_conv(s, &d->gn, rb.c1, d->buf[xi], d->gn.ss, nullptr, d->buf[t1], nullptr, nullptr, B, H, W, false);
+  launch_gn(s, &d->gn, rb.n2, d->buf[t1], B, H * W);
   if (!rb.has_sc) {
-    launch_conv(s, d, rb.c2, d->buf[t1], d->gn_ss, d->buf[xi], d->buf[t2], nullptr, nullptr, B, H, W, false);
+    launch_conv(s, &d->gn, rb.c2, d->buf[t1], d->gn.ss, d->buf[xi], d->buf[t2], nullptr, nullptr, B, H, W, false);
     return t2;
   }
   // shortcut quirk (autoencoder.py:72-73,93-96): out = h + nin_shortcut(h); the block input is dropped
-  launch_conv(s, d, rb.c2, d->buf[t1], d->gn_ss, nullptr, d->buf[t2], nullptr, nullptr, B, H, W, false, false);   // read by the shortcut conv, not by a GroupNorm
-  launch_conv(s, d, rb.sc, d->buf[t2], nullptr, d->buf[t2], d->buf[t1], nullptr, nullptr, B, H, W, false);
+  launch_conv(s, &d->gn, rb.c2, d->buf[t1], d->gn.ss, nullptr, d->buf[t2], nullptr, nullptr, B, H, W, false, false);   // read by the shortcut conv, not by a GroupNorm
+  launch_conv(s, &d->gn, rb.sc, d->buf[t2], nullptr, d->buf[t2], d->buf[t1], nullptr, nullptr, B, H, W, false);
   return t1;
 }
 
@@ -665,10 +700,9 @@ mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err, int c
       st.up.cin = cout;
       if (ok && st.has_up && cfg.sample_with_conv) {      // DownsamplingStage.down_conv: 3x3, stride 2, bias (autoencoder.py:165)
         Conv& dc = st.up;
-        dc.name = "encoder.down." + std::to_string(s) + ".down_conv";
-        dc.cin = cout; dc.cout = cout; dc.cout_w = cout; dc.ks = 2; dc.has_bias = true; dc.down = true;
-        dc.cin_pad = 4 * cout; dc.cout_pad = (cout + 127) / 128 * 128;
-        ok = dalloc(d, &dc.w, (size_t)4 * dc.cout_pad * dc.cin_pad, err) && dalloc(d, &dc.b, (size_t)dc.cout_pad, err);
+        dc.name = "encoder.down." + std::to_string(s) + ".down_conv"; dc.sat = d->sat;
+        shape_down_conv(dc, cout);
+        ok = dalloc(d, &dc.w, conv_weight_elems(dc), err) && dalloc(d, &dc.b, (size_t)dc.cout_pad, err);
         if (ok) (void)hipMemset(dc.b, 0, dc.cout_pad * sizeof(float));
       }
     }
@@ -684,8 +718,8 @@ mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err, int c
   for (int i = 0; ok && i < 3; ++i) ok = dalloc(d, &d->buf[i], (size_t)max_batch * max_elems, err);
   const size_t nlat = (size_t)max_batch * cfg.latent_size * cfg.latent_size;
   ok = ok && dalloc(d, &d->z, nlat * d->conv_in.cin_pad, err) &&
-       dalloc(d, &d->gn_part, (size_t)max_batch * std::max(GN_MAXCHUNK, (d->out_res / TH8) * (d->out_res / TW)) * 64, err) &&
-       dalloc(d, &d->gn_ss, (size_t)max_batch * 4096, err);
+       dalloc(d, &d->gn.part, (size_t)max_batch * std::max(GN_MAXCHUNK, (d->out_res / TH8) * (d->out_res / TW)) * 64, err) &&
+       dalloc(d, &d->gn.ss, (size_t)max_batch * 4096, err);
   if (ok && vq) {
     VqCodebook& q = d->q;
     q.C = codebook_size; q.K = cfg.token_size; q.Kp = vq_kp(q.K); q.Cpad = vq_cpad(q.C); q.l2 = l2_normalize ? 1 : 0;
@@ -738,10 +772,10 @@ int dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shap
       if (hipMemcpyAsync(c->b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) { err = "copy failed"; return -10; }
     } else if (c->down) {
       if (numel != (size_t)c->cout_w * c->cin * 9) { err = n + ": wrong weight size"; return -4; }
-      hipLaunchKernelGGL(repack_down_kernel, dim3(512), dim3(256), 0, s, data, c->w, c->cout_w, c->cin, c->cout_pad);
+      repack_weights(s, *c, data);
     } else {
       if (numel != (size_t)c->cout_w * c->cin * c->ks * c->ks) { err = n + ": wrong weight size"; return -4; }
-      hipLaunchKernelGGL(repack_conv_kernel, dim3(512), dim3(256), 0, s, data, c->w, c->cout_w, c->cin, c->ks, c->cout_pad, c->cin_pad);
+      repack_weights(s, *c, data);
     }
     return 0;
   }
@@ -760,7 +794,7 @@ namespace {
 // ConvDecoder.forward (autoencoder.py:399-423) from the latent in d->z
 void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s) {
   int res = d->c.latent_size;
-  launch_conv(s, d, d->conv_in, d->z, nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
+  launch_conv(s, &d->gn, d->conv_in, d->z, nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
   for (auto& rb : d->mid) xi = run_block(s, d, rb, xi, B, res, res);
   for (auto& st : d->up) {
@@ -768,12 +802,12 @@ void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipS
     if (st.has_up) {
       res *= 2;
       const int t = (xi + 1) % 3;
-      launch_conv(s, d, st.up, d->buf[xi], nullptr, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
+      launch_conv(s, &d->gn, st.up, d->buf[xi], nullptr, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
       xi = t;
     }
   }
-  launch_gn(s, d, d->norm_out, d->buf[xi], B, res * res);
-  launch_conv(s, d, d->conv_out, d->buf[xi], d->gn_ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, res, res, true);
+  launch_gn(s, &d->gn, d->norm_out, d->buf[xi], B, res * res);
+  launch_conv(s, &d->gn, d->conv_out, d->buf[xi], d->gn.ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, res, res, true);
 }
 }  // namespace
 
@@ -816,32 +850,29 @@ int encode_to_z(mb_dec* d, const float* img, int B, hipStream_t s, int* res_out)
   const size_t npix = (size_t)B * res * res;
   hipLaunchKernelGGL(pack_image_kernel, dim3((unsigned)std::min<size_t>(4096, (npix * 8 + 255) / 256)), dim3(256), 0, s,
                      img, d->buf[2], B, c.num_channels, res, res);
-  launch_conv(s, d, d->e_conv_in, d->buf[2], nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
+  launch_conv(s, &d->gn, d->e_conv_in, d->buf[2], nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
   for (auto& st : d->e_down) {
     for (auto& rb : st.blocks) xi = run_block(s, d, rb, xi, B, res, res);
     if (st.has_up) {
       const int t = (xi + 1) % 3, t2 = (xi + 2) % 3;
-      const size_t n8 = (size_t)B * res * res * (st.up.cin / 8);
       if (!c.sample_with_conv) {                           // F.avg_pool2d(2, 2) (autoencoder.py:182)
-        hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 / 4 + 255) / 256)), dim3(256), 0, s, d->buf[xi], d->buf[t], B, res,
-                           res, st.up.cin);
-        d->gn_of = nullptr;                             // (no conv wrote this tensor: its GroupNorm takes the separate sweep)
+        launch_avgpool2(s, d->buf[xi], d->buf[t], B, res, res, st.up.cin);
+        d->gn.of = nullptr;                             // (no conv wrote this tensor: its GroupNorm takes the separate sweep)
         res /= 2;
         xi = t;
         continue;
       }
-      hipLaunchKernelGGL(s2d_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 + 255) / 256)), dim3(256), 0, s, d->buf[xi], d->buf[t], B, res, res,
-                         st.up.cin);
+      launch_s2d(s, d->buf[xi], d->buf[t], B, res, res, st.up.cin);
       res /= 2;
-      launch_conv(s, d, st.up, d->buf[t], nullptr, nullptr, d->buf[t2], nullptr, nullptr, B, res, res, false);
+      launch_conv(s, &d->gn, st.up, d->buf[t], nullptr, nullptr, d->buf[t2], nullptr, nullptr, B, res, res, false);
       xi = t2;
     }
   }
   for (auto& rb : d->e_mid) xi = run_block(s, d, rb, xi, B, res, res);
-  launch_gn(s, d, d->e_norm_out, d->buf[xi], B, res * res);
+  launch_gn(s, &d->gn, d->e_norm_out, d->buf[xi], B, res * res);
   const int t = (xi + 1) % 3;
-  launch_conv(s, d, d->e_conv_out, d->buf[xi], d->gn_ss, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
+  launch_conv(s, &d->gn, d->e_conv_out, d->buf[xi], d->gn.ss, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
   *res_out = res;
   return t;
 }
@@ -870,6 +901,100 @@ int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* 
   const size_t np = (size_t)B * res * res;
   hipLaunchKernelGGL(lfq_kernel, dim3((unsigned)std::min<size_t>(1024, (np + 255) / 256)), dim3(256), 0, s, d->buf[t], indices, zq, zraw, B, res * res,
                      c.token_size, d->e_conv_out.cout);
+  return 0;
+}
+
+// ---- single layers on caller buffers (include/maskbit_hip_diag.h): the helpers above on a scratch context instead of a handle ----------------
+namespace {
+struct Scratch {                                   // device allocations of one diagnostic call
+  std::vector<void*> owned;
+  ~Scratch() { for (void* p : owned) (void)hipFree(p); }
+  template <typename T>
+  bool get(T** p, size_t n) {
+    if (hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
+    owned.push_back((void*)*p);
+    return true;
+  }
+};
+size_t gn_part_elems(int B, int H, int W) { return (size_t)B * std::max(GN_MAXCHUNK, (H / TH8) * (W / TW)) * 64; }
+}  // namespace
+
+int diag_groupnorm(const void* x, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, hipStream_t s, std::string& err) {
+  if (B <= 0 || HW <= 0 || C < 32 || C > 2048 || C % 32 || (C / 8) > 256) { err = "C must be a multiple of 32 in [32, 2048]"; return -1; }
+  Scratch m;
+  GnCtx gc;
+  if (!m.get(&gc.part, (size_t)B * GN_MAXCHUNK * 64) || !m.get(&gc.ss, (size_t)B * C)) { err = "hipMalloc failed"; return -10; }
+  Norm n; n.c = C; n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta);
+  launch_gn(s, &gc, n, (const h16*)x, B, HW);      // gc.of is null: the sweep (gn_partial_kernel) + gn_finalize_kernel
+  if (hipMemcpyAsync(scale_shift, gc.ss, (size_t)B * C * sizeof(float2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) { err = "copy failed"; return -10; }
+  return 0;
+}
+
+int diag_pool(bool avg, const void* x, void* y, int B, int H, int W, int C, hipStream_t s, std::string& err) {
+  if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8) { err = "H and W must be even, C a multiple of 8"; return -1; }
+  if (avg) launch_avgpool2(s, (const h16*)x, (h16*)y, B, H, W, C);
+  else launch_s2d(s, (const h16*)x, (h16*)y, B, H, W, C);
+  return 0;
+}
+
+int diag_conv(const ConvDiag& q, hipStream_t s, std::string& err) {
+  const int B = q.B, H = q.H, W = q.W;
+  const bool fin = q.final_layer != 0, up = q.up != 0;
+  if (!q.in || !q.w || B <= 0 || q.Cin <= 0 || q.Cout <= 0) { err = "null or empty argument"; return -1; }
+  if (q.ks < 1 || q.ks > 3) { err = "ks must be 1, 2 or 3"; return -1; }
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW) { err = "the output must be whole 8 x 16 pixel tiles"; return -1; }
+  if (fin && (q.ks != 3 || up || q.Cout > 4 || q.residual || !(q.img_nchw || q.img_u8))) { err = "final layer: ks 3, at most 4 channels, no residual, an image output"; return -1; }
+  if (!fin && (!q.out || q.Cout % 4)) { err = "fp16 output: Cout must be a multiple of 4"; return -1; }
+  if (up && q.ks != 3) { err = "upsampling goes with ks 3"; return -1; }
+  if (q.ks == 2 && (q.Cin % 16 || q.gamma)) { err = "ks 2 (stride-2 conv): Cin must be a multiple of 16, no prologue"; return -1; }
+  if ((q.gamma != nullptr) != (q.beta != nullptr) || (q.gamma && (q.Cin % CK || q.Cin > 2048))) { err = "prologue: gamma and beta, Cin a multiple of 64 up to 2048"; return -1; }
+  if (q.out_scale_shift && (fin || !q.out_gamma || !q.out_beta || q.Cout % 32 || q.Cout > 2048)) { err = "output statistics: gamma and beta, Cout a multiple of 32 up to 2048"; return -1; }
+  Conv c;
+  if (q.ks == 2) shape_down_conv(c, q.Cin); else shape_conv(c, q.Cin, q.Cout, q.ks, q.bias != nullptr, up, fin);
+  if (q.ks == 2) { c.cout = q.Cout; c.cout_w = q.Cout; c.cout_pad = (q.Cout + 127) / 128 * 128; c.has_bias = q.bias != nullptr; }
+  Scratch m;
+  GnCtx gc;
+  const int Hin = q.ks == 2 ? 2 * H : (up ? H / 2 : H), Win = q.ks == 2 ? 2 * W : (up ? W / 2 : W);   // the caller's input tensor
+  if (up && (H % 2 || W % 2)) { err = "upsampling needs even H and W"; return -1; }
+  const size_t npix_in = (size_t)B * Hin * Win;
+  h16* staged = nullptr;
+  if (!m.get(&c.w, conv_weight_elems(c)) || !m.get(&c.b, (size_t)c.cout_pad) || !m.get(&c.sat, 1) ||
+      !m.get(&gc.part, gn_part_elems(B, std::max(H, Hin), std::max(W, Win))) || !m.get(&gc.ss, (size_t)B * std::max(c.cin_pad, std::max(q.Cout, 1)))) { err = "hipMalloc failed"; return -10; }
+  bool ok = hipMemsetAsync(c.b, 0, c.cout_pad * sizeof(float), s) == hipSuccess && hipMemsetAsync(c.sat, 0, sizeof(unsigned), s) == hipSuccess;
+  if (ok && q.bias) ok = hipMemcpyAsync(c.b, q.bias, (size_t)q.Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  repack_weights(s, c, q.w);
+  const h16* in = (const h16*)q.in;
+  if (q.ks == 2) {                                  // [B, 2H, 2W, Cin] -> [B, H, W, 4 Cin]
+    if (!m.get(&staged, npix_in * q.Cin)) { err = "hipMalloc failed"; return -10; }
+    launch_s2d(s, in, staged, B, Hin, Win, q.Cin);
+    in = staged;
+  } else if (c.cin_pad != q.Cin) {                  // channels padded with zeros to a whole chunk, as pack_image_kernel / latent_kernel leave them
+    if (!m.get(&staged, npix_in * c.cin_pad)) { err = "hipMalloc failed"; return -10; }
+    ok = ok && hipMemsetAsync(staged, 0, npix_in * c.cin_pad * sizeof(h16), s) == hipSuccess &&
+         hipMemcpy2DAsync(staged, c.cin_pad * sizeof(h16), in, q.Cin * sizeof(h16), q.Cin * sizeof(h16), npix_in, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    in = staged;
+  }
+  if (!ok) { err = "copy failed"; return -10; }
+  const float2* gn = nullptr;
+  if (q.gamma) {
+    Norm n; n.c = q.Cin; n.g = const_cast<float*>(q.gamma); n.b = const_cast<float*>(q.beta);
+    launch_gn(s, &gc, n, in, B, Hin * Win);
+    gn = gc.ss;
+  }
+  launch_conv(s, &gc, c, in, gn, (const h16*)q.residual, (h16*)q.out, q.img_nchw, q.img_u8, B, H, W, fin);
+  const int tiles = gc.of == (const void*)q.out && !fin ? gc.ntile : 0;      // the epilogue wrote GroupNorm partials of the output
+  if (q.part_tiles) *q.part_tiles = tiles;
+  if (q.out_part && tiles) ok = hipMemcpyAsync(q.out_part, gc.part, (size_t)B * tiles * 64 * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (ok && q.out_scale_shift) {
+    Norm n; n.c = q.Cout; n.g = const_cast<float*>(q.out_gamma); n.b = const_cast<float*>(q.out_beta);
+    launch_gn(s, &gc, n, (const h16*)q.out, B, H * W);                       // from the epilogue's partials when there are any, else the sweep
+    ok = hipMemcpyAsync(q.out_scale_shift, gc.ss, (size_t)B * q.Cout * sizeof(float2), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  }
+  unsigned nsat = 0;
+  ok = ok && hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) { err = "copy failed"; return -10; }
+  if (q.saturated) *q.saturated = nsat;
   return 0;
 }
 

@@ -895,6 +895,41 @@ int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int
   return 0;
 }
 
+// ---- single tokenizer layers on caller buffers (maskbit_hip_diag.h) ----
+int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
+                  void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
+                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
+                  mb_stream stream) {
+  mb::ConvDiag q{in_h16, w_oihw, bias, gn_gamma, gn_beta, residual_h16, out_h16, img_nchw, img_nhwc_u8, out_gamma, out_beta, out_scale_shift,
+                 out_gn_part, part_tiles, saturated, B, H, W, Cin, Cout, ks, up, final_layer};
+  std::string err;
+  int rc = mb::diag_conv(q, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "mb_conv_layer: %s", err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream) {
+  if (!x_h16 || !gamma || !beta || !scale_shift) return fail(-1, "mb_groupnorm_stats: null argument");
+  std::string err;
+  int rc = mb::diag_groupnorm(x_h16, gamma, beta, scale_shift, B, HW, C, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "mb_groupnorm_stats: %s", err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+static int pool_entry(const char* what, bool avg, const void* x, void* y, int B, int H, int W, int C, mb_stream stream) {
+  if (!x || !y) return fail(-1, "%s: null argument", what);
+  std::string err;
+  int rc = mb::diag_pool(avg, x, y, B, H, W, C, (hipStream_t)stream, err);
+  if (rc) return fail(rc, "%s: %s", what, err.c_str());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  return 0;
+}
+int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", true, x_h16, y_h16, B, H, W, C, stream); }
+int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", false, x_h16, y_h16, B, H, W, C, stream); }
+
 int mb_dec_saturation_count(mb_dec* d, unsigned* count, int reset, mb_stream stream) {
   if (!d || !count) return fail(-1, "mb_dec_saturation_count: null argument");
   if (mb::dec_saturation_count(d, count, reset != 0, (hipStream_t)stream)) return fail(-10, "mb_dec_saturation_count: copy failed");

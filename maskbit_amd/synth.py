@@ -162,9 +162,49 @@ def decoder_plan(cfg: TokCfg) -> List[Tuple[str, int, int, bool]]:
     return out
 
 
-def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = False, lfq_buffers: bool = True) -> StateDict:
+TOK_OFFSET_GROUPS = 3      # tokenizer style "trained": GroupNorm groups of every residual block's output that carry a large constant offset ...
+TOK_OFFSET_DC = 12.0       # ... of this size per block (|mean| / std of those groups ~ 8 .. 36 at the next GroupNorm)
+TOK_OFFSET_BETA = 6.0      # the norm2 beta of the channel that feeds it (SiLU(6) = 5.985, gamma x 0.1 there: nearly input-independent)
+TOK_STREAM_GAIN = 1.2      # conv2 of every residual block: the residual stream grows along the stages
+
+
+def _trained_like_tokenizer(sd: StateDict, seed: int) -> None:
+    """Post-transform of the Gaussian tokenizer draw towards what trained VQGAN decoders show and the Gaussian draw does not (what the fp32
+    E[x^2] - mean^2 GroupNorm statistics and the fp16 activations are sensitive to): (1) heavy-tailed conv weights (_HEAVY_TAIL_SCALES, as _trained_like);
+    (2) in every residual block one norm2 channel with beta = TOK_OFFSET_BETA feeds, through the centre tap of conv2 alone (so the offset is the same at the
+    borders), TOK_OFFSET_GROUPS whole GroupNorm groups of the block's output with a constant +-TOK_OFFSET_DC: the next GroupNorm sees groups whose
+    |mean| is 8 .. 36 x their std (less where an up- / downsampling conv has mixed the channels in between); (3) conv2 x TOK_STREAM_GAIN: a residual stream that grows from block to block.  Deterministic from the seed (a
+    generator of its own: the Gaussian draw and every existing fixture stay what they were)."""
+    g = torch.Generator().manual_seed(1_000_003 * (seed + 1) + 17)
+    for k in sorted(sd):
+        if sd[k].dim() == 4:
+            sd[k] = sd[k] * _HEAVY_TAIL_SCALES[torch.randint(0, 64, sd[k].shape, generator=g)]
+    for k in sorted(sd):
+        if not k.endswith(".norm2.weight"):
+            continue
+        p = k[: -len(".norm2.weight")]
+        w = sd[p + ".conv2.weight"] * TOK_STREAM_GAIN
+        co = w.shape[0]
+        cpg = co // 32
+        src = int(torch.randint(0, co, (1,), generator=g))
+        groups = torch.randperm(32, generator=g)[:TOK_OFFSET_GROUPS]
+        sign = torch.where(torch.rand(TOK_OFFSET_GROUPS, generator=g) < 0.5, -1.0, 1.0)
+        sd[p + ".norm2.weight"][src] *= 0.1
+        sd[p + ".norm2.bias"][src] = TOK_OFFSET_BETA
+        for gi, sg in zip(groups.tolist(), sign.tolist()):
+            w[gi * cpg:(gi + 1) * cpg, src] = 0.0
+            w[gi * cpg:(gi + 1) * cpg, src, 1, 1] = sg * TOK_OFFSET_DC / 5.985
+            if p + ".nin_shortcut.weight" in sd:           # out = h + W h: the shortcut does not smear the offset over the other groups
+                sd[p + ".nin_shortcut.weight"][:, gi * cpg:(gi + 1) * cpg] = 0.0
+        sd[p + ".conv2.weight"] = w
+
+
+def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = False, lfq_buffers: bool = True, style: str = "gaussian") -> StateDict:
     """Seeded conv weights randn/sqrt(fan_in), GN gamma ~ 1, with the reference's key names.  ``lfq_buffers=False``: without the LFQ
-    quantizer's derived buffers (a lookup tokenizer's codebook comes from make_vq_codebook instead)."""
+    quantizer's derived buffers (a lookup tokenizer's codebook comes from make_vq_codebook instead).  ``style`` "trained": see
+    _trained_like_tokenizer."""
+    if style not in ("gaussian", "trained"):
+        raise ValueError(f"unknown tokenizer weight style '{style}'")
     g = torch.Generator().manual_seed(seed)
 
     def conv(co, ci, k):
@@ -217,6 +257,8 @@ def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = Fals
         if lfq_buffers:
             sd["quantize.bits_to_indices"] = (1 << torch.arange(cfg.token_size)).to(torch.int32)
             sd["quantize.codebook"] = _index_to_bits(torch.arange(1 << cfg.token_size), cfg.token_size)
+    if style == "trained":
+        _trained_like_tokenizer(sd, seed)
     return sd
 
 

@@ -302,61 +302,96 @@ def _conv_same(x: Tensor, w: Tensor, b: Optional[Tensor], stride: int = 1) -> Te
     return F.conv2d(x, w, b, stride=stride)
 
 
-def _gn_silu(x: Tensor, sd: StateDict, p: str) -> Tensor:
-    return F.silu(F.group_norm(x, 32, sd[p + ".weight"], sd[p + ".bias"], 1e-6))     # autoencoder.py:39-43
+def _store(x: Tensor, fp16: bool) -> Tensor:
+    """fp16_storage emulation: a tensor the HIP engine keeps in memory (or in LDS, for the GroupNorm+SiLU prologue) is rounded to fp16 there."""
+    return x.to(torch.float16).to(x.dtype) if fp16 else x
 
 
-def _res_block(x: Tensor, sd: StateDict, p: str) -> Tensor:
+def _gn_silu(x: Tensor, sd: StateDict, p: str, fp16: bool = False) -> Tensor:
+    return _store(F.silu(F.group_norm(x, 32, sd[p + ".weight"], sd[p + ".bias"], 1e-6)), fp16)     # autoencoder.py:39-43
+
+
+def _res_block(x: Tensor, sd: StateDict, p: str, fp16: bool = False) -> Tensor:
     """ResidualBlock (autoencoder.py:76-96). NB the shortcut quirk: when Cin != Cout the 1x1
     conv is applied to the block OUTPUT h and the input is dropped: out = h + W*h."""
-    h = _conv_same(_gn_silu(x, sd, p + ".norm1"), sd[p + ".conv1.weight"], None)
-    h = _conv_same(_gn_silu(h, sd, p + ".norm2"), sd[p + ".conv2.weight"], None)
+    h = _store(_conv_same(_gn_silu(x, sd, p + ".norm1", fp16), sd[p + ".conv1.weight"], None), fp16)
+    h = _conv_same(_gn_silu(h, sd, p + ".norm2", fp16), sd[p + ".conv2.weight"], None)
     if (p + ".nin_shortcut.weight") in sd:
-        return h + _conv_same(h, sd[p + ".nin_shortcut.weight"], None)
-    return h + x
+        h = _store(h, fp16)
+        return _store(h + _conv_same(h, sd[p + ".nin_shortcut.weight"], None), fp16)
+    return _store(h + x, fp16)
 
 
-def decode_latents(sd: StateDict, cfg: TokCfg, z: Tensor) -> Tensor:
+def _prepare(sd: StateDict, dtype: Optional[torch.dtype], fp16_storage: bool) -> StateDict:
+    """The weights as a run in ``dtype`` sees them; with ``fp16_storage`` the convolution weights carry the engine's fp16 rounding (biases and
+    GroupNorm parameters stay fp32 there)."""
+    if dtype is None and not fp16_storage:
+        return sd
+    out = {}
+    for k, v in sd.items():
+        if v.is_floating_point():
+            if fp16_storage and v.dim() == 4:
+                v = v.to(torch.float16)
+            v = v.to(dtype or torch.float32)
+        out[k] = v
+    return out
+
+
+def decode_latents(sd: StateDict, cfg: TokCfg, z: Tensor, fp16_storage: bool = False) -> Tensor:
     """ConvDecoder.forward (autoencoder.py:399-423): z [b,K,h,w] -> image [b,3,H,W]."""
-    nrb = cfg.num_res_blocks
-    x = _conv_same(z, sd["decoder.conv_in.weight"], sd["decoder.conv_in.bias"])
+    nrb, q = cfg.num_res_blocks, fp16_storage
+    x = _store(_conv_same(z, sd["decoder.conv_in.weight"], sd["decoder.conv_in.bias"]), q)
     for r in range(nrb):
-        x = _res_block(x, sd, f"decoder.mid.res_blocks.{r}")
+        x = _res_block(x, sd, f"decoder.mid.res_blocks.{r}", q)
     for s in range(cfg.num_resolutions):               # up.0 is the coarsest level (i_level = R-1)
         for r in range(nrb):
-            x = _res_block(x, sd, f"decoder.up.{s}.res_blocks.{r}")
+            x = _res_block(x, sd, f"decoder.up.{s}.res_blocks.{r}", q)
         if s < cfg.num_resolutions - 1:                # UpsamplingStage: nearest x2 then conv (:224-225)
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-            x = _conv_same(x, sd[f"decoder.up.{s}.upsample_conv.weight"], sd[f"decoder.up.{s}.upsample_conv.bias"])
-    x = _gn_silu(x, sd, "decoder.norm_out")
-    return _conv_same(x, sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"])
+            x = _store(_conv_same(x, sd[f"decoder.up.{s}.upsample_conv.weight"], sd[f"decoder.up.{s}.upsample_conv.bias"]), q)
+    x = _gn_silu(x, sd, "decoder.norm_out", q)
+    return _conv_same(x, sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"])      # (the engine writes the image as fp32)
 
 
-def decode_tokens(sd: StateDict, cfg: TokCfg, tokens: Tensor) -> Tensor:
-    """ConvVQModel.decode_tokens (conv_vqgan.py:98-112): tokens [b,n] (any numeric dtype)."""
+def decode_tokens(sd: StateDict, cfg: TokCfg, tokens: Tensor, dtype: Optional[torch.dtype] = None, fp16_storage: bool = False) -> Tensor:
+    """ConvVQModel.decode_tokens (conv_vqgan.py:98-112): tokens [b,n] (any numeric dtype).
+    ``dtype`` (test infrastructure): run in that precision (torch.float64: the exact mathematics of the layers); ``fp16_storage``: the same run with
+    the HIP engine's documented roundings applied -- convolution weights and every stored activation rounded to fp16.  The difference of the two
+    float64 runs is the design's own error (E_model), the yardstick of tests/test_hip_tokenizer_precision.py."""
     z = index_to_bits(tokens.long(), cfg.token_size)              # [b,n,K]
     side = int(math.sqrt(float(z.shape[1])))
     z = z.reshape(z.shape[0], side, side, -1).permute(0, 3, 1, 2).contiguous()
-    return decode_latents(sd, cfg, z)
+    if dtype is not None:
+        z = z.to(dtype)
+    return decode_latents(_prepare(sd, dtype, fp16_storage), cfg, z, fp16_storage)
 
 
-def encode_image(sd: StateDict, cfg: TokCfg, x: Tensor) -> Tuple[Tensor, Tensor]:
-    """ConvEncoder.forward + LFQ sign/pack (autoencoder.py:274-286, lookup_free.py:57-62).
-    Returns (z_quantized [b,K,h,w] in {-1,+1}, indices [b,h,w]).  BASELINE config 1 plumbing."""
-    nrb = cfg.num_res_blocks
-    h = _conv_same(x, sd["encoder.conv_in.weight"], None)
+def encode_latent(sd: StateDict, cfg: TokCfg, x: Tensor, dtype: Optional[torch.dtype] = None, fp16_storage: bool = False) -> Tensor:
+    """ConvEncoder.forward (autoencoder.py:274-286): image -> pre-quantiser latent z [b,K,h,w].  ``dtype`` / ``fp16_storage``: see decode_tokens
+    (the engine also stores the input image and z itself as fp16)."""
+    nrb, q = cfg.num_res_blocks, fp16_storage
+    sd = _prepare(sd, dtype, fp16_storage)
+    if dtype is not None:
+        x = x.to(dtype)
+    h = _store(_conv_same(_store(x, q), sd["encoder.conv_in.weight"], None), q)
     for s in range(cfg.num_resolutions):
         for r in range(nrb):
-            h = _res_block(h, sd, f"encoder.down.{s}.res_blocks.{r}")
+            h = _res_block(h, sd, f"encoder.down.{s}.res_blocks.{r}", q)
         if s < cfg.num_resolutions - 1:
             if cfg.sample_with_conv:
-                h = _conv_same(h, sd[f"encoder.down.{s}.down_conv.weight"], sd[f"encoder.down.{s}.down_conv.bias"], stride=2)
+                h = _store(_conv_same(h, sd[f"encoder.down.{s}.down_conv.weight"], sd[f"encoder.down.{s}.down_conv.bias"], stride=2), q)
             else:
-                h = F.avg_pool2d(h, kernel_size=2, stride=2)
+                h = _store(F.avg_pool2d(h, kernel_size=2, stride=2), q)
     for r in range(nrb):
-        h = _res_block(h, sd, f"encoder.mid.res_blocks.{r}")
-    h = _gn_silu(h, sd, "encoder.norm_out")
-    z = _conv_same(h, sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"])
+        h = _res_block(h, sd, f"encoder.mid.res_blocks.{r}", q)
+    h = _gn_silu(h, sd, "encoder.norm_out", q)
+    return _store(_conv_same(h, sd["encoder.conv_out.weight"], sd["encoder.conv_out.bias"]), q)
+
+
+def encode_image(sd: StateDict, cfg: TokCfg, x: Tensor, dtype: Optional[torch.dtype] = None, fp16_storage: bool = False) -> Tuple[Tensor, Tensor]:
+    """ConvEncoder.forward + LFQ sign/pack (autoencoder.py:274-286, lookup_free.py:57-62).
+    Returns (z_quantized [b,K,h,w] in {-1,+1}, indices [b,h,w]).  BASELINE config 1 plumbing."""
+    z = encode_latent(sd, cfg, x, dtype, fp16_storage)
     zq = torch.where(z > 0.0, torch.ones_like(z), -torch.ones_like(z))
     idx = bits_to_index(zq.permute(0, 2, 3, 1))
     return zq, idx

@@ -30,6 +30,19 @@ def hip_tokenizer(cfg: O.TokCfg, sd, device="cuda"):
     return m.eval().requires_grad_(False).to(device)
 
 
+def decidable_bits(sd, cfg: O.TokCfg, x: torch.Tensor):
+    """Which bits of the encoder's sign quantiser the REFERENCE decides: |z| of the float64 oracle clear of twice the largest error the design's own
+    fp16 storage causes on this input (the oracle's fp16_storage model) -- nothing here depends on the kernel under test.
+    -> (mask [b, h, w, K], excluded share of the bits)."""
+    exact = O.encode_latent(sd, cfg, x, dtype=torch.float64)
+    model = O.encode_latent(sd, cfg, x, dtype=torch.float64, fp16_storage=True)
+    clear = exact.permute(0, 2, 3, 1).abs() > 2.0 * float((model - exact).abs().max())
+    return clear, 1.0 - float(clear.double().mean())
+
+
+MAX_UNDECIDABLE = 0.02        # at most this share of the bits may be left out of the comparison
+
+
 def token_mismatch(a: torch.Tensor, b: torch.Tensor, where=None) -> float:
     ne = (a != b)
     if where is not None:
