@@ -18,6 +18,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/maskbit_hip.h"
+#include "mb_abi.h"
 #include "mb_decoder.h"
 #include "mb_kernels.h"
 #include "mb_vq.h"
@@ -508,6 +510,7 @@ struct mb_dec {
   unsigned* sat = nullptr;  // device counter: fp16 clamps in the conv epilogues since the last read
   mb::GnCtx gn;
   std::vector<void*> owned;
+  hipError_t alloc_error = hipSuccess;   // of the hipMalloc that stopped create
 };
 
 namespace mb {
@@ -516,9 +519,9 @@ namespace {
 constexpr int GN_MAXCHUNK = 64;
 
 template <typename T>
-bool dalloc(mb_dec* d, T** p, size_t n, std::string& err) {
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) { err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return false; }
+bool dalloc(mb_dec* d, T** p, size_t n) {
+  d->alloc_error = hipMalloc((void**)p, n * sizeof(T));
+  if (d->alloc_error != hipSuccess) return false;
   d->owned.push_back((void*)*p);
   return true;
 }
@@ -549,26 +552,25 @@ void launch_avgpool2(hipStream_t s, const h16* x, h16* y, int B, int H, int W, i
   hipLaunchKernelGGL(avgpool2_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 / 4 + 255) / 256)), dim3(256), 0, s, x, y, B, H, W, C);
 }
 
-bool init_conv(mb_dec* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool bias, bool up, bool final_,
-               std::string& err) {
+bool init_conv(mb_dec* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool bias, bool up, bool final_) {
   c.name = name; c.sat = d->sat;
   shape_conv(c, cin, cout, ks, bias, up, final_);
-  if (!dalloc(d, &c.w, conv_weight_elems(c), err)) return false;
+  if (!dalloc(d, &c.w, conv_weight_elems(c))) return false;
   if (bias) {
-    if (!dalloc(d, &c.b, (size_t)c.cout_pad, err)) return false;
+    if (!dalloc(d, &c.b, (size_t)c.cout_pad)) return false;
     (void)hipMemset(c.b, 0, c.cout_pad * sizeof(float));
   }
   return true;
 }
-bool init_norm(mb_dec* d, Norm& n, const std::string& name, int c, std::string& err) {
+bool init_norm(mb_dec* d, Norm& n, const std::string& name, int c) {
   n.name = name; n.c = c;
-  return dalloc(d, &n.g, (size_t)c, err) && dalloc(d, &n.b, (size_t)c, err);
+  return dalloc(d, &n.g, (size_t)c) && dalloc(d, &n.b, (size_t)c);
 }
-bool init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout, std::string& err) {
+bool init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout) {
   rb.has_sc = cin != cout;
-  bool ok = init_norm(d, rb.n1, p + ".norm1", cin, err) && init_conv(d, rb.c1, p + ".conv1", cin, cout, 3, false, false, false, err) &&
-            init_norm(d, rb.n2, p + ".norm2", cout, err) && init_conv(d, rb.c2, p + ".conv2", cout, cout, 3, false, false, false, err);
-  if (ok && rb.has_sc) ok = init_conv(d, rb.sc, p + ".nin_shortcut", cout, cout, 1, false, false, false, err);
+  bool ok = init_norm(d, rb.n1, p + ".norm1", cin) && init_conv(d, rb.c1, p + ".conv1", cin, cout, 3, false, false, false) &&
+            init_norm(d, rb.n2, p + ".norm2", cout) && init_conv(d, rb.c2, p + ".conv2", cout, cout, 3, false, false, false);
+  if (ok && rb.has_sc) ok = init_conv(d, rb.sc, p + ".nin_shortcut", cout, cout, 1, false, false, false);
   return ok;
 }
 
@@ -633,163 +635,6 @@ bool find_norm(Norm& nm, const std::string& n, float** dst) {
 }
 }  // namespace
 
-mb_dec* dec_create(const mb_dec_cfg& cfg, int max_batch, std::string& err, int codebook_size, int l2_normalize) {
-  const int R = cfg.num_resolutions;
-  const bool vq = codebook_size > 0;
-  if (R < 1 || R > 7) { err = "num_resolutions out of range"; return nullptr; }
-  if (cfg.hidden_channels % 64) { err = "hidden_channels must be a multiple of 64 for the HIP decoder"; return nullptr; }
-  if (!vq && (cfg.token_size > CK || cfg.token_size < 1)) { err = "token_size must be in [1, 64]"; return nullptr; }
-  if (vq && (cfg.token_size > 256 || cfg.token_size < 1)) { err = "token_size must be in [1, 256]"; return nullptr; }
-  if (vq && (codebook_size < 2 || codebook_size > 65536)) { err = "codebook_size must be in [2, 65536]"; return nullptr; }
-  if (cfg.latent_size % 16) { err = "latent_size must be a multiple of 16"; return nullptr; }
-  if (cfg.num_channels > 4) { err = "num_channels > 4 unsupported"; return nullptr; }
-  mb_dec* d = new mb_dec();
-  d->c = cfg; d->max_batch = max_batch; d->out_res = cfg.latent_size << (R - 1);
-  if (!dalloc(d, &d->sat, 1, err)) { dec_destroy(d); return nullptr; }
-  (void)hipMemset(d->sat, 0, sizeof(unsigned));
-  const int hc = cfg.hidden_channels;
-  std::vector<int> mult(cfg.channel_mult, cfg.channel_mult + R);
-  mult.push_back(cfg.channel_mult[R - 1]);
-  const int top = hc * cfg.channel_mult[R - 1];
-  bool ok = init_conv(d, d->conv_in, "decoder.conv_in", cfg.token_size, top, 3, true, false, false, err);
-  d->mid.resize(cfg.num_res_blocks);
-  for (int r = 0; ok && r < cfg.num_res_blocks; ++r)
-    ok = init_block(d, d->mid[r], "decoder.mid.res_blocks." + std::to_string(r), top, top, err);
-  d->up.resize(R);
-  int last = top;
-  size_t max_elems = 0;
-  int res = cfg.latent_size;
-  max_elems = std::max((size_t)res * res * top, (size_t)d->out_res * d->out_res * (size_t)std::max(CK, hc));
-  for (int s = 0; ok && s < R; ++s) {                    // up.0 = coarsest level (autoencoder.py:384-392)
-    const int lvl = R - 1 - s;
-    const int cin = hc * mult[lvl + 1], cout = hc * mult[lvl];
-    Stage& st = d->up[s];
-    st.blocks.resize(cfg.num_res_blocks);
-    int c = cin;
-    for (int r = 0; ok && r < cfg.num_res_blocks; ++r) {
-      ok = init_block(d, st.blocks[r], "decoder.up." + std::to_string(s) + ".res_blocks." + std::to_string(r), c, cout, err);
-      c = cout;
-    }
-    max_elems = std::max(max_elems, (size_t)res * res * std::max(cin, cout));
-    st.has_up = lvl > 0;
-    if (ok && st.has_up) {
-      ok = init_conv(d, st.up, "decoder.up." + std::to_string(s) + ".upsample_conv", cout, cout, 3, true, true, false, err);
-      res *= 2;
-      max_elems = std::max(max_elems, (size_t)res * res * cout);
-    }
-    last = cout;
-  }
-  ok = ok && init_norm(d, d->norm_out, "decoder.norm_out", last, err) &&
-       init_conv(d, d->conv_out, "decoder.conv_out", last, cfg.num_channels, 3, true, false, true, err);
-  if (ok && cfg.build_encoder) {                          // ConvEncoder (autoencoder.py:230-262): mirrors the decoder top-down
-    const int enrb = cfg.enc_res_blocks > 0 ? cfg.enc_res_blocks : cfg.num_res_blocks;
-    std::vector<int> imult{1};
-    imult.insert(imult.end(), cfg.channel_mult, cfg.channel_mult + R);
-    ok = ok && init_conv(d, d->e_conv_in, "encoder.conv_in", cfg.num_channels, hc, 3, false, false, false, err);
-    d->e_down.resize(R);
-    for (int s = 0; ok && s < R; ++s) {
-      const int cin = hc * imult[s], cout = hc * imult[s + 1];
-      Stage& st = d->e_down[s];
-      st.blocks.resize(enrb);
-      int c = cin;
-      for (int r = 0; ok && r < enrb; ++r) {
-        ok = init_block(d, st.blocks[r], "encoder.down." + std::to_string(s) + ".res_blocks." + std::to_string(r), c, cout, err);
-        c = cout;
-      }
-      st.has_up = s < R - 1;                              // a downsampling step follows: down_conv, or avg_pool2d when !sample_with_conv
-      st.up.cin = cout;
-      if (ok && st.has_up && cfg.sample_with_conv) {      // DownsamplingStage.down_conv: 3x3, stride 2, bias (autoencoder.py:165)
-        Conv& dc = st.up;
-        dc.name = "encoder.down." + std::to_string(s) + ".down_conv"; dc.sat = d->sat;
-        shape_down_conv(dc, cout);
-        ok = dalloc(d, &dc.w, conv_weight_elems(dc), err) && dalloc(d, &dc.b, (size_t)dc.cout_pad, err);
-        if (ok) (void)hipMemset(dc.b, 0, dc.cout_pad * sizeof(float));
-      }
-    }
-    d->e_mid.resize(enrb);
-    for (int r = 0; ok && r < enrb; ++r)
-      ok = init_block(d, d->e_mid[r], "encoder.mid.res_blocks." + std::to_string(r), top, top, err);
-    const int k4 = (cfg.token_size + 3) / 4 * 4;           // stored channel count of z (8-byte stores)
-    ok = ok && init_norm(d, d->e_norm_out, "encoder.norm_out", top, err) &&
-         init_conv(d, d->e_conv_out, "encoder.conv_out", top, k4, 1, true, false, false, err);
-    d->e_conv_out.cout_w = cfg.token_size;
-    d->has_enc = ok;
-  }
-  for (int i = 0; ok && i < 3; ++i) ok = dalloc(d, &d->buf[i], (size_t)max_batch * max_elems, err);
-  const size_t nlat = (size_t)max_batch * cfg.latent_size * cfg.latent_size;
-  ok = ok && dalloc(d, &d->z, nlat * d->conv_in.cin_pad, err) &&
-       dalloc(d, &d->gn.part, (size_t)max_batch * std::max(GN_MAXCHUNK, (d->out_res / TH8) * (d->out_res / TW)) * 64, err) &&
-       dalloc(d, &d->gn.ss, (size_t)max_batch * 4096, err);
-  if (ok && vq) {
-    VqCodebook& q = d->q;
-    q.C = codebook_size; q.K = cfg.token_size; q.Kp = vq_kp(q.K); q.Cpad = vq_cpad(q.C); q.l2 = l2_normalize ? 1 : 0;
-    const size_t npad = (size_t)vq_npad((int)nlat);
-    ok = dalloc(d, &q.cb, (size_t)q.C * q.K, err) && dalloc(d, &q.cbT, (size_t)q.Kp * q.Cpad, err) && dalloc(d, &q.cbn, (size_t)q.Cpad, err) &&
-         dalloc(d, &d->vq_zT, (size_t)q.Kp * npad, err) && dalloc(d, &d->vq_ps, VQ_SPLIT_MAX * npad, err) &&
-         dalloc(d, &d->vq_pi, VQ_SPLIT_MAX * npad, err);
-    d->vq = ok;
-  }
-  if (!ok) { dec_destroy(d); return nullptr; }
-  return d;
-}
-
-void dec_destroy(mb_dec* d) {
-  if (!d) return;
-  for (void* p : d->owned) (void)hipFree(p);
-  delete d;
-}
-
-int dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shape, int ndim, hipStream_t s, std::string& err) {
-  const std::string n(name);
-  if (d->vq && n == "quantize.embedding.weight") {                               // SimpleVectorizer.embedding [C, K]
-    if (ndim != 2 || shape[0] != d->q.C || shape[1] != d->q.K) { err = n + ": expected [codebook_size, token_size]"; return -4; }
-    vq_prep_codebook(d->q, data, s);
-    d->cb_loaded = true;
-    return 0;
-  }
-  if (n.rfind("quantize.", 0) == 0) return 0;                                    // derived buffers
-  if (n.rfind("encoder.", 0) == 0 && !d->has_enc) return 0;                       // encode half not built in this engine
-  size_t numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  std::vector<Conv*> convs{&d->conv_in, &d->conv_out};
-  std::vector<Norm*> norms{&d->norm_out};
-  auto add_block = [&](ResBlock& rb) {
-    convs.push_back(&rb.c1); convs.push_back(&rb.c2); if (rb.has_sc) convs.push_back(&rb.sc);
-    norms.push_back(&rb.n1); norms.push_back(&rb.n2);
-  };
-  for (auto& rb : d->mid) add_block(rb);
-  for (auto& st : d->up) { for (auto& rb : st.blocks) add_block(rb); if (st.has_up) convs.push_back(&st.up); }
-  if (d->has_enc) {
-    convs.push_back(&d->e_conv_in); convs.push_back(&d->e_conv_out); norms.push_back(&d->e_norm_out);
-    for (auto& rb : d->e_mid) add_block(rb);
-    for (auto& st : d->e_down) { for (auto& rb : st.blocks) add_block(rb); if (st.has_up && d->c.sample_with_conv) convs.push_back(&st.up); }
-  }
-  for (Conv* c : convs) {
-    Conv* hit = nullptr; bool is_bias = false;
-    if (!find_conv(*c, n, &hit, &is_bias)) continue;
-    if (is_bias) {
-      if (numel != (size_t)c->cout_w) { err = n + ": wrong bias size"; return -4; }
-      if (hipMemcpyAsync(c->b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) { err = "copy failed"; return -10; }
-    } else if (c->down) {
-      if (numel != (size_t)c->cout_w * c->cin * 9) { err = n + ": wrong weight size"; return -4; }
-      repack_weights(s, *c, data);
-    } else {
-      if (numel != (size_t)c->cout_w * c->cin * c->ks * c->ks) { err = n + ": wrong weight size"; return -4; }
-      repack_weights(s, *c, data);
-    }
-    return 0;
-  }
-  for (Norm* nm : norms) {
-    float* dst = nullptr;
-    if (!find_norm(*nm, n, &dst)) continue;
-    if (numel != (size_t)nm->c) { err = n + ": wrong norm size"; return -4; }
-    if (hipMemcpyAsync(dst, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) { err = "copy failed"; return -10; }
-    return 0;
-  }
-  err = "unknown checkpoint entry '" + n + "'";
-  return -2;
-}
-
 namespace {
 // ConvDecoder.forward (autoencoder.py:399-423) from the latent in d->z
 void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s) {
@@ -810,37 +655,6 @@ void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipS
   launch_conv(s, &d->gn, d->conv_out, d->buf[xi], d->gn.ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, res, res, true);
 }
 }  // namespace
-
-int dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s, std::string& err) {
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
-  const mb_dec_cfg& c = d->c;
-  const size_t npix = (size_t)B * c.latent_size * c.latent_size;
-  if (d->vq) {                                        // SimpleVectorizer.get_codebook_entry (quantizer.py:105-119): codebook rows
-    if (!d->cb_loaded) { err = "the codebook (quantize.embedding.weight) is not loaded"; return -1; }
-    vq_gather(d->q, tokens, npix, d->z, d->conv_in.cin_pad, d->sat, s);
-  } else {
-    hipLaunchKernelGGL(latent_kernel, dim3((unsigned)std::min<size_t>(2048, (npix * CK + 255) / 256)), dim3(256), 0, s,
-                       tokens, d->z, npix, c.token_size);
-  }
-  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
-  return 0;
-}
-
-int dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s, std::string& err) {
-  if (!d->vq) { err = "decode of a float latent needs a lookup (VQ) handle"; return -1; }
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
-  const int hw = d->c.latent_size * d->c.latent_size;
-  vq_pack_latent(z_nchw, B, d->c.token_size, hw, d->z, d->conv_in.cin_pad, d->sat, s);
-  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
-  return 0;
-}
-
-// ConvVQModel.encode (conv_vqgan.py:70-83): image [B,C,H,W] fp32 -> code indices [B, h*w] (+ optional +-1 latent / raw z, fp32 NCHW)
-int dec_saturation_count(mb_dec* d, unsigned* count, bool reset, hipStream_t s) {
-  if (hipMemcpyAsync(count, d->sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) return -10;
-  if (reset && hipMemsetAsync(d->sat, 0, sizeof(unsigned), s) != hipSuccess) return -10;
-  return hipStreamSynchronize(s) == hipSuccess ? 0 : -10;
-}
 
 namespace {
 // ConvEncoder.forward (autoencoder.py:264-286) -> index of the buffer holding z (fp16 NHWC, e_conv_out.cout channels per pixel); *res_out = its side
@@ -878,32 +692,6 @@ int encode_to_z(mb_dec* d, const float* img, int B, hipStream_t s, int* res_out)
 }
 }  // namespace
 
-int enc_encode_vq(mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, hipStream_t s, std::string& err) {
-  if (!d->has_enc) { err = "this engine was created without the encoder half (mb_dec_cfg.build_encoder)"; return -1; }
-  if (!d->vq) { err = "not a lookup (VQ) handle"; return -1; }
-  if (!d->cb_loaded) { err = "the codebook (quantize.embedding.weight) is not loaded"; return -1; }
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
-  int res = 0;
-  const int t = encode_to_z(d, img, B, s, &res);
-  const int hw = res * res, N = B * hw;
-  vq_prep_rows(d->q, d->buf[t], d->e_conv_out.cout, nullptr, N, hw, d->vq_zT, zraw, s);
-  vq_search(d->q, d->vq_zT, N, hw, vq_splits(d->q, N, 0), d->vq_ps, d->vq_pi, indices, zq, row_dist, s);
-  return 0;
-}
-
-int enc_encode(mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, int B, hipStream_t s, std::string& err) {
-  if (d->vq) return enc_encode_vq(d, img, indices, zq, zraw, nullptr, B, s, err);
-  if (!d->has_enc) { err = "this engine was created without the encoder half (mb_dec_cfg.build_encoder)"; return -1; }
-  if (B <= 0 || B > d->max_batch) { err = "batch outside [1, max_batch]"; return -1; }
-  const mb_dec_cfg& c = d->c;
-  int res = 0;
-  const int t = encode_to_z(d, img, B, s, &res);
-  const size_t np = (size_t)B * res * res;
-  hipLaunchKernelGGL(lfq_kernel, dim3((unsigned)std::min<size_t>(1024, (np + 255) / 256)), dim3(256), 0, s, d->buf[t], indices, zq, zraw, B, res * res,
-                     c.token_size, d->e_conv_out.cout);
-  return 0;
-}
-
 // ---- single layers on caller buffers (include/maskbit_hip_diag.h): the helpers above on a scratch context instead of a handle ----------------
 namespace {
 struct Scratch {                                   // device allocations of one diagnostic call
@@ -919,63 +707,63 @@ struct Scratch {                                   // device allocations of one 
 size_t gn_part_elems(int B, int H, int W) { return (size_t)B * std::max(GN_MAXCHUNK, (H / TH8) * (W / TW)) * 64; }
 }  // namespace
 
-int diag_groupnorm(const void* x, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, hipStream_t s, std::string& err) {
-  if (B <= 0 || HW <= 0 || C < 32 || C > 2048 || C % 32 || (C / 8) > 256) { err = "C must be a multiple of 32 in [32, 2048]"; return -1; }
+int diag_groupnorm(const void* x, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, hipStream_t s) {
+  if (B <= 0 || HW <= 0 || C < 32 || C > 2048 || C % 32 || (C / 8) > 256) return fail(-1, "mb_groupnorm_stats: C must be a multiple of 32 in [32, 2048]");
   Scratch m;
   GnCtx gc;
-  if (!m.get(&gc.part, (size_t)B * GN_MAXCHUNK * 64) || !m.get(&gc.ss, (size_t)B * C)) { err = "hipMalloc failed"; return -10; }
+  if (!m.get(&gc.part, (size_t)B * GN_MAXCHUNK * 64) || !m.get(&gc.ss, (size_t)B * C)) return fail(-10, "mb_groupnorm_stats: hipMalloc failed");
   Norm n; n.c = C; n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta);
   launch_gn(s, &gc, n, (const h16*)x, B, HW);      // gc.of is null: the sweep (gn_partial_kernel) + gn_finalize_kernel
   if (hipMemcpyAsync(scale_shift, gc.ss, (size_t)B * C * sizeof(float2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) { err = "copy failed"; return -10; }
+      hipStreamSynchronize(s) != hipSuccess) return fail(-10, "mb_groupnorm_stats: copy failed");
   return 0;
 }
 
-int diag_pool(bool avg, const void* x, void* y, int B, int H, int W, int C, hipStream_t s, std::string& err) {
-  if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8) { err = "H and W must be even, C a multiple of 8"; return -1; }
+int diag_pool(const char* what, bool avg, const void* x, void* y, int B, int H, int W, int C, hipStream_t s) {
+  if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8) return fail(-1, "%s: H and W must be even, C a multiple of 8", what);
   if (avg) launch_avgpool2(s, (const h16*)x, (h16*)y, B, H, W, C);
   else launch_s2d(s, (const h16*)x, (h16*)y, B, H, W, C);
   return 0;
 }
 
-int diag_conv(const ConvDiag& q, hipStream_t s, std::string& err) {
+int diag_conv(const ConvDiag& q, hipStream_t s) {
   const int B = q.B, H = q.H, W = q.W;
   const bool fin = q.final_layer != 0, up = q.up != 0;
-  if (!q.in || !q.w || B <= 0 || q.Cin <= 0 || q.Cout <= 0) { err = "null or empty argument"; return -1; }
-  if (q.ks < 1 || q.ks > 3) { err = "ks must be 1, 2 or 3"; return -1; }
-  if (H <= 0 || W <= 0 || H % TH8 || W % TW) { err = "the output must be whole 8 x 16 pixel tiles"; return -1; }
-  if (fin && (q.ks != 3 || up || q.Cout > 4 || q.residual || !(q.img_nchw || q.img_u8))) { err = "final layer: ks 3, at most 4 channels, no residual, an image output"; return -1; }
-  if (!fin && (!q.out || q.Cout % 4)) { err = "fp16 output: Cout must be a multiple of 4"; return -1; }
-  if (up && q.ks != 3) { err = "upsampling goes with ks 3"; return -1; }
-  if (q.ks == 2 && (q.Cin % 16 || q.gamma)) { err = "ks 2 (stride-2 conv): Cin must be a multiple of 16, no prologue"; return -1; }
-  if ((q.gamma != nullptr) != (q.beta != nullptr) || (q.gamma && (q.Cin % CK || q.Cin > 2048))) { err = "prologue: gamma and beta, Cin a multiple of 64 up to 2048"; return -1; }
-  if (q.out_scale_shift && (fin || !q.out_gamma || !q.out_beta || q.Cout % 32 || q.Cout > 2048)) { err = "output statistics: gamma and beta, Cout a multiple of 32 up to 2048"; return -1; }
+  if (!q.in || !q.w || B <= 0 || q.Cin <= 0 || q.Cout <= 0) return fail(-1, "mb_conv_layer: null or empty argument");
+  if (q.ks < 1 || q.ks > 3) return fail(-1, "mb_conv_layer: ks must be 1, 2 or 3");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_conv_layer: the output must be whole 8 x 16 pixel tiles");
+  if (fin && (q.ks != 3 || up || q.Cout > 4 || q.residual || !(q.img_nchw || q.img_u8))) return fail(-1, "mb_conv_layer: final layer: ks 3, at most 4 channels, no residual, an image output");
+  if (!fin && (!q.out || q.Cout % 4)) return fail(-1, "mb_conv_layer: fp16 output: Cout must be a multiple of 4");
+  if (up && q.ks != 3) return fail(-1, "mb_conv_layer: upsampling goes with ks 3");
+  if (q.ks == 2 && (q.Cin % 16 || q.gamma)) return fail(-1, "mb_conv_layer: ks 2 (stride-2 conv): Cin must be a multiple of 16, no prologue");
+  if ((q.gamma != nullptr) != (q.beta != nullptr) || (q.gamma && (q.Cin % CK || q.Cin > 2048))) return fail(-1, "mb_conv_layer: prologue: gamma and beta, Cin a multiple of 64 up to 2048");
+  if (q.out_scale_shift && (fin || !q.out_gamma || !q.out_beta || q.Cout % 32 || q.Cout > 2048)) return fail(-1, "mb_conv_layer: output statistics: gamma and beta, Cout a multiple of 32 up to 2048");
   Conv c;
   if (q.ks == 2) shape_down_conv(c, q.Cin); else shape_conv(c, q.Cin, q.Cout, q.ks, q.bias != nullptr, up, fin);
   if (q.ks == 2) { c.cout = q.Cout; c.cout_w = q.Cout; c.cout_pad = (q.Cout + 127) / 128 * 128; c.has_bias = q.bias != nullptr; }
   Scratch m;
   GnCtx gc;
   const int Hin = q.ks == 2 ? 2 * H : (up ? H / 2 : H), Win = q.ks == 2 ? 2 * W : (up ? W / 2 : W);   // the caller's input tensor
-  if (up && (H % 2 || W % 2)) { err = "upsampling needs even H and W"; return -1; }
+  if (up && (H % 2 || W % 2)) return fail(-1, "mb_conv_layer: upsampling needs even H and W");
   const size_t npix_in = (size_t)B * Hin * Win;
   h16* staged = nullptr;
   if (!m.get(&c.w, conv_weight_elems(c)) || !m.get(&c.b, (size_t)c.cout_pad) || !m.get(&c.sat, 1) ||
-      !m.get(&gc.part, gn_part_elems(B, std::max(H, Hin), std::max(W, Win))) || !m.get(&gc.ss, (size_t)B * std::max(c.cin_pad, std::max(q.Cout, 1)))) { err = "hipMalloc failed"; return -10; }
+      !m.get(&gc.part, gn_part_elems(B, std::max(H, Hin), std::max(W, Win))) || !m.get(&gc.ss, (size_t)B * std::max(c.cin_pad, std::max(q.Cout, 1)))) return fail(-10, "mb_conv_layer: hipMalloc failed");
   bool ok = hipMemsetAsync(c.b, 0, c.cout_pad * sizeof(float), s) == hipSuccess && hipMemsetAsync(c.sat, 0, sizeof(unsigned), s) == hipSuccess;
   if (ok && q.bias) ok = hipMemcpyAsync(c.b, q.bias, (size_t)q.Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
   repack_weights(s, c, q.w);
   const h16* in = (const h16*)q.in;
   if (q.ks == 2) {                                  // [B, 2H, 2W, Cin] -> [B, H, W, 4 Cin]
-    if (!m.get(&staged, npix_in * q.Cin)) { err = "hipMalloc failed"; return -10; }
+    if (!m.get(&staged, npix_in * q.Cin)) return fail(-10, "mb_conv_layer: hipMalloc failed");
     launch_s2d(s, in, staged, B, Hin, Win, q.Cin);
     in = staged;
   } else if (c.cin_pad != q.Cin) {                  // channels padded with zeros to a whole chunk, as pack_image_kernel / latent_kernel leave them
-    if (!m.get(&staged, npix_in * c.cin_pad)) { err = "hipMalloc failed"; return -10; }
+    if (!m.get(&staged, npix_in * c.cin_pad)) return fail(-10, "mb_conv_layer: hipMalloc failed");
     ok = ok && hipMemsetAsync(staged, 0, npix_in * c.cin_pad * sizeof(h16), s) == hipSuccess &&
          hipMemcpy2DAsync(staged, c.cin_pad * sizeof(h16), in, q.Cin * sizeof(h16), q.Cin * sizeof(h16), npix_in, hipMemcpyDeviceToDevice, s) == hipSuccess;
     in = staged;
   }
-  if (!ok) { err = "copy failed"; return -10; }
+  if (!ok) return fail(-10, "mb_conv_layer: copy failed");
   const float2* gn = nullptr;
   if (q.gamma) {
     Norm n; n.c = q.Cin; n.g = const_cast<float*>(q.gamma); n.b = const_cast<float*>(q.beta);
@@ -993,9 +781,269 @@ int diag_conv(const ConvDiag& q, hipStream_t s, std::string& err) {
   }
   unsigned nsat = 0;
   ok = ok && hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) { err = "copy failed"; return -10; }
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_conv_layer: copy failed");
   if (q.saturated) *q.saturated = nsat;
   return 0;
 }
 
 }  // namespace mb
+
+// ================================================================================================
+// C entry points of the tokenizer handle (include/maskbit_hip.h)
+// ================================================================================================
+using namespace mb;
+
+namespace {
+
+// mb_dec_create / mb_dec_create_vq (`what`).  codebook_size > 0: a lookup (VQ) handle with that many entries; 0: the LFQ handle
+int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int codebook_size, int l2_normalize, mb_dec** out) {
+  const int R = cfg.num_resolutions;
+  const bool vq = codebook_size > 0;
+  if (R < 1 || R > 7) return fail(-1, "%s: num_resolutions out of range", what);
+  if (cfg.hidden_channels % 64) return fail(-1, "%s: hidden_channels must be a multiple of 64 for the HIP decoder", what);
+  if (!vq && (cfg.token_size > CK || cfg.token_size < 1)) return fail(-1, "%s: token_size must be in [1, 64]", what);
+  if (vq && (cfg.token_size > 256 || cfg.token_size < 1)) return fail(-1, "%s: token_size must be in [1, 256]", what);
+  if (cfg.latent_size % 16) return fail(-1, "%s: latent_size must be a multiple of 16", what);
+  if (cfg.num_channels > 4) return fail(-1, "%s: num_channels > 4 unsupported", what);
+  mb_dec* d = new mb_dec();
+  d->c = cfg; d->max_batch = max_batch; d->out_res = cfg.latent_size << (R - 1);
+  bool ok = dalloc(d, &d->sat, 1);
+  if (ok) (void)hipMemset(d->sat, 0, sizeof(unsigned));
+  const int hc = cfg.hidden_channels;
+  std::vector<int> mult(cfg.channel_mult, cfg.channel_mult + R);
+  mult.push_back(cfg.channel_mult[R - 1]);
+  const int top = hc * cfg.channel_mult[R - 1];
+  ok = ok && init_conv(d, d->conv_in, "decoder.conv_in", cfg.token_size, top, 3, true, false, false);
+  d->mid.resize(cfg.num_res_blocks);
+  for (int r = 0; ok && r < cfg.num_res_blocks; ++r)
+    ok = init_block(d, d->mid[r], "decoder.mid.res_blocks." + std::to_string(r), top, top);
+  d->up.resize(R);
+  int last = top;
+  size_t max_elems = 0;
+  int res = cfg.latent_size;
+  max_elems = std::max((size_t)res * res * top, (size_t)d->out_res * d->out_res * (size_t)std::max(CK, hc));
+  for (int s = 0; ok && s < R; ++s) {                    // up.0 = coarsest level (autoencoder.py:384-392)
+    const int lvl = R - 1 - s;
+    const int cin = hc * mult[lvl + 1], cout = hc * mult[lvl];
+    Stage& st = d->up[s];
+    st.blocks.resize(cfg.num_res_blocks);
+    int c = cin;
+    for (int r = 0; ok && r < cfg.num_res_blocks; ++r) {
+      ok = init_block(d, st.blocks[r], "decoder.up." + std::to_string(s) + ".res_blocks." + std::to_string(r), c, cout);
+      c = cout;
+    }
+    max_elems = std::max(max_elems, (size_t)res * res * std::max(cin, cout));
+    st.has_up = lvl > 0;
+    if (ok && st.has_up) {
+      ok = init_conv(d, st.up, "decoder.up." + std::to_string(s) + ".upsample_conv", cout, cout, 3, true, true, false);
+      res *= 2;
+      max_elems = std::max(max_elems, (size_t)res * res * cout);
+    }
+    last = cout;
+  }
+  ok = ok && init_norm(d, d->norm_out, "decoder.norm_out", last) &&
+       init_conv(d, d->conv_out, "decoder.conv_out", last, cfg.num_channels, 3, true, false, true);
+  if (ok && cfg.build_encoder) {                          // ConvEncoder (autoencoder.py:230-262): mirrors the decoder top-down
+    const int enrb = cfg.enc_res_blocks > 0 ? cfg.enc_res_blocks : cfg.num_res_blocks;
+    std::vector<int> imult{1};
+    imult.insert(imult.end(), cfg.channel_mult, cfg.channel_mult + R);
+    ok = ok && init_conv(d, d->e_conv_in, "encoder.conv_in", cfg.num_channels, hc, 3, false, false, false);
+    d->e_down.resize(R);
+    for (int s = 0; ok && s < R; ++s) {
+      const int cin = hc * imult[s], cout = hc * imult[s + 1];
+      Stage& st = d->e_down[s];
+      st.blocks.resize(enrb);
+      int c = cin;
+      for (int r = 0; ok && r < enrb; ++r) {
+        ok = init_block(d, st.blocks[r], "encoder.down." + std::to_string(s) + ".res_blocks." + std::to_string(r), c, cout);
+        c = cout;
+      }
+      st.has_up = s < R - 1;                              // a downsampling step follows: down_conv, or avg_pool2d when !sample_with_conv
+      st.up.cin = cout;
+      if (ok && st.has_up && cfg.sample_with_conv) {      // DownsamplingStage.down_conv: 3x3, stride 2, bias (autoencoder.py:165)
+        Conv& dc = st.up;
+        dc.name = "encoder.down." + std::to_string(s) + ".down_conv"; dc.sat = d->sat;
+        shape_down_conv(dc, cout);
+        ok = dalloc(d, &dc.w, conv_weight_elems(dc)) && dalloc(d, &dc.b, (size_t)dc.cout_pad);
+        if (ok) (void)hipMemset(dc.b, 0, dc.cout_pad * sizeof(float));
+      }
+    }
+    d->e_mid.resize(enrb);
+    for (int r = 0; ok && r < enrb; ++r)
+      ok = init_block(d, d->e_mid[r], "encoder.mid.res_blocks." + std::to_string(r), top, top);
+    const int k4 = (cfg.token_size + 3) / 4 * 4;           // stored channel count of z (8-byte stores)
+    ok = ok && init_norm(d, d->e_norm_out, "encoder.norm_out", top) &&
+         init_conv(d, d->e_conv_out, "encoder.conv_out", top, k4, 1, true, false, false);
+    d->e_conv_out.cout_w = cfg.token_size;
+    d->has_enc = ok;
+  }
+  for (int i = 0; ok && i < 3; ++i) ok = dalloc(d, &d->buf[i], (size_t)max_batch * max_elems);
+  const size_t nlat = (size_t)max_batch * cfg.latent_size * cfg.latent_size;
+  ok = ok && dalloc(d, &d->z, nlat * d->conv_in.cin_pad) &&
+       dalloc(d, &d->gn.part, (size_t)max_batch * std::max(GN_MAXCHUNK, (d->out_res / TH8) * (d->out_res / TW)) * 64) &&
+       dalloc(d, &d->gn.ss, (size_t)max_batch * 4096);
+  if (ok && vq) {
+    VqCodebook& q = d->q;
+    q.C = codebook_size; q.K = cfg.token_size; q.Kp = vq_kp(q.K); q.Cpad = vq_cpad(q.C); q.l2 = l2_normalize ? 1 : 0;
+    const size_t npad = (size_t)vq_npad((int)nlat);
+    ok = dalloc(d, &q.cb, (size_t)q.C * q.K) && dalloc(d, &q.cbT, (size_t)q.Kp * q.Cpad) && dalloc(d, &q.cbn, (size_t)q.Cpad) &&
+         dalloc(d, &d->vq_zT, (size_t)q.Kp * npad) && dalloc(d, &d->vq_ps, VQ_SPLIT_MAX * npad) &&
+         dalloc(d, &d->vq_pi, VQ_SPLIT_MAX * npad);
+    d->vq = ok;
+  }
+  if (!ok) {
+    const hipError_t e = d->alloc_error;
+    mb_dec_destroy(d);
+    return fail(-1, "%s: hipMalloc failed: %s", what, hipGetErrorString(e));
+  }
+  *out = d;
+  return 0;
+}
+
+// ConvVQModel.encode with the lookup quantizer: mb_enc_encode_vq, and mb_enc_encode on a lookup handle (`what`)
+int encode_vq(const char* what, mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, hipStream_t s) {
+  ProfScope p("encode", s);
+  if (!d->has_enc) return fail(-1, "%s: this engine was created without the encoder half (mb_dec_cfg.build_encoder)", what);
+  if (!d->vq) return fail(-1, "%s: not a lookup (VQ) handle", what);
+  if (!d->cb_loaded) return fail(-1, "%s: the codebook (quantize.embedding.weight) is not loaded", what);
+  if (B <= 0 || B > d->max_batch) return fail(-1, "%s: batch outside [1, max_batch]", what);
+  int res = 0;
+  const int t = encode_to_z(d, img, B, s, &res);
+  const int hw = res * res, N = B * hw;
+  vq_prep_rows(d->q, d->buf[t], d->e_conv_out.cout, nullptr, N, hw, d->vq_zT, zraw, s);
+  vq_search(d->q, d->vq_zT, N, hw, vq_splits(d->q, N, 0), d->vq_ps, d->vq_pi, indices, zq, row_dist, s);
+  return launched();
+}
+
+}  // namespace
+
+extern "C" {
+
+int mb_dec_create(const mb_dec_cfg* cfg, int max_batch, mb_dec** out) {
+  if (!cfg || !out || max_batch <= 0) return fail(-1, "mb_dec_create: bad arguments");
+  return create_handle("mb_dec_create", *cfg, max_batch, 0, 0, out);
+}
+int mb_dec_create_vq(const mb_dec_cfg* cfg, int codebook_size, int l2_normalize, int max_batch, mb_dec** out) {
+  if (!cfg || !out || max_batch <= 0) return fail(-1, "mb_dec_create_vq: bad arguments");
+  if (codebook_size < 2 || codebook_size > 65536) return fail(-1, "mb_dec_create_vq: codebook_size %d outside [2, 65536]", codebook_size);
+  return create_handle("mb_dec_create_vq", *cfg, max_batch, codebook_size, l2_normalize, out);
+}
+void mb_dec_destroy(mb_dec* d) {
+  if (!d) return;
+  for (void* p : d->owned) (void)hipFree(p);
+  delete d;
+}
+
+int mb_dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
+  if (!d || !name || !data) return fail(-1, "mb_dec_load: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const std::string n(name);
+  if (d->vq && n == "quantize.embedding.weight") {                               // SimpleVectorizer.embedding [C, K]
+    if (ndim != 2 || shape[0] != d->q.C || shape[1] != d->q.K) return fail(-4, "mb_dec_load: %s: expected [codebook_size, token_size]", name);
+    vq_prep_codebook(d->q, data, s);
+    d->cb_loaded = true;
+    return 0;
+  }
+  if (n.rfind("quantize.", 0) == 0) return 0;                                    // derived buffers
+  if (n.rfind("encoder.", 0) == 0 && !d->has_enc) return 0;                       // encode half not built in this engine
+  size_t numel = 1;
+  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
+  std::vector<Conv*> convs{&d->conv_in, &d->conv_out};
+  std::vector<Norm*> norms{&d->norm_out};
+  auto add_block = [&](ResBlock& rb) {
+    convs.push_back(&rb.c1); convs.push_back(&rb.c2); if (rb.has_sc) convs.push_back(&rb.sc);
+    norms.push_back(&rb.n1); norms.push_back(&rb.n2);
+  };
+  for (auto& rb : d->mid) add_block(rb);
+  for (auto& st : d->up) { for (auto& rb : st.blocks) add_block(rb); if (st.has_up) convs.push_back(&st.up); }
+  if (d->has_enc) {
+    convs.push_back(&d->e_conv_in); convs.push_back(&d->e_conv_out); norms.push_back(&d->e_norm_out);
+    for (auto& rb : d->e_mid) add_block(rb);
+    for (auto& st : d->e_down) { for (auto& rb : st.blocks) add_block(rb); if (st.has_up && d->c.sample_with_conv) convs.push_back(&st.up); }
+  }
+  for (Conv* c : convs) {
+    Conv* hit = nullptr; bool is_bias = false;
+    if (!find_conv(*c, n, &hit, &is_bias)) continue;
+    if (is_bias) {
+      if (numel != (size_t)c->cout_w) return fail(-4, "mb_dec_load: %s: wrong bias size", name);
+      if (hipMemcpyAsync(c->b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(-10, "mb_dec_load: copy failed");
+    } else if (c->down) {
+      if (numel != (size_t)c->cout_w * c->cin * 9) return fail(-4, "mb_dec_load: %s: wrong weight size", name);
+      repack_weights(s, *c, data);
+    } else {
+      if (numel != (size_t)c->cout_w * c->cin * c->ks * c->ks) return fail(-4, "mb_dec_load: %s: wrong weight size", name);
+      repack_weights(s, *c, data);
+    }
+    return 0;
+  }
+  for (Norm* nm : norms) {
+    float* dst = nullptr;
+    if (!find_norm(*nm, n, &dst)) continue;
+    if (numel != (size_t)nm->c) return fail(-4, "mb_dec_load: %s: wrong norm size", name);
+    if (hipMemcpyAsync(dst, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(-10, "mb_dec_load: copy failed");
+    return 0;
+  }
+  return fail(-2, "mb_dec_load: unknown checkpoint entry '%s'", name);
+}
+
+int mb_dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
+  if (!d || !tokens) return fail(-1, "mb_dec_decode: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope p("decode", s);
+  if (B <= 0 || B > d->max_batch) return fail(-1, "mb_dec_decode: batch outside [1, max_batch]");
+  const mb_dec_cfg& c = d->c;
+  const size_t npix = (size_t)B * c.latent_size * c.latent_size;
+  if (d->vq) {                                        // SimpleVectorizer.get_codebook_entry (quantizer.py:105-119): codebook rows
+    if (!d->cb_loaded) return fail(-1, "mb_dec_decode: the codebook (quantize.embedding.weight) is not loaded");
+    vq_gather(d->q, tokens, npix, d->z, d->conv_in.cin_pad, d->sat, s);
+  } else {
+    hipLaunchKernelGGL(latent_kernel, dim3((unsigned)std::min<size_t>(2048, (npix * CK + 255) / 256)), dim3(256), 0, s,
+                       tokens, d->z, npix, c.token_size);
+  }
+  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
+  return launched();
+}
+int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
+  if (!d || !z_nchw) return fail(-1, "mb_dec_decode_latent: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope p("decode", s);
+  if (!d->vq) return fail(-1, "mb_dec_decode_latent: decode of a float latent needs a lookup (VQ) handle");
+  if (B <= 0 || B > d->max_batch) return fail(-1, "mb_dec_decode_latent: batch outside [1, max_batch]");
+  const int hw = d->c.latent_size * d->c.latent_size;
+  vq_pack_latent(z_nchw, B, d->c.token_size, hw, d->z, d->conv_in.cin_pad, d->sat, s);
+  decode_from_z(d, img_nchw, img_nhwc_u8, B, s);
+  return launched();
+}
+
+// synchronises the stream
+int mb_dec_saturation_count(mb_dec* d, unsigned* count, int reset, mb_stream stream) {
+  if (!d || !count) return fail(-1, "mb_dec_saturation_count: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(count, d->sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      (reset && hipMemsetAsync(d->sat, 0, sizeof(unsigned), s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
+    return fail(-10, "mb_dec_saturation_count: copy failed");
+  return 0;
+}
+
+// ConvVQModel.encode (conv_vqgan.py:70-83): image [B,C,H,W] fp32 -> code indices [B, h*w] (+ optional +-1 latent / raw z, fp32 NCHW)
+int mb_enc_encode(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, int B, mb_stream stream) {
+  if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (d->vq) return encode_vq("mb_enc_encode", d, img_nchw, indices, zq, zraw, nullptr, B, s);
+  ProfScope p("encode", s);
+  if (!d->has_enc) return fail(-1, "mb_enc_encode: this engine was created without the encoder half (mb_dec_cfg.build_encoder)");
+  if (B <= 0 || B > d->max_batch) return fail(-1, "mb_enc_encode: batch outside [1, max_batch]");
+  const mb_dec_cfg& c = d->c;
+  int res = 0;
+  const int t = encode_to_z(d, img_nchw, B, s, &res);
+  const size_t np = (size_t)B * res * res;
+  hipLaunchKernelGGL(lfq_kernel, dim3((unsigned)std::min<size_t>(1024, (np + 255) / 256)), dim3(256), 0, s, d->buf[t], indices, zq, zraw, B, res * res,
+                     c.token_size, d->e_conv_out.cout);
+  return launched();
+}
+int mb_enc_encode_vq(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, mb_stream stream) {
+  if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode_vq: null argument");
+  return encode_vq("mb_enc_encode_vq", d, img_nchw, indices, zq, zraw, row_dist, B, (hipStream_t)stream);
+}
+
+}  // extern "C"

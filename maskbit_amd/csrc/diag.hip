@@ -1,0 +1,159 @@
+// Diagnostic entry points (include/maskbit_hip_diag.h): single kernels and single layers on caller buffers, for the tests and the tools.
+// No host binding of the product needs them.  Argument checks and the launchers' own calls only: this file holds no kernel.
+// (mb_gen_set_alo, the one entry of that header that needs the generator handle's members, is in engine.hip.)
+#include <hip/hip_runtime.h>
+
+#include "../../include/maskbit_hip_diag.h"
+#include "mb_abi.h"
+#include "mb_decoder.h"
+#include "mb_kernels.h"
+#include "mb_vq.h"
+
+using mb::fail;
+using mb::launched;
+using mb::ProfScope;
+
+namespace {
+
+// The common tail of the GEMM entries: the timed launch, the refusal message (`mini`: the entry's name, sequence-aligned tiles), the launch check.
+int run_gemm(mb_stream stream, int epi, const mb::GemmArgs& a, int variant, const char* mini = nullptr) {
+  ProfScope p("gemm_diag", (hipStream_t)stream);
+  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, variant))
+    return mini ? fail(-3, "%s: shape refused", mini) : fail(-3, "GEMM shape M=%d N=%d K=%d is outside the kernels' shapes", a.M, a.N, a.K);
+  return launched();
+}
+
+int w4_entry(const char* what, decltype(mb::w4_from_f32)* pack, const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
+  if (!W || !dst4 || !scale_out || N <= 0 || K <= 0 || N % 64 || K % 128) return fail(-1, "%s: bad arguments", what);
+  pack((hipStream_t)stream, W, (uint8_t*)dst4, N, K, (uint8_t*)scale_out);
+  return launched();
+}
+
+int pool_entry(const char* what, bool avg, const void* x, void* y, int B, int H, int W, int C, mb_stream stream) {
+  if (!x || !y) return fail(-1, "%s: null argument", what);
+  if (int rc = mb::diag_pool(what, avg, x, y, B, H, W, C, (hipStream_t)stream)) return rc;
+  return launched();
+}
+
+}  // namespace
+
+extern "C" {
+
+int mb_set_cu_count(int n) { mb::set_cu_count(n); return 0; }
+
+// ---- one GEMM of the trunk family on caller buffers (tests and tools/gemm_bench.py) ----
+int mb_gemm(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16,
+            int M, int N, int K, int period, int variant, mb_stream stream) {
+  if (!A || !W || !bias || epi < 0 || epi > 4) return fail(-1, "mb_gemm: bad arguments");
+  if (K % 64) return fail(-1, "mb_gemm: K must be a multiple of 64");
+  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, K, period};
+  return run_gemm(stream, epi, a, variant);
+}
+int mb_gemm_ex(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16,
+               int M, int N, int K, const float* ln_stats, const float* ln_g, const float* ln_b, int period, int variant, mb_stream stream) {
+  if (!A || !W || !bias || epi < 0 || epi > 4) return fail(-1, "mb_gemm_ex: bad arguments");
+  if (K % 64) return fail(-1, "mb_gemm_ex: K must be a multiple of 64");
+  if (ln_stats && (!ln_g || !ln_b || epi != mb::EPI_RES_F32)) return fail(-1, "mb_gemm_ex: LayerNorm residual needs gamma, beta and the fp32+residual epilogue");
+  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, K, period, nullptr, ln_stats, ln_g, ln_b};
+  return run_gemm(stream, epi, a, variant);
+}
+int mb_gemm_act_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, const float* residual, float* out_f32,
+                      void* out_h16, int M, int N, int kw, int variant, mb_stream stream) {
+  if (!A_hi || !A_lo || !W || !bias || epi < 0 || epi > 3 || kw <= 0 || kw % 64) return fail(-1, "mb_gemm_act_split: bad arguments");
+  mb::GemmArgs a{(const h16*)A_hi, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, 2 * kw, 0};
+  a.A2 = (const h16*)A_lo; a.kw = kw;
+  return run_gemm(stream, epi, a, variant);
+}
+int mb_gemm_mini(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16, void* out4,
+                 void* out4_scale, int rows, int pair, int N, int K, int nlo, const void* const* lo /* nlo x {A4, a_scale, W4, w_scale} */, mb_stream stream) {
+  return mb_gemm_mini_seq(epi, A, W, bias, residual, out_f32, out_h16, out4, out4_scale, nullptr, nullptr, rows, pair, 0, N, K, nlo, lo, stream);
+}
+int mb_gemm_mini_seq(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16, void* out4,
+                     void* out4_scale, void* out4l, void* out4l_scale, int rows, int pair, int seq_rows, int N, int K, int nlo, const void* const* lo, mb_stream stream) {
+  if ((out4l || out4l_scale) && (!out4l || !out4l_scale || !out4 || !out4_scale)) return fail(-1, "mb_gemm_mini_seq: the lo copy (out4l / out4l_scale) rides with the value copy (out4 / out4_scale)");
+  if (!A || !W || !bias || epi < 0 || epi > 2 || rows <= 0 || K <= 0 || K % 64 || nlo < 0 || nlo > 2 || (nlo && !lo)) return fail(-1, "mb_gemm_mini: bad arguments");
+  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, pair ? 2 * rows : rows, N, K, 0};
+  if (pair) a.pair_rows = rows;
+  a.seq_rows = seq_rows;
+  a.nlo = nlo;
+  for (int i = 0; i < nlo; ++i) a.lo[i] = {(const uint8_t*)lo[4 * i], (const uint8_t*)lo[4 * i + 1], (const uint8_t*)lo[4 * i + 2], (const uint8_t*)lo[4 * i + 3]};
+  a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale;
+  a.out4l = (uint8_t*)out4l; a.out4l_scale = (uint8_t*)out4l_scale;
+  if ((!seq_rows && a.M % 257) || !mb::gemm_ht_supported((mb::GemmEpi)epi, a)) return fail(-3, "mb_gemm_mini: shape not supported by the sequence-aligned tiles");
+  return run_gemm(stream, epi, a, 257, "mb_gemm_mini");
+}
+int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, void* out_h16, void* out4, void* out4_scale,
+                       int rows, int N, int kw, const void* const* lo /* {A4, a_scale, W4, w_scale} */, mb_stream stream) {
+  if (!A_hi || !A_lo || !W || !bias || !out_h16 || !lo || epi < 0 || epi > 1 || rows <= 0 || rows % 257 || kw <= 0 || kw % 128)
+    return fail(-1, "mb_gemm_mini_split: bad arguments");
+  mb::GemmArgs a{(const h16*)A_hi, (const h16*)W, bias, nullptr, nullptr, (h16*)out_h16, rows, N, 2 * kw, 0};
+  a.A2 = (const h16*)A_lo; a.kw = kw;
+  a.nlo = 1;
+  a.lo[0] = {(const uint8_t*)lo[0], (const uint8_t*)lo[1], (const uint8_t*)lo[2], (const uint8_t*)lo[3]};
+  a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale;
+  if (!mb::gemm_ht_supported((mb::GemmEpi)epi, a)) return fail(-3, "mb_gemm_mini_split: shape not supported by the sequence-aligned tiles");
+  return run_gemm(stream, epi, a, 257, "mb_gemm_mini_split");
+}
+
+int mb_w4_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
+  return w4_entry("mb_w4_from_f32", mb::w4_from_f32, W, N, K, dst4, scale_out, stream);
+}
+int mb_w4lo_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
+  return w4_entry("mb_w4lo_from_f32", mb::w4lo_from_f32, W, N, K, dst4, scale_out, stream);
+}
+
+int mb_layernorm(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x_lo, float* stats, int M,
+                 int d, mb_stream stream) {
+  if (!y || !gamma || !beta || M <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_layernorm: bad arguments");
+  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, stats, M, d, (h16*)x_lo);
+  return launched();
+}
+int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+                    void* xl4_scale, int M, int d, mb_stream stream) {
+  if (!y || !gamma || !beta || (!x4 && !xl4) || (x4 && !x4_scale) || (xl4 && !xl4_scale) || M <= 0 || M % 257 || (d != 768 && d != 1024))
+    return fail(-1, "mb_layernorm_f4: bad arguments (d must be 768 or 1024, M a multiple of 257)");
+  mb::Fp4Rows f4{(uint8_t*)x4, (uint8_t*)x4_scale, (uint8_t*)xl4, (uint8_t*)xl4_scale, M / 257};
+  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4);
+  return launched();
+}
+
+int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, int heads, mb_stream stream) {
+  if (!qkv || !out_h16 || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair: bad arguments");
+  ProfScope p("attention", (hipStream_t)stream);
+  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, nullptr, nullptr))
+    return fail(-3, "mb_attention_pair: head width %d (N = %d tokens) is outside the attention kernels", d / heads, N);
+  return launched();
+}
+int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_scale, void* out4l, void* out4l_scale, int pairs, int N, int d, int heads, mb_stream stream) {
+  if (!qkv || !out_h16 || !out4 || !out4_scale || (!out4l) != (!out4l_scale) || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair_f4: bad arguments");
+  ProfScope p("attention", (hipStream_t)stream);
+  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale, (uint8_t*)out4l, (uint8_t*)out4l_scale))
+    return fail(-3, "mb_attention_pair_f4: head width %d / N = %d tokens: no e2m1 copy for this shape", d / heads, N);
+  return launched();
+}
+
+int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream) {
+  if (!z || !codebook || !idx) return fail(-1, "mb_vq_argmin: null argument");
+  if (int rc = mb::vq_argmin(z, codebook, N, C, K, l2, splits, idx, dist, (hipStream_t)stream)) return rc;
+  return launched();
+}
+
+// ---- single tokenizer layers on caller buffers (the handle's own launch helpers: mb::diag_* in decoder.hip) ----
+int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
+                  void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
+                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
+                  mb_stream stream) {
+  mb::ConvDiag q{in_h16, w_oihw, bias, gn_gamma, gn_beta, residual_h16, out_h16, img_nchw, img_nhwc_u8, out_gamma, out_beta, out_scale_shift,
+                 out_gn_part, part_tiles, saturated, B, H, W, Cin, Cout, ks, up, final_layer};
+  if (int rc = mb::diag_conv(q, (hipStream_t)stream)) return rc;
+  return launched();
+}
+int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream) {
+  if (!x_h16 || !gamma || !beta || !scale_shift) return fail(-1, "mb_groupnorm_stats: null argument");
+  if (int rc = mb::diag_groupnorm(x_h16, gamma, beta, scale_shift, B, HW, C, (hipStream_t)stream)) return rc;
+  return launched();
+}
+int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", true, x_h16, y_h16, B, H, W, C, stream); }
+int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", false, x_h16, y_h16, B, H, W, C, stream); }
+
+}  // extern "C"

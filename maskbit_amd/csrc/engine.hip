@@ -1,89 +1,25 @@
-// C ABI of libmaskbit_hip.so (include/maskbit_hip.h): handle objects, checkpoint ingest with h16
-// repack, the generator forward schedule, the fused sampling step and the whole sampling loop.
+// The generator handle of libmaskbit_hip.so (include/maskbit_hip.h): checkpoint ingest with h16 repack, the two forward schedules (plain and
+// differential CFG), the fused sampling step and the whole sampling loop; and the three ABI-wide entries (mb_abi_version, mb_last_error, mb_prof_*).
+// The tokenizer handle's entry points are in decoder.hip, the diagnostic ones (include/maskbit_hip_diag.h) in diag.hip -- all but mb_gen_set_alo,
+// which needs struct mb_gen; the error path and the profiling scopes they all share are in mb_abi.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/maskbit_hip_diag.h"
-#include "mb_decoder.h"
+#include "mb_abi.h"
 #include "mb_kernels.h"
-#include "mb_vq.h"
+
+using mb::fail;
+using mb::g_prof;
+using mb::launched;
+using mb::ProfScope;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(-10, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
-// ---- optional per-kernel device timing with HIP events on the launch stream ------------------
-struct Prof {
-  bool on = false;
-  // Generator forwards are sampled: the kernels of every `stride`-th forward are timed -- counted separately for GUIDED forwards (mb_gen_forward_cfg
-  // and the guided steps of mb_sample: kernel names as they are) and PLAIN ones (mb_gen_forward, the unguided / zero-scale steps: names + ".plain"),
-  // so that a plain forward never lands in a guided kernel's average whatever the step plan and the chunking (round-3 advice).
-  int stride = 1, tick[2] = {0, 0};
-  bool fwd_live = true, fwd_plain = false;
-  void begin_forward(bool plain) { fwd_plain = plain; fwd_live = (tick[plain]++ % stride) == stride / 2; }   // (the middle of every stride)
-  struct Rec { hipEvent_t a, b; int kind; };
-  std::vector<Rec> recs;
-  std::vector<std::string> names;
-  std::map<std::string, int> index;
-  std::map<int, std::pair<long, double>> acc;   // kind -> (calls, ms)
-  int kind(const char* n0, bool in_forward) {
-    const std::string n = (in_forward && fwd_plain) ? std::string(n0) + ".plain" : std::string(n0);
-    auto it = index.find(n);
-    if (it != index.end()) return it->second;
-    names.push_back(n);
-    return index[n] = (int)names.size() - 1;
-  }
-  void drain() {
-    for (auto& r : recs) {
-      float ms = 0.f;
-      if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-        acc[r.kind].first += 1; acc[r.kind].second += ms;
-      }
-      (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b);
-    }
-    recs.clear();
-  }
-} g_prof;
-
-struct ProfScope {
-  hipStream_t s; bool live; hipEvent_t a, b; int kind;
-  ProfScope(const char* name, hipStream_t st, bool in_forward = false) : s(st), live(g_prof.on && (!in_forward || g_prof.fwd_live)) {
-    if (!live) return;
-    kind = g_prof.kind(name, in_forward);
-    (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-    (void)hipEventRecord(a, s);
-  }
-  ~ProfScope() {
-    if (!live) return;
-    (void)hipEventRecord(b, s);
-    g_prof.recs.push_back({a, b, kind});
-  }
-};
 
 template <typename T>
 int dev_alloc(T** p, size_t n) {
@@ -96,6 +32,10 @@ int dev_alloc(T** p, size_t n) {
 // ================================================================================================
 // generator
 // ================================================================================================
+// An e2m1 (MX-fp4) copy of an activation: values at the row stride of the fp16 sibling (2 * width bytes, the first width / 2 used) and their
+// block-scale bytes in lane order, [width / 64][sequences][256]
+struct F4Buf { uint8_t *v = nullptr, *s = nullptr; };
+
 struct mb_gen {
   mb_gen_cfg c{};
   int max_seqs = 0, chunk_seqs = 0, N = 0, C = 0, gbits = 0, device = 0;   // chunk_seqs: sequences per forward pass (workspace size)
@@ -116,11 +56,11 @@ struct mb_gen {
   h16 *x_h16 = nullptr, *x_lo = nullptr, *qkv = nullptr, *att = nullptr, *h = nullptr;   // x_lo: lo halves of x_h16 (head GEMMs; precision >= 1: QKV / FFN-up of plain forwards)
   // precision >= 1: differential CFG forward (pair_ok = the shape allows it).  precision >= 2 (mini_ok = the shape allows it): every trunk GEMM carries the
   // MX-fp4 weight-correction mini-tiles (gemm_ht.hip, XP = 6) -- in the guided forward on the conditional rows, in the plain forward (257-token sequences)
-  // on every row: x4 / att4 / h4 hold e2m1 of the LayerNorm outputs, attention outputs and FFN hiddens (values; x4s / att4s / h4s their lane-ordered
-  // block scales), w4lo / w4los e2m1 of the weights' fp16 rounding errors.  precision 3 additionally corrects the fp16 rounding of the LayerNorm OUTPUTS
-  // in the guided forward's FFN-up GEMM: xl4 / xl4s = e2m1 of their lo halves, w4 / w4s = e2m1 of the (fp16) weight net.0.
+  // on every row: x4 / att4 / h4 hold e2m1 of the LayerNorm outputs, attention outputs and FFN hiddens,
+  // w4lo / w4los e2m1 of the weights' fp16 rounding errors.  precision 3 additionally corrects the fp16 rounding of the LayerNorm OUTPUTS
+  // in the guided forward's FFN-up GEMM: xl4 = e2m1 of their lo halves, w4 / w4s = e2m1 of the (fp16) weight net.0.
   bool pair_ok = false, mini_ok = false;
-  uint8_t *x4 = nullptr, *x4s = nullptr, *xl4 = nullptr, *xl4s = nullptr;
+  F4Buf x4, xl4;
   std::vector<uint8_t*> w4, w4s;                                                         // [4 * layer + {qkv, o, 1, 2}]: the GEMMs of alo_mask_built only
   float* logits_tmp = nullptr;                          // guided forwards over more pairs than one pass holds
   // The two head GEMMs run hi + lo inputs against hi + lo WEIGHTS in every mode (GemmArgs.W2: three sweeps): their rounding reaches the logits
@@ -131,8 +71,8 @@ struct mb_gen {
   float* head_scale = nullptr;
   unsigned* sat = nullptr;                              // lanes of the QKV / FFN-up epilogues that clamped a fp16 store (mb_gen_saturation_count)
   std::vector<uint8_t*> w4lo, w4los;                                                     // [4 * layer + {qkv, o, 1, 2}]
-  uint8_t *att4 = nullptr, *att4s = nullptr, *h4 = nullptr, *h4s = nullptr;              // e2m1 of the conditional attention outputs / FFN hiddens + block scales
-  uint8_t *attl4 = nullptr, *attl4s = nullptr, *hl4 = nullptr, *hl4s = nullptr;          // precision 4: e2m1 of their fp16 LO HALVES (activation-lo sets of out-proj / FFN-down)
+  F4Buf att4, h4;                                       // e2m1 of the conditional attention outputs / FFN hiddens
+  F4Buf attl4, hl4;                                     // precision 4: e2m1 of their fp16 LO HALVES (activation-lo sets of out-proj / FFN-down)
   // loop state for mb_sample
   // the run mb_sample is in the middle of (step chunks): samples, total steps, guidance flag, the step the next chunk must begin with (-1: no run)
   int loop_B = 0, loop_steps = 0, loop_guided = 0, loop_next = -1;
@@ -157,6 +97,15 @@ template <typename T>
 int galloc(mb_gen* g, T** p, size_t n) {
   int rc = dev_alloc(p, n);
   if (rc == 0) g->owned.push_back((void*)*p);
+  return rc;
+}
+
+// rows x width e2m1 values and the scale bytes of ntok = sequences x tokens rows, zeroed
+int galloc_f4(mb_gen* g, F4Buf* b, size_t rows, size_t width, size_t ntok) {
+  const size_t nv = rows * 2 * width, ns = (width / 64) * ntok + 256;
+  int rc = galloc(g, &b->v, nv);
+  rc |= galloc(g, &b->s, ns);
+  if (!rc) { (void)hipMemset(b->v, 0, nv); (void)hipMemset(b->s, 0, ns); }
   return rc;
 }
 
@@ -213,7 +162,7 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
   h16* const xlo_qkv = xlo_all ? g->x_lo : nullptr;
   // the LayerNorms write the MX-fp4 copy (+ scale bytes) only when a GEMM of THIS forward reads it (the buffers also exist for the pair forward)
   Fp4Rows f4x;
-  if (wm) { f4x.x4 = g->x4; f4x.x4s = g->x4s; f4x.nseq = nb; f4x.seq_rows = N; }
+  if (wm) { f4x.x4 = g->x4.v; f4x.x4s = g->x4.s; f4x.nseq = nb; f4x.seq_rows = N; }
   auto lo_set = [&](GemmArgs& ga, const uint8_t* a4, const uint8_t* a4s, int widx) {
     if (!wm) return;
     ga.nlo = 1; ga.lo[0] = {a4, a4s, g->w4lo[widx], g->w4los[widx]};
@@ -222,8 +171,8 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
   auto xgemm = [&](GemmEpi epi, const h16* W, const float* bias, h16* out, int Nout, int widx) {
     GemmArgs ga{g->x_h16, W, bias, nullptr, nullptr, out, M, Nout, d, 0};
     if (wm) ga.seq_rows = N;
-    lo_set(ga, g->x4, g->x4s, widx);
-    if (wm && epi == EPI_GELU_H16) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
+    lo_set(ga, g->x4.v, g->x4.s, widx);
+    if (wm && epi == EPI_GELU_H16) { ga.out4 = g->h4.v; ga.out4_scale = g->h4.s; }
     if (((widx & 3) == 2 || xlo_all) && xlo_layer(widx >> 2)) { ga.K = 2 * d; ga.A2 = g->x_lo; ga.kw = d; }   // FFN-up only with the correction (see above)
     ga.sat = g->sat;
     gemm_rc |= gemm_tn(s, epi, ga, wm ? 257 : 0);
@@ -252,24 +201,23 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     // x = x + FFN(LN(x)): the buffer holds x itself, every LayerNorm only produces the GEMM operand, the residual GEMMs add the buffer's own rows.
     if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, L.ln1g, L.ln1b, 1e-12f, nullptr, g->x_h16, nullptr, M, d, xlo_qkv, f4x); }
     { ProfScope p("gemm_qkv", s, true); xgemm(EPI_H16, L.wqkv, L.bqkv, g->qkv, 3 * d, 4 * l); }
-    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wm ? g->att4 : nullptr, wm ? g->att4s : nullptr); }
+    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wm ? g->att4.v : nullptr, wm ? g->att4.s : nullptr); }
     attn_rc |= attn_maps(l);
     { ProfScope p("gemm_attn_out", s, true);
       const bool re = !c.prenorm && l > 0;
-      rgemm(g->att, L.wo, L.bo, d, 4 * l + 1, g->att4, g->att4s, re ? g->layers[l - 1].ln2g : nullptr, re ? g->layers[l - 1].ln2b : nullptr); }
+      rgemm(g->att, L.wo, L.bo, d, 4 * l + 1, g->att4.v, g->att4.s, re ? g->layers[l - 1].ln2g : nullptr, re ? g->layers[l - 1].ln2b : nullptr); }
     { ProfScope p("layernorm", s, true);
       layernorm_rows(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, nullptr, g->x_h16, c.prenorm ? nullptr : g->ln_stats, M, d, xlo_layer(l) ? xlo_ffn : nullptr, f4x); }
     { ProfScope p("gemm_ffn_up", s, true); xgemm(EPI_GELU_H16, L.w1, L.b1, g->h, f, 4 * l + 2); }
     { ProfScope p("gemm_ffn_down", s, true);
-      rgemm(g->h, L.w2, L.b2, f, 4 * l + 3, g->h4, g->h4s, c.prenorm ? nullptr : L.ln1g, c.prenorm ? nullptr : L.ln1b); }
+      rgemm(g->h, L.w2, L.b2, f, 4 * l + 3, g->h4.v, g->h4.s, c.prenorm ? nullptr : L.ln1g, c.prenorm ? nullptr : L.ln1b); }
     if (!c.prenorm) { ProfScope p("layernorm", s, true);
       const bool last = l + 1 == c.depth;                  // the last one feeds the head: plain hi + lo rows
       layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, last ? g->x_lo : xlo_qkv, last ? Fp4Rows{} : f4x); }
   }
   if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo); }   // norm_after_transformer
   gemm_rc |= head_gemms(g, logits, M, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  if (int rc = launched()) return rc;
   if (attn_rc) return fail(-3, "attention maps: head dim %d / %d tokens not supported", d / c.heads, N);
   if (gemm_rc) return fail(-3, "a trunk GEMM of this forward (%d sequences x %d tokens, hidden %d, mlp %d; precision %d%s) is outside the half-tile "
                                "kernel's shapes: its correction mini-tiles cannot run", nb, N, d, f, c.precision, wm ? ", weight-correction mini-tiles" : "");
@@ -302,8 +250,8 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
   auto f4_for = [&](bool feeds_ffn = false) {   // what the producer of a LayerNorm operand also writes
     Fp4Rows f;
     if (wmode) {
-      f.x4 = g->x4; f.x4s = g->x4s; f.nseq = B; f.seq_rows = N;
-      if (alo_on(feeds_ffn ? 2 : 0)) { f.xl4 = g->xl4; f.xl4s = g->xl4s; }   // (the lo halves' e2m1 copy: only the LayerNorm in front of a GEMM that carries the set)
+      f.x4 = g->x4.v; f.x4s = g->x4.s; f.nseq = B; f.seq_rows = N;
+      if (alo_on(feeds_ffn ? 2 : 0)) { f.xl4 = g->xl4.v; f.xl4s = g->xl4.s; }   // (the lo halves' e2m1 copy: only the LayerNorm in front of a GEMM that carries the set)
     }
     return f;
   };
@@ -342,13 +290,13 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     const mb_gen::Layer& L = g->layers[l];
     const int xlo_mode = wmode ? (alo_on(2) ? 2 : 1) : 0;
     { ProfScope p("gemm_qkv", s, true);
-      GemmArgs ga = pgemm(EPI_H16, g->x_h16, L.wqkv, L.bqkv, g->qkv, nullptr, 3 * d, d, 4 * l, wmode ? (alo_on(0) ? 2 : 1) : 0, g->x4, g->x4s, g->xl4, g->xl4s);
+      GemmArgs ga = pgemm(EPI_H16, g->x_h16, L.wqkv, L.bqkv, g->qkv, nullptr, 3 * d, d, 4 * l, wmode ? (alo_on(0) ? 2 : 1) : 0, g->x4.v, g->x4.s, g->xl4.v, g->xl4.s);
       rc |= gemm_tn(s, EPI_H16, ga, 257); }
     const bool lo_o = alo_on(1), lo_h = alo_on(3);      // the producers also write the lo halves' e2m1 copies for a consumer that carries the set
-    { ProfScope p("attention", s, true); rc |= attention_pair(s, g->qkv, g->att, B, N, d, c.heads, wmode ? g->att4 : nullptr, wmode ? g->att4s : nullptr,
-                                                              lo_o ? g->attl4 : nullptr, lo_o ? g->attl4s : nullptr); }
+    { ProfScope p("attention", s, true); rc |= attention_pair(s, g->qkv, g->att, B, N, d, c.heads, wmode ? g->att4.v : nullptr, wmode ? g->att4.s : nullptr,
+                                                              lo_o ? g->attl4.v : nullptr, lo_o ? g->attl4.s : nullptr); }
     { ProfScope p("gemm_attn_out", s, true);
-      GemmArgs ga = pgemm(EPI_RES_F32, g->att, L.wo, L.bo, nullptr, g->y_f32, d, d, 4 * l + 1, wmode ? (alo_on(1) ? 2 : 1) : 0, g->att4, g->att4s, g->attl4, g->attl4s);
+      GemmArgs ga = pgemm(EPI_RES_F32, g->att, L.wo, L.bo, nullptr, g->y_f32, d, d, 4 * l + 1, wmode ? (alo_on(1) ? 2 : 1) : 0, g->att4.v, g->att4.s, g->attl4.v, g->attl4.s);
       if (l > 0 && !c.prenorm) { ga.ln_stats = g->ln_stats; ga.ln_g = g->layers[l - 1].ln2g; ga.ln_b = g->layers[l - 1].ln2b; }
       rc |= gemm_tn(s, EPI_RES_F32, ga, 257); }
     // post-norm: LayerNorm 1 follows the attention block; pre-norm: LayerNorm 2 precedes the FFN (same place in the launch order, other parameters;
@@ -356,12 +304,12 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     { ProfScope p("layernorm", s, true);
       rc |= layernorm_pair(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, g->x_h16, c.prenorm ? nullptr : g->ln_stats, P, d, f4_for(true)); }
     { ProfScope p("gemm_ffn_up", s, true);
-      GemmArgs ga = pgemm(EPI_GELU_H16, g->x_h16, L.w1, L.b1, g->h, nullptr, f, d, 4 * l + 2, xlo_mode, g->x4, g->x4s, g->xl4, g->xl4s);
-      if (wmode) { ga.out4 = g->h4; ga.out4_scale = g->h4s; }
-      if (lo_h) { ga.out4l = g->hl4; ga.out4l_scale = g->hl4s; }
+      GemmArgs ga = pgemm(EPI_GELU_H16, g->x_h16, L.w1, L.b1, g->h, nullptr, f, d, 4 * l + 2, xlo_mode, g->x4.v, g->x4.s, g->xl4.v, g->xl4.s);
+      if (wmode) { ga.out4 = g->h4.v; ga.out4_scale = g->h4.s; }
+      if (lo_h) { ga.out4l = g->hl4.v; ga.out4l_scale = g->hl4.s; }
       rc |= gemm_tn(s, EPI_GELU_H16, ga, 257); }
     { ProfScope p("gemm_ffn_down", s, true);
-      GemmArgs ga = pgemm(EPI_RES_F32, g->h, L.w2, L.b2, nullptr, g->y_f32, d, f, 4 * l + 3, wmode ? (alo_on(3) ? 2 : 1) : 0, g->h4, g->h4s, g->hl4, g->hl4s);
+      GemmArgs ga = pgemm(EPI_RES_F32, g->h, L.w2, L.b2, nullptr, g->y_f32, d, f, 4 * l + 3, wmode ? (alo_on(3) ? 2 : 1) : 0, g->h4.v, g->h4.s, g->hl4.v, g->hl4.s);
       if (!c.prenorm) { ga.ln_stats = g->ln_stats; ga.ln_g = L.ln1g; ga.ln_b = L.ln1b; }
       rc |= gemm_tn(s, EPI_RES_F32, ga, 257); }
     { ProfScope p("layernorm", s, true);
@@ -373,8 +321,7 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
       else rc |= layernorm_pair(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, g->x_h16, g->ln_stats, P, d, f4_for()); }
   }
   rc |= head_gemms(g, logits, M, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+  if (int lrc = launched()) return lrc;
   if (rc) return fail(-3, "differential CFG forward: a kernel refused the shape (%d pairs x %d tokens, hidden %d, mlp %d)", B, N, d, f);
   return 0;
 }
@@ -433,9 +380,8 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
 extern "C" {
 
 int mb_abi_version(void) { return MB_ABI_VERSION; }
-const char* mb_last_error(void) { return g_err.c_str(); }
+const char* mb_last_error(void) { return mb::g_err.c_str(); }
 
-int mb_set_cu_count(int n) { mb::set_cu_count(n); return 0; }
 int mb_prof_enable(int on) {
   if (!on) g_prof.drain();
   g_prof.on = on != 0;
@@ -453,131 +399,6 @@ int mb_prof_read(char* buf, int buflen) {
   if ((int)out.size() + 1 > buflen) return fail(-3, "mb_prof_read: buffer too small (%zu needed)", out.size() + 1);
   memcpy(buf, out.c_str(), out.size() + 1);
   return (int)out.size();
-}
-
-int mb_gemm_ex(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16,
-               int M, int N, int K, const float* ln_stats, const float* ln_g, const float* ln_b, int period, int variant, mb_stream stream) {
-  if (!A || !W || !bias || epi < 0 || epi > 4) return fail(-1, "mb_gemm_ex: bad arguments");
-  if (K % 64) return fail(-1, "mb_gemm_ex: K must be a multiple of 64");
-  if (ln_stats && (!ln_g || !ln_b || epi != mb::EPI_RES_F32)) return fail(-1, "mb_gemm_ex: LayerNorm residual needs gamma, beta and the fp32+residual epilogue");
-  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, K, period, nullptr, ln_stats, ln_g, ln_b};
-  ProfScope p("gemm_diag", (hipStream_t)stream);
-  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, variant)) return fail(-3, "GEMM shape M=%d N=%d K=%d is outside the kernels' shapes", a.M, a.N, a.K);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_gemm_mini(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16, void* out4,
-                 void* out4_scale, int rows, int pair, int N, int K, int nlo, const void* const* lo /* nlo x {A4, a_scale, W4, w_scale} */, mb_stream stream) {
-  return mb_gemm_mini_seq(epi, A, W, bias, residual, out_f32, out_h16, out4, out4_scale, nullptr, nullptr, rows, pair, 0, N, K, nlo, lo, stream);
-}
-int mb_gemm_mini_seq(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16, void* out4,
-                     void* out4_scale, void* out4l, void* out4l_scale, int rows, int pair, int seq_rows, int N, int K, int nlo, const void* const* lo, mb_stream stream) {
-  if ((out4l || out4l_scale) && (!out4l || !out4l_scale || !out4 || !out4_scale)) return fail(-1, "mb_gemm_mini_seq: the lo copy (out4l / out4l_scale) rides with the value copy (out4 / out4_scale)");
-  if (!A || !W || !bias || epi < 0 || epi > 2 || rows <= 0 || K <= 0 || K % 64 || nlo < 0 || nlo > 2 || (nlo && !lo)) return fail(-1, "mb_gemm_mini: bad arguments");
-  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, pair ? 2 * rows : rows, N, K, 0};
-  if (pair) a.pair_rows = rows;
-  a.seq_rows = seq_rows;
-  a.nlo = nlo;
-  for (int i = 0; i < nlo; ++i) a.lo[i] = {(const uint8_t*)lo[4 * i], (const uint8_t*)lo[4 * i + 1], (const uint8_t*)lo[4 * i + 2], (const uint8_t*)lo[4 * i + 3]};
-  a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale;
-  a.out4l = (uint8_t*)out4l; a.out4l_scale = (uint8_t*)out4l_scale;
-  if ((!seq_rows && a.M % 257) || !mb::gemm_ht_supported((mb::GemmEpi)epi, a)) return fail(-3, "mb_gemm_mini: shape not supported by the sequence-aligned tiles");
-  ProfScope p("gemm_diag", (hipStream_t)stream);
-  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, 257)) return fail(-3, "mb_gemm_mini: shape refused");
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, void* out_h16, void* out4, void* out4_scale,
-                       int rows, int N, int kw, const void* const* lo /* {A4, a_scale, W4, w_scale} */, mb_stream stream) {
-  if (!A_hi || !A_lo || !W || !bias || !out_h16 || !lo || epi < 0 || epi > 1 || rows <= 0 || rows % 257 || kw <= 0 || kw % 128)
-    return fail(-1, "mb_gemm_mini_split: bad arguments");
-  mb::GemmArgs a{(const h16*)A_hi, (const h16*)W, bias, nullptr, nullptr, (h16*)out_h16, rows, N, 2 * kw, 0};
-  a.A2 = (const h16*)A_lo; a.kw = kw;
-  a.nlo = 1;
-  a.lo[0] = {(const uint8_t*)lo[0], (const uint8_t*)lo[1], (const uint8_t*)lo[2], (const uint8_t*)lo[3]};
-  a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale;
-  if (!mb::gemm_ht_supported((mb::GemmEpi)epi, a)) return fail(-3, "mb_gemm_mini_split: shape not supported by the sequence-aligned tiles");
-  ProfScope p("gemm_diag", (hipStream_t)stream);
-  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, 257)) return fail(-3, "mb_gemm_mini_split: shape refused");
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, int heads, mb_stream stream) {
-  if (!qkv || !out_h16 || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair: bad arguments");
-  ProfScope p("attention", (hipStream_t)stream);
-  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, nullptr, nullptr))
-    return fail(-3, "mb_attention_pair: head width %d (N = %d tokens) is outside the attention kernels", d / heads, N);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_scale, void* out4l, void* out4l_scale, int pairs, int N, int d, int heads, mb_stream stream) {
-  if (!qkv || !out_h16 || !out4 || !out4_scale || (!out4l) != (!out4l_scale) || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair_f4: bad arguments");
-  ProfScope p("attention", (hipStream_t)stream);
-  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale, (uint8_t*)out4l, (uint8_t*)out4l_scale))
-    return fail(-3, "mb_attention_pair_f4: head width %d / N = %d tokens: no e2m1 copy for this shape", d / heads, N);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_gemm_act_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, const float* residual, float* out_f32,
-                      void* out_h16, int M, int N, int kw, int variant, mb_stream stream) {
-  if (!A_hi || !A_lo || !W || !bias || epi < 0 || epi > 3 || kw <= 0 || kw % 64) return fail(-1, "mb_gemm_act_split: bad arguments");
-  mb::GemmArgs a{(const h16*)A_hi, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, 2 * kw, 0};
-  a.A2 = (const h16*)A_lo; a.kw = kw;
-  ProfScope p("gemm_diag", (hipStream_t)stream);
-  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, variant)) return fail(-3, "GEMM shape M=%d N=%d K=%d is outside the kernels' shapes", a.M, a.N, a.K);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_w4_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
-  if (!W || !dst4 || !scale_out || N <= 0 || K <= 0 || N % 64 || K % 128) return fail(-1, "mb_w4_from_f32: bad arguments");
-  mb::w4_from_f32((hipStream_t)stream, W, (uint8_t*)dst4, N, K, (uint8_t*)scale_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_w4lo_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
-  if (!W || !dst4 || !scale_out || N <= 0 || K <= 0 || N % 64 || K % 128) return fail(-1, "mb_w4lo_from_f32: bad arguments");
-  mb::w4lo_from_f32((hipStream_t)stream, W, (uint8_t*)dst4, N, K, (uint8_t*)scale_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
-                    void* xl4_scale, int M, int d, mb_stream stream) {
-  if (!y || !gamma || !beta || (!x4 && !xl4) || (x4 && !x4_scale) || (xl4 && !xl4_scale) || M <= 0 || M % 257 || (d != 768 && d != 1024))
-    return fail(-1, "mb_layernorm_f4: bad arguments (d must be 768 or 1024, M a multiple of 257)");
-  mb::Fp4Rows f4{(uint8_t*)x4, (uint8_t*)x4_scale, (uint8_t*)xl4, (uint8_t*)xl4_scale, M / 257};
-  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_layernorm(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x_lo, float* stats, int M,
-                 int d, mb_stream stream) {
-  if (!y || !gamma || !beta || M <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_layernorm: bad arguments");
-  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, stats, M, d, (h16*)x_lo);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
-// Diagnostic entry: one GEMM of the trunk family on caller buffers (tests and tools/gemm_bench.py).
-int mb_gemm(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16,
-            int M, int N, int K, int period, int variant, mb_stream stream) {
-  if (!A || !W || !bias || epi < 0 || epi > 4) return fail(-1, "mb_gemm: bad arguments");
-  if (K % 64) return fail(-1, "mb_gemm: K must be a multiple of 64");
-  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, residual, out_f32, (h16*)out_h16, M, N, K, period};
-  ProfScope p("gemm_diag", (hipStream_t)stream);
-  if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, variant)) return fail(-3, "GEMM shape M=%d N=%d K=%d is outside the kernels' shapes", a.M, a.N, a.K);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
 }
 
 int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
@@ -636,38 +457,22 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   g->pair_ok = c.precision >= 1 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && g->chunk_seqs >= 2 &&
                (c.precision == 1 || g->mini_ok);
   if (g->mini_ok) {
-    // e2m1 operands: row stride of the fp16 sibling (2 * width bytes, first width / 2 used); scale bytes in lane order: [width / 64][sequences][256]
-    const size_t ns = (size_t)g->chunk_seqs * c.seq;
-    rc |= galloc(g, &g->x4, M * 2 * d); rc |= galloc(g, &g->x4s, (d / 64) * ns + 256);
-    rc |= galloc(g, &g->att4, M * 2 * d); rc |= galloc(g, &g->att4s, (d / 64) * ns + 256);
-    rc |= galloc(g, &g->h4, M * 2 * f); rc |= galloc(g, &g->h4s, (f / 64) * ns + 256);
-    if (g->alo_mask_built & 5) { rc |= galloc(g, &g->xl4, M * 2 * d); rc |= galloc(g, &g->xl4s, (d / 64) * ns + 256); }
-    if (g->alo_mask_built & 2) {
-      rc |= galloc(g, &g->attl4, M * 2 * d); rc |= galloc(g, &g->attl4s, (d / 64) * ns + 256);
-      if (!rc) { (void)hipMemset(g->attl4, 0, M * 2 * d); (void)hipMemset(g->attl4s, 0, (d / 64) * ns + 256); }
-    }
-    if (g->alo_mask_built & 8) {
-      rc |= galloc(g, &g->hl4, M * 2 * f); rc |= galloc(g, &g->hl4s, (f / 64) * ns + 256);
-      if (!rc) { (void)hipMemset(g->hl4, 0, M * 2 * f); (void)hipMemset(g->hl4s, 0, (f / 64) * ns + 256); }
-    }
-    if (!rc) {
-      (void)hipMemset(g->x4, 0, M * 2 * d); (void)hipMemset(g->x4s, 0, (d / 64) * ns + 256);
-      (void)hipMemset(g->att4, 0, M * 2 * d); (void)hipMemset(g->att4s, 0, (d / 64) * ns + 256);
-      (void)hipMemset(g->h4, 0, M * 2 * f); (void)hipMemset(g->h4s, 0, (f / 64) * ns + 256);
-      if (g->xl4) { (void)hipMemset(g->xl4, 0, M * 2 * d); (void)hipMemset(g->xl4s, 0, (d / 64) * ns + 256); }
-    }
+    const size_t ntok = (size_t)g->chunk_seqs * c.seq;
+    rc |= galloc_f4(g, &g->x4, M, d, ntok);
+    rc |= galloc_f4(g, &g->att4, M, d, ntok);
+    rc |= galloc_f4(g, &g->h4, M, f, ntok);
+    if (g->alo_mask_built & 5) rc |= galloc_f4(g, &g->xl4, M, d, ntok);
+    if (g->alo_mask_built & 2) rc |= galloc_f4(g, &g->attl4, M, d, ntok);
+    if (g->alo_mask_built & 8) rc |= galloc_f4(g, &g->hl4, M, f, ntok);
     g->w4lo.assign((size_t)4 * c.depth, nullptr); g->w4los.assign((size_t)4 * c.depth, nullptr);
     g->w4.assign((size_t)4 * c.depth, nullptr); g->w4s.assign((size_t)4 * c.depth, nullptr);
-    for (int l = 0; l < c.depth; ++l) {
-      // (mini-tile-packed: half a byte per weight; one scale byte per (weight row, 128 columns))
-      rc |= galloc(g, &g->w4lo[4 * l], 3 * d * d / 2); rc |= galloc(g, &g->w4los[4 * l], 3 * d * d / 128);
-      rc |= galloc(g, &g->w4lo[4 * l + 1], d * d / 2); rc |= galloc(g, &g->w4los[4 * l + 1], d * d / 128);
-      rc |= galloc(g, &g->w4lo[4 * l + 2], f * d / 2); rc |= galloc(g, &g->w4los[4 * l + 2], f * d / 128);
-      rc |= galloc(g, &g->w4lo[4 * l + 3], d * f / 2); rc |= galloc(g, &g->w4los[4 * l + 3], d * f / 128);
+    // mini-tile-packed e2m1 of the four weights of a layer: half a byte per weight, one scale byte per (weight row, 128 columns)
+    const size_t wn[4] = {3 * d * d, d * d, f * d, d * f};
+    for (int i = 0; i < 4 * c.depth; ++i) {
+      const size_t n = wn[i & 3];
+      rc |= galloc(g, &g->w4lo[i], n / 2); rc |= galloc(g, &g->w4los[i], n / 128);
       // e2m1 of the fp16 weight VALUES for the GEMMs that carry an activation-lo set (precision >= 3)
-      const size_t wn[4] = {3 * d * d, d * d, f * d, d * f};
-      for (int q = 0; q < 4; ++q)
-        if ((g->alo_mask_built >> q) & 1) { rc |= galloc(g, &g->w4[4 * l + q], wn[q] / 2); rc |= galloc(g, &g->w4s[4 * l + q], wn[q] / 128); }
+      if ((g->alo_mask_built >> (i & 3)) & 1) { rc |= galloc(g, &g->w4[i], n / 2); rc |= galloc(g, &g->w4s[i], n / 128); }
     }
   }
   const size_t P = (size_t)c.seq * c.splits, B = max_seqs;
@@ -817,134 +622,7 @@ int mb_sample_step(const float* logits_c, const float* logits_u, float scale, fl
   mb::StepArgs a{logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, tokens_out, pred_out, B, n * m, C};
   ProfScope p("sample_step", (hipStream_t)stream);
   if (mb::sample_step((hipStream_t)stream, a, tokens_in)) return fail(-1, "mb_sample_step: C=%d or n*m=%d too large", C, n * m);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// decoder handle (kernels in decoder.hip)
-// ================================================================================================
-extern "C" {
-
-int mb_dec_create(const mb_dec_cfg* cfg, int max_batch, mb_dec** out) {
-  if (!cfg || !out || max_batch <= 0) return fail(-1, "mb_dec_create: bad arguments");
-  std::string err;
-  mb_dec* d = mb::dec_create(*cfg, max_batch, err);
-  if (!d) return fail(-1, "mb_dec_create: %s", err.c_str());
-  *out = d;
-  return 0;
-}
-void mb_dec_destroy(mb_dec* d) { mb::dec_destroy(d); }
-int mb_dec_load(mb_dec* d, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
-  if (!d || !name || !data) return fail(-1, "mb_dec_load: bad arguments");
-  std::string err;
-  int rc = mb::dec_load(d, name, data, shape, ndim, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_dec_load: %s", err.c_str());
-  return 0;
-}
-int mb_dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
-  if (!d || !tokens) return fail(-1, "mb_dec_decode: null argument");
-  std::string err;
-  ProfScope p("decode", (hipStream_t)stream);
-  int rc = mb::dec_decode(d, tokens, img_nchw, img_nhwc_u8, B, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_dec_decode: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
-int mb_dec_create_vq(const mb_dec_cfg* cfg, int codebook_size, int l2_normalize, int max_batch, mb_dec** out) {
-  if (!cfg || !out || max_batch <= 0) return fail(-1, "mb_dec_create_vq: bad arguments");
-  if (codebook_size < 2 || codebook_size > 65536) return fail(-1, "mb_dec_create_vq: codebook_size %d outside [2, 65536]", codebook_size);
-  std::string err;
-  mb_dec* d = mb::dec_create(*cfg, max_batch, err, codebook_size, l2_normalize);
-  if (!d) return fail(-1, "mb_dec_create_vq: %s", err.c_str());
-  *out = d;
-  return 0;
-}
-int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
-  if (!d || !z_nchw) return fail(-1, "mb_dec_decode_latent: null argument");
-  std::string err;
-  ProfScope p("decode", (hipStream_t)stream);
-  int rc = mb::dec_decode_latent(d, z_nchw, img_nchw, img_nhwc_u8, B, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_dec_decode_latent: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_enc_encode_vq(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, mb_stream stream) {
-  if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode_vq: null argument");
-  std::string err;
-  ProfScope p("encode", (hipStream_t)stream);
-  int rc = mb::enc_encode_vq(d, img_nchw, indices, zq, zraw, row_dist, B, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_enc_encode_vq: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream) {
-  if (!z || !codebook || !idx) return fail(-1, "mb_vq_argmin: null argument");
-  std::string err;
-  int rc = mb::vq_argmin(z, codebook, N, C, K, l2, splits, idx, dist, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_vq_argmin: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-
-// ---- single tokenizer layers on caller buffers (maskbit_hip_diag.h) ----
-int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
-                  void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
-                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
-                  mb_stream stream) {
-  mb::ConvDiag q{in_h16, w_oihw, bias, gn_gamma, gn_beta, residual_h16, out_h16, img_nchw, img_nhwc_u8, out_gamma, out_beta, out_scale_shift,
-                 out_gn_part, part_tiles, saturated, B, H, W, Cin, Cout, ks, up, final_layer};
-  std::string err;
-  int rc = mb::diag_conv(q, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_conv_layer: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream) {
-  if (!x_h16 || !gamma || !beta || !scale_shift) return fail(-1, "mb_groupnorm_stats: null argument");
-  std::string err;
-  int rc = mb::diag_groupnorm(x_h16, gamma, beta, scale_shift, B, HW, C, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_groupnorm_stats: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-static int pool_entry(const char* what, bool avg, const void* x, void* y, int B, int H, int W, int C, mb_stream stream) {
-  if (!x || !y) return fail(-1, "%s: null argument", what);
-  std::string err;
-  int rc = mb::diag_pool(avg, x, y, B, H, W, C, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "%s: %s", what, err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
-}
-int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", true, x_h16, y_h16, B, H, W, C, stream); }
-int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", false, x_h16, y_h16, B, H, W, C, stream); }
-
-int mb_dec_saturation_count(mb_dec* d, unsigned* count, int reset, mb_stream stream) {
-  if (!d || !count) return fail(-1, "mb_dec_saturation_count: null argument");
-  if (mb::dec_saturation_count(d, count, reset != 0, (hipStream_t)stream)) return fail(-10, "mb_dec_saturation_count: copy failed");
-  return 0;
-}
-
-int mb_enc_encode(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, int B, mb_stream stream) {
-  if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode: null argument");
-  std::string err;
-  ProfScope p("encode", (hipStream_t)stream);
-  int rc = mb::enc_encode(d, img_nchw, indices, zq, zraw, B, (hipStream_t)stream, err);
-  if (rc) return fail(rc, "mb_enc_encode: %s", err.c_str());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 // ================================================================================================
@@ -1005,8 +683,7 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
   }
   g->cfg_labels_ready = nullptr;
   if (s1 < plan->num_steps) {                          // more chunks follow: keep the last predictions only if they are the engine's own buffer
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+    if (int rc = launched()) return rc;
     g->loop_next = s1;
     return 0;
   }
@@ -1017,9 +694,7 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
     int rc = mb_dec_decode(d, codes, img_nchw, img_nhwc_u8, B, stream);
     if (rc) return rc;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 }  // extern "C"

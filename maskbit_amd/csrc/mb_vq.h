@@ -1,11 +1,9 @@
 // Lookup (VQ) quantizer kernels (vq.hip): nearest-codeword search fused with its argmin, code -> latent gather and the latent pack of
 // ConvVQModel with quantizer_type = "lookup" (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119).  Used by decoder.hip and by the
-// diagnostic entry mb_vq_argmin (engine.hip).
+// diagnostic entry mb_vq_argmin (diag.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <string>
 
 #include "mb_common.h"
 
@@ -43,7 +41,8 @@ void vq_gather(const VqCodebook& q, const int64_t* codes, size_t npix, h16* z, i
 // fp32 NCHW latent [B][K][HW] -> fp16 NHWC [B*HW][cin_pad], saturating stores counted in *sat
 void vq_pack_latent(const float* z, int B, int K, int HW, h16* out, int cin_pad, unsigned* sat, hipStream_t s);
 
-// Diagnostic (mb_vq_argmin): the whole search on caller buffers, z fp32 [N][K], w fp32 [C][K] codebook; temporaries are stream-ordered
-int vq_argmin(const float* z, const float* w, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, hipStream_t s, std::string& err);
+// Diagnostic (mb_vq_argmin): the whole search on caller buffers, z fp32 [N][K], w fp32 [C][K] codebook; temporaries are stream-ordered.
+// 0, or the code of a fail() in that entry's name
+int vq_argmin(const float* z, const float* w, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, hipStream_t s);
 
 }  // namespace mb

@@ -11,8 +11,8 @@
 // batch composition.  The finalize pass recomputes the chosen entry's squared distance exactly (sequential fp32) and writes zq.
 #include <algorithm>
 #include <cmath>
-#include <string>
 
+#include "mb_abi.h"
 #include "mb_vq.h"
 
 namespace mb {
@@ -249,8 +249,8 @@ void vq_pack_latent(const float* z, int B, int K, int HW, h16* out, int cin_pad,
   hipLaunchKernelGGL(vq_pack_kernel, dim3((unsigned)std::min<size_t>(4096, (n + 255) / 256)), dim3(256), 0, s, z, B, K, HW, cin_pad, out, sat);
 }
 
-int vq_argmin(const float* z, const float* w, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, hipStream_t s, std::string& err) {
-  if (N < 1 || C < 2 || C > 65536 || K < 1 || K > 256) { err = "N >= 1, C in [2, 65536], K in [1, 256] required"; return -1; }
+int vq_argmin(const float* z, const float* w, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, hipStream_t s) {
+  if (N < 1 || C < 2 || C > 65536 || K < 1 || K > 256) return fail(-1, "mb_vq_argmin: N >= 1, C in [2, 65536], K in [1, 256] required");
   VqCodebook q;
   q.C = C; q.K = K; q.Kp = vq_kp(K); q.Cpad = vq_cpad(C); q.l2 = l2 ? 1 : 0;
   const int Npad = vq_npad(N);
@@ -267,12 +267,10 @@ int vq_argmin(const float* z, const float* w, int N, int C, int K, int l2, int s
     vq_prep_codebook(q, w, s);
     vq_prep_rows(q, nullptr, 0, z, N, N, zT, nullptr, s);
     vq_search(q, zT, N, N, splits, ps, pi, idx, nullptr, dist, s);
-  } else {
-    err = "device allocation failed";
   }
   for (void* p : {(void*)q.cb, (void*)q.cbT, (void*)q.cbn, (void*)zT, (void*)ps, (void*)pi})
     if (p) (void)hipFreeAsync(p, s);
-  return ok ? 0 : -10;
+  return ok ? 0 : fail(-10, "mb_vq_argmin: device allocation failed");
 }
 
 }  // namespace mb
