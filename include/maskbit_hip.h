@@ -14,6 +14,7 @@
 #ifndef MASKBIT_HIP_H
 #define MASKBIT_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -167,6 +168,25 @@ int mb_enc_encode_vq(mb_dec* d, const float* img_nchw, int64_t* indices, float* 
 int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B,
               const float* exp_noise, const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out,
               float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
+
+/* ---- tokenizer evaluation: TokenizerEvaluator.update, evaluator/evaluator.py:262-375 (scripts/eval_tokenizer.py:137-149) ---------------- *
+ * Stateless: the caller owns every buffer (and zeroes its running state once); nothing is allocated, nothing synchronises.
+ * Bytes of workspace mb_eval_images needs for this shape (one slot of three doubles per 32 x 32 tile of every image plane); 0 for a shape it
+ * does not take. */
+size_t mb_eval_workspace_bytes(int B, int C, int H, int W);
+/* MAE, MSE, PSNR and SSIM of fake against real (fp32 [B,C,H,W], H, W >= 6) from one read of both: replaces the difference / power / mean chains of
+ * evaluator.py:282-294 and the clone / reflect-pad / product / cat / depthwise 11 x 11 Gaussian conv2d / SSIM formula chain of evaluator.py:296-334
+ * (window gaussian(11, 1.5) of evaluator.py:44-56, k1 / k2 = 0.01 / 0.03, data range 1).  metrics: bit 0 = absolute error, bit 1 = squared error
+ * and PSNR, bit 2 = SSIM (needs C == 3, evaluator.py:298).  clamp01 != 0 clamps both inputs to [0, 1] on the load (eval_tokenizer.py:146-147).
+ * per_image double [B][3] receives sum |d|, sum d^2, sum SSIM over each image's C*H*W values (0 for a metric not asked for); sums double [4] +=
+ * the batch's per-image MAE, MSE, PSNR = 10 log10(1 / (mse + 1e-10)) and mean-SSIM terms, added in image order (what evaluator.py:284,288,292,334
+ * add to the four running sums), deterministic: one update of a batch and consecutive updates of its parts leave identical bits. */
+int mb_eval_images(const float* real, const float* fake, int B, int C, int H, int W, unsigned metrics, int clamp01, void* workspace,
+                   double* per_image, double* sums, mb_stream stream);
+/* hist[i] += number of indices equal to i, over n int64 indices of any shape: replaces both torch.unique calls, the .tolist() into a Python set
+ * (a host synchronisation per batch) and the index_add_ of evaluator.py:370-375.  Indices outside [0, K) are not counted; *out_of_range += their
+ * number. */
+int mb_eval_codebook(const int64_t* indices, int64_t n, int K, int64_t* hist, unsigned* out_of_range, mb_stream stream);
 
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */

@@ -1,0 +1,158 @@
+"""Tokenizer evaluation on the device: the reference's ``TokenizerEvaluator`` (evaluator/evaluator.py:145-466) behind the gfx950 kernels of
+``csrc/evaluator.hip``.
+
+Same constructor keywords, ``reset_metrics()``, ``update(real_images, fake_images, codebook_indices=None)`` and ``result()``.  In scope are
+the six closed-form metrics -- MAE, MSE, PSNR, SSIM (11 x 11 Gaussian window, sigma 1.5, reflect padding, k1 / k2 = 0.01 / 0.03, data range 1),
+CodebookUsage and CodebookEntropy.  ``update()`` is two kernels for the images (``mb_eval_images``: one read of both images for all four image
+metrics, then a small deterministic finalize) and one for the indices (``mb_eval_codebook``: a histogram, in place of two ``torch.unique``
+calls and a ``.tolist()`` into a Python set); it enqueues on the current stream and never synchronises.  The running state -- four float64
+sums, an int64 histogram, an out-of-range counter -- stays on the device; ``result()`` makes one device-to-host copy.
+
+The network metrics (rFID, Inception score, LPIPS) are not built: they raise at construction.  There is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Mapping, Optional, Text
+
+import torch
+
+from . import _lib
+
+_ABS, _SQ, _SSIM = 1, 2, 4          # metrics bits of mb_eval_images
+
+
+class TokenizerEvaluator:
+    def __init__(
+        self,
+        device,
+        enable_rfid: bool = False,
+        enable_inception_score: bool = False,
+        enable_psnr_score: bool = False,
+        enable_ssim_score: bool = False,
+        enable_lpips_score: bool = False,
+        enable_mse_error: bool = False,
+        enable_mae_error: bool = False,
+        enable_codebook_usage_measure: bool = False,
+        enable_codebook_entropy_measure: bool = False,
+        num_codebook_entries: int = 1024
+    ):
+        for flag, name in ((enable_rfid, "enable_rfid"), (enable_inception_score, "enable_inception_score"), (enable_lpips_score, "enable_lpips_score")):
+            if flag:
+                raise NotImplementedError(
+                    f"{name}: rFID, Inception score and LPIPS need the Inception / LPIPS networks and their weights, which are out of scope here "
+                    "(SURVEY.md section 2). Run them with the reference's own evaluator beside this one (evaluator.TokenizerEvaluator with only "
+                    "those flags set; both take the same update() arguments).")
+        self._device = torch.device(device)
+        if self._device.type != "cuda":
+            raise RuntimeError(f"TokenizerEvaluator runs only on an AMD GPU through libmaskbit_hip.so (device is {self._device}); "
+                               "maskbit_amd has no CPU path.")
+        self._enable_psnr_score = bool(enable_psnr_score)
+        self._enable_ssim_score = bool(enable_ssim_score)
+        self._enable_mse_error = bool(enable_mse_error)
+        self._enable_mae_error = bool(enable_mae_error)
+        self._enable_codebook_usage_measure = bool(enable_codebook_usage_measure)
+        self._enable_codebook_entropy_measure = bool(enable_codebook_entropy_measure)
+        self._num_codebook_entries = int(num_codebook_entries)
+        if self._num_codebook_entries < 1:
+            raise ValueError(f"num_codebook_entries={num_codebook_entries}: at least one entry")
+        self._metrics = ((_ABS if self._enable_mae_error else 0) | (_SQ if self._enable_mse_error or self._enable_psnr_score else 0)
+                         | (_SSIM if self._enable_ssim_score else 0))
+        self._codebook = self._enable_codebook_usage_measure or self._enable_codebook_entropy_measure
+        self._workspace: Optional[torch.Tensor] = None
+        self._sums: Optional[torch.Tensor] = None
+        self._hist: Optional[torch.Tensor] = None
+        self._out_of_range: Optional[torch.Tensor] = None
+        self.last_per_image: Optional[torch.Tensor] = None
+        if self._device.index is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        self.reset_metrics()
+
+    def reset_metrics(self):
+        """Resets all metrics (the device state is zeroed by enqueued fills; no synchronisation)."""
+        self._num_examples = 0
+        self._num_updates = 0
+        if self._sums is None:
+            _lib.load()
+            self._sums = torch.zeros(4, dtype=torch.float64, device=self._device)                 # MAE, MSE, PSNR, SSIM sums of per-image terms
+            self._hist = torch.zeros(self._num_codebook_entries if self._codebook else 1, dtype=torch.int64, device=self._device)
+            self._out_of_range = torch.zeros(1, dtype=torch.int32, device=self._device)
+        else:
+            self._sums.zero_()
+            self._hist.zero_()
+            self._out_of_range.zero_()
+        self.last_per_image = None
+
+    def update(self, real_images: torch.Tensor, fake_images: torch.Tensor, codebook_indices: Optional[torch.Tensor] = None, clamp: bool = False):
+        """Adds a batch.  ``real_images`` / ``fake_images``: [B, C, H, W] of any float dtype (cast to contiguous fp32 only when needed), equal
+        element counts (``real`` is viewed as ``fake``, evaluator.py:283), H, W >= 6, C == 3 when SSIM is enabled.  ``clamp=True`` clamps both
+        to [0, 1] inside the kernel (eval_tokenizer.py:146-147).  ``codebook_indices``: integer tensor of any shape, required when a codebook
+        metric is enabled.  Violations raise ``ValueError`` before any device work.  After the call ``last_per_image`` is the batch's float64
+        [B, 3] device tensor of sum |d|, sum d^2 and sum SSIM per image (zeros for a metric that is not enabled)."""
+        if real_images.dim() != 4 or fake_images.dim() != 4:
+            raise ValueError(f"update expects [B, C, H, W] images, got {tuple(real_images.shape)} and {tuple(fake_images.shape)}")
+        if real_images.numel() != fake_images.numel():
+            raise ValueError(f"real and fake images differ in size: {tuple(real_images.shape)} vs {tuple(fake_images.shape)}")
+        B, C, H, W = (int(v) for v in fake_images.shape)
+        if B < 1 or C < 1:
+            raise ValueError(f"empty batch: {tuple(fake_images.shape)}")
+        if H < 6 or W < 6:
+            raise ValueError(f"images of {H} x {W}: the 11 x 11 window's reflect padding needs H, W >= 6")
+        if self._enable_ssim_score and C != 3:
+            raise ValueError(f"SSIM takes 3 channels (evaluator.py:298), got {C}")
+        if self._codebook and codebook_indices is None:
+            raise ValueError("codebook_indices is required when a codebook metric is enabled")
+        if self._codebook and (codebook_indices.is_floating_point() or codebook_indices.is_complex()):
+            raise ValueError(f"codebook_indices must be an integer tensor, got {codebook_indices.dtype}")
+        lib = _lib.load()
+        need = int(lib.mb_eval_workspace_bytes(B, C, H, W)) if self._metrics else 0
+        if self._metrics and need == 0:
+            raise ValueError(f"batch of {tuple(fake_images.shape)} is outside what mb_eval_images takes (B, C <= 65535)")
+        self._num_examples += B
+        self._num_updates += 1
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream().cuda_stream
+            if self._metrics:
+                fake = fake_images.to(device=self._device, dtype=torch.float32).contiguous()
+                real = real_images.to(device=self._device, dtype=torch.float32).reshape(fake.shape).contiguous()
+                if self._workspace is None or self._workspace.numel() * 8 < need:
+                    self._workspace = torch.empty(need // 8, dtype=torch.float64, device=self._device)
+                per_image = torch.empty((B, 3), dtype=torch.float64, device=self._device)
+                _lib.check(lib.mb_eval_images(real.data_ptr(), fake.data_ptr(), B, C, H, W, self._metrics, 1 if clamp else 0,
+                                              self._workspace.data_ptr(), per_image.data_ptr(), self._sums.data_ptr(), stream), "mb_eval_images")
+                self.last_per_image = per_image
+            if self._codebook:
+                idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
+                _lib.check(lib.mb_eval_codebook(idx.data_ptr(), idx.numel(), self._num_codebook_entries, self._hist.data_ptr(),
+                                                self._out_of_range.data_ptr(), stream), "mb_eval_codebook")
+
+    def result(self) -> Mapping[Text, torch.Tensor]:
+        """The averages over all images given, keys and order of evaluator.py:385-466: Python floats, except ``CodebookEntropy``, a 0-d float64
+        tensor on the evaluator's device as in the reference.  One device-to-host copy.  ``IndexError`` if an index fell outside
+        [0, num_codebook_entries)."""
+        if self._num_examples < 1:
+            raise ValueError("No examples to evaluate.")
+        entropy = None
+        parts = [self._sums]
+        if self._codebook:
+            counts = self._hist.double()
+            probs = counts / counts.sum()
+            entropy = (-torch.log2(probs + 1e-8) * probs).sum()                                # evaluator.py:462-463
+            parts += [(self._hist != 0).sum().double().reshape(1), (self._out_of_range.long() & 0xFFFFFFFF).double()]
+        host = torch.cat(parts).cpu()                                                           # the one copy
+        if self._codebook and host[5] != 0:
+            raise IndexError(f"{int(host[5])} codebook indices outside [0, {self._num_codebook_entries})")
+        eval_score = {}
+        n = self._num_examples
+        if self._enable_mae_error:
+            eval_score["MAE"] = host[0].item() / n
+        if self._enable_mse_error:
+            eval_score["MSE"] = host[1].item() / n
+        if self._enable_psnr_score:
+            eval_score["PSNR"] = host[2].item() / n
+        if self._enable_ssim_score:
+            eval_score["SSIM"] = host[3].item() / n
+        if self._enable_codebook_usage_measure:
+            eval_score["CodebookUsage"] = float(int(host[4])) / self._num_codebook_entries
+        if self._enable_codebook_entropy_measure:
+            eval_score["CodebookEntropy"] = entropy
+        return eval_score

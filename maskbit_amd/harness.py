@@ -95,3 +95,20 @@ def to_evaluator_uint8(u8_nhwc: torch.Tensor) -> torch.Tensor:
     network, ``(generated_images * 255).to(torch.uint8)`` on the clamped float image (evaluator/evaluator.py:549-551): the same
     bytes without materialising the float image.  A view, no copy."""
     return u8_nhwc.permute(0, 3, 1, 2)
+
+
+@torch.no_grad()
+def eval_reconstruction(model: ConvVQModel, loader, evaluator):
+    """The reconstruction loop of the reference's tokenizer evaluation (scripts/eval_tokenizer.py:126-167, without the image dump): per batch
+    ``model(images)``, then ``evaluator.update(original, reconstruction, min_encoding_indices)`` on both images clamped to [0, 1] -- the clamp
+    runs inside the evaluator's kernel (``clamp=True``) instead of as two extra passes -- and ``evaluator.result()`` at the end.  ``loader``
+    yields dicts with an ``"image"`` tensor [B, 3, H, W] as the reference's data loader does; ``evaluator`` is a
+    ``maskbit_amd.TokenizerEvaluator``.  Nothing in the loop synchronises with the host."""
+    dev = model._require_cuda("eval_reconstruction")
+    model.eval()
+    evaluator.reset_metrics()
+    for batch in loader:
+        images = batch["image"].to(dev, memory_format=torch.contiguous_format, non_blocking=True)
+        reconstructed_images, model_dict = model(images)
+        evaluator.update(images, reconstructed_images, model_dict["min_encoding_indices"], clamp=True)
+    return evaluator.result()

@@ -269,3 +269,42 @@ def make_vq_codebook(codebook_size: int, token_size: int, seed: int, mean, std) 
     mean = torch.as_tensor(mean, dtype=torch.float32).reshape(1, -1)
     std = torch.as_tensor(std, dtype=torch.float32).reshape(1, -1)
     return torch.randn(codebook_size, token_size, generator=g) * std + mean
+
+
+EVAL_FAMILIES = ("noise", "sin", "flat", "bright")
+
+
+def make_eval_images(family: str, err_sigma: float, B: int, H: int, W: int, seed: int, C: int = 3) -> Tuple[Tensor, Tensor]:
+    """Seeded (real, fake) fp32 [B, C, H, W] image pairs for the evaluator's fixtures, fake = real + err_sigma * randn (not clamped).
+    Families: ``noise`` uniform [0, 1); ``sin`` smooth sinusoids around 0.5; ``flat`` a 0.8 field with 0.002 noise; ``bright`` uniform
+    [0.9, 1.0) -- the last two are where E[x^2] - E[x]^2 cancels and the fp32 rounding of the SSIM filter shows."""
+    g = torch.Generator().manual_seed(seed)
+    if family == "noise":
+        real = torch.rand(B, C, H, W, generator=g)
+    elif family == "sin":
+        f = torch.rand(B, C, 2, generator=g) * 6.0 + 0.5
+        ph = torch.rand(B, C, generator=g) * (2.0 * math.pi)
+        yy = torch.arange(H, dtype=torch.float64).view(1, 1, H, 1) / H
+        xx = torch.arange(W, dtype=torch.float64).view(1, 1, 1, W) / W
+        f, ph = f.double(), ph.double()
+        arg = 2.0 * math.pi * (f[..., 0].view(B, C, 1, 1) * yy + f[..., 1].view(B, C, 1, 1) * xx) + ph.view(B, C, 1, 1)
+        real = (0.5 + 0.4 * torch.sin(arg)).float()            # evaluated in fp64: the fp32 rounding hides the last-bit spread of libm's sin
+    elif family == "flat":
+        real = 0.8 + 0.002 * torch.randn(B, C, H, W, generator=g)
+    elif family == "bright":
+        real = 0.9 + 0.1 * torch.rand(B, C, H, W, generator=g)
+    else:
+        raise ValueError(f"unknown image family {family!r}")
+    fake = real + err_sigma * torch.randn(B, C, H, W, generator=g)
+    return real.contiguous(), fake.contiguous()
+
+
+def make_eval_indices(kind: str, K: int, shape, seed: int) -> Tensor:
+    """Seeded int64 codebook indices in [0, K): ``uniform`` over all entries, or ``skew`` (a cubed uniform draw over the first third of the
+    codebook: repeated entries, most of the codebook unused)."""
+    g = torch.Generator().manual_seed(seed)
+    if kind == "uniform":
+        return torch.randint(0, K, tuple(shape), generator=g)
+    if kind == "skew":
+        return (torch.rand(tuple(shape), generator=g).pow(3) * (K // 3)).long()
+    raise ValueError(f"unknown index kind {kind!r}")
