@@ -169,6 +169,48 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
               const float* exp_noise, const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out,
               float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
 
+/* ---- image editing: sampling from a partly known token map (inpainting, outpainting, regenerating a region under another label) ------------ *
+ * No counterpart in the reference, whose sample() always starts from the all-masked state (sampling.py:65-71).  Per sample b a run starts with
+ * num_regen[b] masked slots (the reference's num_maskable, per sample) and each step re-masks per sample: with nm_b = sample b's masked count on
+ * entry and mask_len = floor(mask_ratio * num_regen[b]) in fp32 (torch.floor(ratio * num_maskable) with a float32 ratio),
+ *   nm_b >= 2: k = min(max(mask_len, 1), nm_b - 1), threshold = the k-th smallest confidence of the sample, every slot at or below it is masked again
+ *              (always a masked slot's confidence: a known slot, at +inf, is never re-masked);
+ *   nm_b <= 1: nothing is re-masked, tokens_out = pred (the reference's clamp gives k = 0 there, whose sorted[-1] = +inf would mask every token).
+ * With every slot masked a run equals mb_sample bit for bit.  The plan of a run: mb_sample_plan with the float32 masking ratios of the steps
+ * (get_masking_ratio(progress), masking.py:41-65) in the place of the mask lengths. */
+typedef struct {
+  int num_steps;
+  int use_guidance;
+  const float* scale;          /* [num_steps] as in mb_sample_plan */
+  const float* temperature;    /* [num_steps] as in mb_sample_plan */
+  const float* mask_ratio;     /* [num_steps] float32 masking ratio of the step */
+  int step_begin, step_end;    /* step chunk of this call, as in mb_sample_plan; chunk 0 reads init_tokens */
+} mb_edit_plan;
+/* mb_sample_step with the per-sample rule above: num_regen int32 [B] (device) and the step's mask_ratio in the place of k_mask_len. */
+int mb_sample_step_edit(const float* logits_c, const float* logits_u, float scale, float temperature,
+                        const float* exp_noise, const float* conf_noise, float mask_ratio, const int32_t* num_regen,
+                        const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out,
+                        int B, int n, int m, int C, mb_stream stream);
+/* mb_sample from the caller's token state: init_tokens int64 [B,n,m] with the value C at the slots to regenerate (values outside [0, C] are clamped
+ * on the device); the first chunk copies them into the engine and counts num_regen per sample on the device.  Everything else -- zero-scale steps,
+ * precision modes, step chunks and their checks, outputs -- as in mb_sample; a chunk of mb_sample does not continue a run mb_sample_edit began, nor
+ * the other way round. */
+int mb_sample_edit(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens,
+                   const float* exp_noise, const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out,
+                   float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
+/* Stateless helpers around such a run: the caller owns every buffer, nothing is allocated, nothing synchronises.
+ * codes int64 [B,n] (what mb_enc_encode gives) + regen_mask uint8 [B,n,m] (non-zero = regenerate) -> tokens int64 [B,n,m] =
+ * (code >> g * log2(C)) & (C - 1), or C where the mask is set; num_regen int32 [B] = the number of set slots per sample. */
+int mb_edit_init(const int64_t* codes, const uint8_t* regen_mask, int64_t* tokens, int32_t* num_regen, int B, int n, int m, int C, mb_stream stream);
+/* pixel_mask uint8 [B,H,W] -> token_mask uint8 [B,H/stride,W/stride]: 1 where any pixel of the stride x stride block is non-zero.  stride = the
+ * tokenizer's 2^(num_resolutions - 1): a power of two dividing H and W; pixel_mask aligned to min(stride, 16) bytes. */
+int mb_edit_token_mask(const uint8_t* pixel_mask, uint8_t* token_mask, int B, int H, int W, int stride, mb_stream stream);
+/* x = pixel_mask ? gen : orig per pixel (fp32 [B,C,H,W], 16-byte aligned; pixel_mask uint8 [B,H,W], 4-byte aligned; C in 1 .. 4, W % 4 == 0), from
+ * one read of each: out_nchw fp32 [B,C,H,W] = x (may be NULL; must not alias an input) and / or out_nhwc_u8 uint8 [B,H,W,C] = trunc(clamp(x,0,1)*255),
+ * the conversion of mb_dec_decode (may be NULL). */
+int mb_edit_composite(const float* gen_nchw, const float* orig_nchw, const uint8_t* pixel_mask, float* out_nchw, uint8_t* out_nhwc_u8,
+                      int B, int C, int H, int W, mb_stream stream);
+
 /* ---- tokenizer evaluation: TokenizerEvaluator.update, evaluator/evaluator.py:262-375 (scripts/eval_tokenizer.py:137-149) ---------------- *
  * Stateless: the caller owns every buffer (and zeroes its running state once); nothing is allocated, nothing synchronises.
  * Bytes of workspace mb_eval_images needs for this shape (one slot of three doubles per 32 x 32 tile of every image plane); 0 for a shape it

@@ -76,6 +76,9 @@ struct mb_gen {
   // loop state for mb_sample
   // the run mb_sample is in the middle of (step chunks): samples, total steps, guidance flag, the step the next chunk must begin with (-1: no run)
   int loop_B = 0, loop_steps = 0, loop_guided = 0, loop_next = -1;
+  // ... and whether it is an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample, [max_seqs])
+  int loop_edit = 0;
+  int* num_regen = nullptr;
   // precision >= 3: which GEMMs carry the activation-lo set (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down).  Coverage measured on the reference's own runs in round 6
   // (profiles/r06_coverage.md: four 14-bit / 256-step runs, four 12-bit runs, three trained-like runs; mismatches / guided-forward time of 64 pairs):
   //   none 595 / 263 / 271 at 29.9 ms;  FFN-up of layers >= depth / 2 (round 5's precision 3) 506 / 222 / 276 at 30.5;  out-proj + FFN-up 384 / 186 / 219 at 31.6;
@@ -479,6 +482,7 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   rc |= galloc(g, &g->tok_a, B * P); rc |= galloc(g, &g->tok_b, B * P); rc |= galloc(g, &g->tok_cfg, B * P);
   rc |= galloc(g, &g->pred, B * P); rc |= galloc(g, &g->codes, B * c.seq);
   rc |= galloc(g, &g->lab_cfg, B); rc |= galloc(g, &g->drop_cfg, B); rc |= galloc(g, &g->logits, B * P * C);
+  rc |= galloc(g, &g->num_regen, B);
   if (g->chunk_seqs < max_seqs) rc |= galloc(g, &g->logits_tmp, (size_t)g->chunk_seqs * P * C);
   if (rc) { mb_gen_destroy(g); return rc; }
   *out = g;
@@ -613,29 +617,48 @@ int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels,
   return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
 }
 
+// (who: the entry point's name in the messages; num_regen != null: the edit step, which reads mask_ratio instead of k_mask_len)
+static int sample_step_checked(const char* who, const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise,
+                               const float* conf_noise, int k_mask_len, float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in,
+                               int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
+  if (!logits_c || !exp_noise || !conf_noise || !tokens_in || !tokens_out) return fail(-1, "%s: null argument", who);
+  if (tokens_in == tokens_out) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
+  if (B <= 0 || n <= 0 || m <= 0 || C <= 0) return fail(-1, "%s: bad sizes", who);
+  mb::StepArgs a{logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, tokens_out, pred_out, B, n * m, C};
+  ProfScope p(num_regen ? "sample_step_edit" : "sample_step", (hipStream_t)stream);
+  if (mb::sample_step((hipStream_t)stream, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, C, n * m);
+  return launched();
+}
+
 int mb_sample_step(const float* logits_c, const float* logits_u, float scale, float temperature,
                    const float* exp_noise, const float* conf_noise, int k_mask_len, const int64_t* tokens_in,
                    int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  if (!logits_c || !exp_noise || !conf_noise || !tokens_in || !tokens_out) return fail(-1, "mb_sample_step: null argument");
-  if (tokens_in == tokens_out) return fail(-1, "mb_sample_step: tokens_in and tokens_out must not alias");
-  if (B <= 0 || n <= 0 || m <= 0 || C <= 0) return fail(-1, "mb_sample_step: bad sizes");
-  mb::StepArgs a{logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, tokens_out, pred_out, B, n * m, C};
-  ProfScope p("sample_step", (hipStream_t)stream);
-  if (mb::sample_step((hipStream_t)stream, a, tokens_in)) return fail(-1, "mb_sample_step: C=%d or n*m=%d too large", C, n * m);
-  return launched();
+  return sample_step_checked("mb_sample_step", logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, 0.f, nullptr, tokens_in, tokens_out,
+                             pred_out, B, n, m, C, stream);
+}
+
+int mb_sample_step_edit(const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise, const float* conf_noise,
+                        float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m,
+                        int C, mb_stream stream) {
+  if (!num_regen) return fail(-1, "mb_sample_step_edit: null argument");
+  return sample_step_checked("mb_sample_step_edit", logits_c, logits_u, scale, temperature, exp_noise, conf_noise, 0, mask_ratio, num_regen, tokens_in,
+                             tokens_out, pred_out, B, n, m, C, stream);
 }
 
 // ================================================================================================
 // whole loop (sampling.py:55-136)
 // ================================================================================================
-int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B, const float* exp_noise,
-              const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
-              uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!g || !plan || !labels || !exp_noise || !conf_noise) return fail(-1, "mb_sample: null argument");
-  if (!plan->scale || !plan->temperature || !plan->mask_len || plan->num_steps <= 0) return fail(-1, "mb_sample: incomplete plan");
-  const int nbf = plan->use_guidance ? 2 * B : B;
-  if (B <= 0 || nbf > g->max_seqs) return fail(-1, "mb_sample: B=%d needs %d sequences, engine holds %d", B, nbf, g->max_seqs);
-  if (!d && (img_nchw || img_nhwc_u8)) return fail(-1, "mb_sample: image requested without a decoder");
+// mb_sample (init_tokens = null: the run starts all-masked, the step reads mask_len) and mb_sample_edit (the run starts from init_tokens, the step reads
+// mask_ratio and the per-sample counts the first chunk left in g->num_regen)
+static int sample_run(const char* who, mb_gen* g, mb_dec* d, int num_steps, int use_guidance, const float* scale, const float* temperature, const int* mask_len,
+                      const float* mask_ratio, int step_begin, int step_end, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
+                      const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
+  const bool edit = mask_ratio != nullptr;
+  if (!g || !labels || !exp_noise || !conf_noise || (edit && !init_tokens)) return fail(-1, "%s: null argument", who);
+  if (!scale || !temperature || !(edit ? (const void*)mask_ratio : (const void*)mask_len) || num_steps <= 0) return fail(-1, "%s: incomplete plan", who);
+  const int nbf = use_guidance ? 2 * B : B;
+  if (B <= 0 || nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
+  if (!d && (img_nchw || img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
   hipStream_t s = (hipStream_t)stream;
   const mb_gen_cfg& c = g->c;
   const int n = c.seq, m = c.splits, C = g->C;
@@ -643,14 +666,18 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
   // state init (sampling.py:65-71): every position masked; CFG batch = [cond | label-dropped]
   // A run may be fed in step chunks (plan->step_begin / step_end: the noise of a whole 256-step run at batch 100 is 6.7 GB): chunk [0, e) starts from
   // the all-masked state, later chunks continue from the token state the engine kept; exp_noise / conf_noise / step_tokens hold THIS chunk's steps.
-  const int s0 = plan->step_end > 0 ? plan->step_begin : 0, s1 = plan->step_end > 0 ? plan->step_end : plan->num_steps;
-  if (s0 < 0 || s1 > plan->num_steps || s0 >= s1) return fail(-1, "mb_sample: step chunk [%d, %d) outside [0, %d)", s0, s1, plan->num_steps);
+  const int s0 = step_end > 0 ? step_begin : 0, s1 = step_end > 0 ? step_end : num_steps;
+  if (s0 < 0 || s1 > num_steps || s0 >= s1) return fail(-1, "%s: step chunk [%d, %d) outside [0, %d)", who, s0, s1, num_steps);
   // A run fed in chunks keeps its token state in the engine: a chunk is accepted only as the exact continuation of the run in progress (same batch,
-  // plan length and guidance flag, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
-  if (s0 == 0) { mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P); g->loop_B = B; g->loop_steps = plan->num_steps; g->loop_guided = plan->use_guidance != 0; }
-  else if (g->loop_next != s0 || g->loop_B != B || g->loop_steps != plan->num_steps || g->loop_guided != (plan->use_guidance != 0))
-    return fail(-1, "mb_sample: step chunk [%d, %d) of a %d-step run with B = %d does not continue the run in progress (next step %d of %d, B = %d)",
-                s0, s1, plan->num_steps, B, g->loop_next, g->loop_steps, g->loop_B);
+  // plan length, guidance flag and kind -- plain or edit --, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
+  if (s0 == 0) {
+    if (edit) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
+    else mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
+    g->loop_B = B; g->loop_steps = num_steps; g->loop_guided = use_guidance != 0; g->loop_edit = edit;
+  }
+  else if (g->loop_next != s0 || g->loop_B != B || g->loop_steps != num_steps || g->loop_guided != (use_guidance != 0) || g->loop_edit != (int)edit)
+    return fail(-1, "%s: step chunk [%d, %d) of a %d-step %s run with B = %d does not continue the run in progress (next step %d of %d, B = %d, %s)",
+                who, s0, s1, num_steps, edit ? "edit" : "plain", B, g->loop_next, g->loop_steps, g->loop_B, g->loop_edit ? "an edit run" : "a plain run");
   g->loop_next = -1;                                   // (set again below when this chunk has been enqueued and more follow)
   int64_t* cur = (s0 & 1) ? g->tok_b : g->tok_a;
   int64_t* nxt = (s0 & 1) ? g->tok_a : g->tok_b;
@@ -665,7 +692,7 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
     // forward is not run: the step is the plain conditional forward, bit for bit what the guided expression evaluates to.
     // (precision 4: the guided forward is also the MORE PRECISE conditional forward -- its pair tiles carry the activation-lo sets, the plain tiles do not --
     // and the first, almost fully masked steps are where near-ties flip: the zero-scale steps run it too; its unconditional half is then multiplied by 0)
-    if (plan->use_guidance && (plan->scale[i] != 0.0f || (g->pair_ok && c.precision >= 4))) {
+    if (use_guidance && (scale[i] != 0.0f || (g->pair_ok && c.precision >= 4))) {
       rc = gen_forward_cfg(g, cur, labels, g->logits, B, s);
       lu = g->logits + (size_t)B * P * C;
       if (B <= g->chunk_seqs / 2) { g->cfg_labels_ready = labels; g->cfg_ready_B = B; }   // lab_cfg / drop_cfg stay valid for the rest of this call
@@ -675,14 +702,16 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
     if (rc) { g->cfg_labels_ready = nullptr; return rc; }
     const size_t k = (size_t)(i - s0);                 // the noise / step_tokens buffers hold this chunk's steps
     int64_t* pred = step_tokens ? step_tokens + k * B * P : g->pred;
-    rc = mb_sample_step(lc, lu, plan->scale[i], plan->temperature[i], exp_noise + k * B * P * C,
-                        conf_noise + k * B * P, plan->mask_len[i], cur, nxt, pred, B, n, m, C, stream);
+    rc = edit ? mb_sample_step_edit(lc, lu, scale[i], temperature[i], exp_noise + k * B * P * C, conf_noise + k * B * P, mask_ratio[i], g->num_regen,
+                                    cur, nxt, pred, B, n, m, C, stream)
+              : mb_sample_step(lc, lu, scale[i], temperature[i], exp_noise + k * B * P * C, conf_noise + k * B * P, mask_len[i], cur, nxt, pred, B, n, m,
+                               C, stream);
     if (rc) { g->cfg_labels_ready = nullptr; return rc; }
     last_pred = pred;
     int64_t* t = cur; cur = nxt; nxt = t;
   }
   g->cfg_labels_ready = nullptr;
-  if (s1 < plan->num_steps) {                          // more chunks follow: keep the last predictions only if they are the engine's own buffer
+  if (s1 < num_steps) {                                // more chunks follow: keep the last predictions only if they are the engine's own buffer
     if (int rc = launched()) return rc;
     g->loop_next = s1;
     return 0;
@@ -695,6 +724,21 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
     if (rc) return rc;
   }
   return launched();
+}
+
+int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B, const float* exp_noise,
+              const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
+              uint8_t* img_nhwc_u8, mb_stream stream) {
+  if (!plan) return fail(-1, "mb_sample: null argument");
+  return sample_run("mb_sample", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, plan->mask_len, nullptr, plan->step_begin,
+                    plan->step_end, labels, B, nullptr, exp_noise, conf_noise, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+}
+
+int mb_sample_edit(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
+                   const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
+  if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_edit: %s", plan ? "incomplete plan" : "null argument");
+  return sample_run("mb_sample_edit", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, nullptr, plan->mask_ratio, plan->step_begin,
+                    plan->step_end, labels, B, init_tokens, exp_noise, conf_noise, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
 }
 
 }  // extern "C"

@@ -167,10 +167,23 @@ struct StepArgs {
   int64_t* pred;             // [B, n*m] out (may be null)
   int B, P /* n*m */, C;
 };
-int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in);
+// num_regen != null: the EDIT step (mb_sample_step_edit) -- per sample b the mask length is floor(mask_ratio * num_regen[b]), the masked count is the
+// sample's own, and a sample with fewer than two masked slots is not re-masked; a.k_mask_len is not read.
+int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in, const int* num_regen = nullptr, float mask_ratio = 0.f);
 
 // ---- small integer helpers of the loop (sampling.py:65, factorization.py:7-24) -------------------
 void fill_i64(hipStream_t s, int64_t* dst, int64_t value, size_t n);
+
+// ---- image editing (edit.hip): the helpers in front of and behind a sampling run that starts from a partly known token map ----------------------
+// One workgroup per sample, deterministic count.  src int64 [B, P] -> dst (may be null) = src clamped to [0, C], num_regen[b] = slots of sample b equal to C
+void edit_load_tokens(hipStream_t s, const int64_t* src, int64_t* dst, int* num_regen, int B, int P, int C);
+// codes int64 [B, n] + regeneration mask uint8 [B, n, m] -> grouped tokens [B, n, m] ((code >> g * gbits) & (C - 1); C where the mask is set), num_regen[B]
+void edit_init(hipStream_t s, const int64_t* codes, const uint8_t* regen, int64_t* tokens, int* num_regen, int B, int n, int m, int gbits);
+// pixel mask uint8 [B, H, W] -> token mask uint8 [B, H / st, W / st]: 1 if any pixel of the st x st block is set.  st a power of two, W % st == 0, H % st == 0
+void edit_token_mask(hipStream_t s, const uint8_t* pixel_mask, uint8_t* token_mask, int B, int H, int W, int st);
+// x = mask ? gen : orig per pixel (fp32 [B, C, H, W], mask uint8 [B, H, W]); out_nchw (may be null) = x, out_u8 (may be null) uint8 [B, H, W, C] =
+// trunc(clamp(x, 0, 1) * 255).  C in 1 .. 4, W % 4 == 0; -1 otherwise
+int edit_composite(hipStream_t s, const float* gen, const float* orig, const uint8_t* pixel_mask, float* out_nchw, uint8_t* out_u8, int B, int C, int H, int W);
 void combine_groups(hipStream_t s, const int64_t* tokens /*[rows,m]*/, int64_t* codes /*[rows]*/, size_t rows, int m, int gbits);
 
 // ---- fp32 -> h16 repack ------------------------------------------------------------------------

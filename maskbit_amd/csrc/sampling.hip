@@ -14,7 +14,8 @@ namespace mb {
 // Two launches (round 3; one workgroup per image did both parts, i.e. 64 of 256 CUs ran 32 latency-bound rows per wave: 100 us per step):
 //   sample_rows_kernel   -- one wave per (image, position, group) row, 16 rows per 4-wave workgroup over the whole chip: guidance, softmax, draw,
 //                           confidence.  Result packed into the int64 slot of tokens_out: low dword = the confidence's float bits, high dword = pred.
-//   sample_thresh_kernel -- one workgroup per image: unpack into LDS, k-th smallest confidence by rank counting, re-mask, write tokens (+ pred).
+//   sample_thresh_kernel -- one workgroup per image: unpack into LDS, k-th smallest confidence by rank counting, re-mask, write tokens (+ pred);
+//                           <true>: the per-sample rule of the edit step (sample_step with num_regen).
 // The arithmetic per row and the order statistic are unchanged (bit-exact with the oracle: tests/test_hip_parity.py).
 template <int CPL>   // logits per lane: C <= 64*CPL
 __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int64_t* __restrict__ tokens_in) {
@@ -81,7 +82,14 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
   }
 }
 
-__global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const int64_t* __restrict__ tokens_in) {
+// The threshold stage of both step kernels.  EDIT = false: the reference's rule (one masked count, SAMPLE 0's, and one mask length for the whole batch; the
+// Python index k - 1 may wrap).  EDIT = true (sample_step_edit, image editing: samples that start from different masked counts): per sample b
+//   mask_len = floor(ratio * M[b]) in fp32 (torch.floor(ratio * num_maskable) with a float32 ratio), nm = sample b's own masked count,
+//   nm >= 2: k = min(max(mask_len, 1), nm - 1) -- k - 1 <= nm - 2, so the threshold is a MASKED slot's confidence and a known slot (+inf) is never re-masked;
+//   nm <= 1: nothing is re-masked (tokens_out = pred).  The reference's clamp reaches k = 0 there, sorted[-1] = +inf, and every token of the image,
+//            the known ones included, would be masked again (DESIGN.md "Editing").
+template <bool EDIT>
+__global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const int64_t* __restrict__ tokens_in, float ratio, const int* __restrict__ num_regen) {
   extern __shared__ float sm[];
   const int P = a.P;
   float* conf_s = sm;                    // [P]
@@ -91,9 +99,10 @@ __global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const i
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int b = blockIdx.x;
   const int64_t mask_tok = (int64_t)a.C;
-  // num_masked of SAMPLE 0 (sampling.py:109 reads index [0] for the whole batch)
+  // num_masked of SAMPLE 0 (sampling.py:109 reads index [0] for the whole batch); EDIT: of this sample
+  const int64_t* tin = EDIT ? tokens_in + (size_t)b * P : tokens_in;
   int mycnt = 0;
-  for (int p = tid; p < P; p += blockDim.x) mycnt += tokens_in[p] == mask_tok;
+  for (int p = tid; p < P; p += blockDim.x) mycnt += tin[p] == mask_tok;
   mycnt = (int)wave_sum((float)mycnt);
   if (lane == 0) cnt_s[wave] = mycnt;
   if (tid == 0) *thr_s = -INFINITY;
@@ -106,26 +115,30 @@ __global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const i
   int nm = 0;
   for (int w = 0; w < nw; ++w) nm += cnt_s[w];
   // k = clamp(floor(ratio*P), 1, num_masked-1), threshold = sorted[k-1] (python index, may wrap)
-  int k = min(max(a.k_mask_len, 1), nm - 1);
+  const int mask_len = EDIT ? (int)floorf(__fmul_rn(ratio, (float)num_regen[b])) : a.k_mask_len;
+  const bool remask = !EDIT || nm >= 2;
+  int k = min(max(mask_len, 1), nm - 1);
   int idx = k - 1;
   if (idx < 0) idx += P;
-  for (int p = tid; p < P; p += blockDim.x) {
-    const float x = conf_s[p];
-    int lt = 0, le = 0;
-    for (int j = 0; j < P; ++j) { const float y = conf_s[j]; lt += y < x; le += y <= x; }
-    if (lt <= idx && idx < le) *thr_s = x;
+  if (remask) {
+    for (int p = tid; p < P; p += blockDim.x) {
+      const float x = conf_s[p];
+      int lt = 0, le = 0;
+      for (int j = 0; j < P; ++j) { const float y = conf_s[j]; lt += y < x; le += y <= x; }
+      if (lt <= idx && idx < le) *thr_s = x;
+    }
   }
   __syncthreads();
   const float thr = *thr_s;
   for (int p = tid; p < P; p += blockDim.x) {
     const size_t row = (size_t)b * P + p;
     const int pr = pred_s[p];
-    a.tokens[row] = conf_s[p] <= thr ? mask_tok : (int64_t)pr;           // :128-129
+    a.tokens[row] = remask && conf_s[p] <= thr ? mask_tok : (int64_t)pr;  // :128-129
     if (a.pred) a.pred[row] = (int64_t)pr;
   }
 }
 
-int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in) {
+int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in, const int* num_regen, float mask_ratio) {
   if (a.C > 4096 || a.P > 8192) return -1;
   const size_t nrows = (size_t)a.B * a.P;
   dim3 grid((unsigned)((nrows + 15) / 16)), block(256);
@@ -137,7 +150,9 @@ int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in) {
   else if (a.C <= 2048) hipLaunchKernelGGL(sample_rows_kernel<32>, grid, block, 0, s, a, tokens_in);
   else hipLaunchKernelGGL(sample_rows_kernel<64>, grid, block, 0, s, a, tokens_in);
   const size_t shm = (size_t)a.P * 8 + 16 * 4 + 16;
-  hipLaunchKernelGGL(sample_thresh_kernel, dim3(a.B), dim3(a.P >= 1024 ? 1024 : 512), shm, s, a, tokens_in);
+  const dim3 tblock(a.P >= 1024 ? 1024 : 512);
+  if (num_regen) hipLaunchKernelGGL(sample_thresh_kernel<true>, dim3(a.B), tblock, shm, s, a, tokens_in, mask_ratio, num_regen);
+  else hipLaunchKernelGGL(sample_thresh_kernel<false>, dim3(a.B), tblock, shm, s, a, tokens_in, 0.f, (const int*)nullptr);
   return 0;
 }
 

@@ -23,26 +23,58 @@ from .conv_vqgan import ConvVQModel
 from .masking import get_masking_ratio
 
 
+def _scale_temperature(i: int, num_steps: int, guidance_scale: float, guidance_annealing: str, scale_pow: float, softmax_temperature: float,
+                       use_sampling_annealing: bool):
+    """Guidance scale and softmax temperature of step ``i`` (sampling.py:82, 90-98, 103-104)."""
+    progress = (i + 1) / num_steps
+    if guidance_annealing == "none":
+        a = guidance_scale * 1.0
+    elif guidance_annealing == "linear":
+        a = guidance_scale * (i / num_steps)
+    elif guidance_annealing == "cosine":
+        sp = torch.ones(1) * scale_pow                                      # float32, as in the reference
+        a = float(guidance_scale * ((1 - torch.cos(((i / num_steps) ** sp) * torch.pi)) * 1 / 2))
+    else:
+        raise ValueError(f"guidance_annealing must be 'none', 'linear' or 'cosine', got {guidance_annealing!r}")
+    return float(torch.tensor(a, dtype=torch.float32)), (0.5 + 0.8 * (1 - progress) if use_sampling_annealing else softmax_temperature)
+
+
 def build_plan(num_steps: int, num_maskable: int, guidance_scale: float, guidance_annealing: str, scale_pow: float,
                softmax_temperature: float, use_sampling_annealing: bool, mask_schedule_strategy: str):
     """Host-side per-step constants (sampling.py:82, 90-98, 103-104, 120-123)."""
     get_masking_ratio(1.0, mask_schedule_strategy)          # raises ValueError on a bad strategy before any GPU work
     scale, temp, mask_len = [], [], []
     for i in range(num_steps):
-        progress = (i + 1) / num_steps
-        if guidance_annealing == "none":
-            a = guidance_scale * 1.0
-        elif guidance_annealing == "linear":
-            a = guidance_scale * (i / num_steps)
-        elif guidance_annealing == "cosine":
-            sp = torch.ones(1) * scale_pow                                      # float32, as in the reference
-            a = float(guidance_scale * ((1 - torch.cos(((i / num_steps) ** sp) * torch.pi)) * 1 / 2))
-        else:
-            raise ValueError(f"guidance_annealing must be 'none', 'linear' or 'cosine', got {guidance_annealing!r}")
-        scale.append(float(torch.tensor(a, dtype=torch.float32)))
-        temp.append(0.5 + 0.8 * (1 - progress) if use_sampling_annealing else softmax_temperature)
-        mask_len.append(int(torch.floor(get_masking_ratio(progress, mask_schedule_strategy) * num_maskable)))
+        a, t = _scale_temperature(i, num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing)
+        scale.append(a)
+        temp.append(t)
+        mask_len.append(int(torch.floor(get_masking_ratio((i + 1) / num_steps, mask_schedule_strategy) * num_maskable)))
     return scale, temp, mask_len
+
+
+class EditPlan(tuple):
+    """(scale, temperature, mask_ratio) per step: the plan of a run that starts from a partly known token map (``mb_sample_edit``)."""
+    edit = True
+    force_guidance = False
+
+    def __new__(cls, plan, force_guidance: bool = False):
+        self = super().__new__(cls, plan)
+        self.force_guidance = force_guidance
+        return self
+
+
+def build_edit_plan(num_steps: int, guidance_scale: float, guidance_annealing: str, scale_pow: float, softmax_temperature: float,
+                    use_sampling_annealing: bool, mask_schedule_strategy: str) -> EditPlan:
+    """``build_plan`` for an edit run: the same scales and temperatures, and in the place of the mask lengths the float32 masking ratios themselves
+    -- the device multiplies each by the sample's own initial masked count (``floor(ratio * M_b)`` in fp32, as ``torch.floor(ratio * num_maskable)``)."""
+    get_masking_ratio(1.0, mask_schedule_strategy)
+    scale, temp, ratio = [], [], []
+    for i in range(num_steps):
+        a, t = _scale_temperature(i, num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing)
+        scale.append(a)
+        temp.append(t)
+        ratio.append(float(get_masking_ratio((i + 1) / num_steps, mask_schedule_strategy)))
+    return EditPlan((scale, temp, ratio))
 
 
 def check_tokenizer(model, vqgan_model) -> None:
@@ -142,7 +174,8 @@ def step_chunks(num_samples: int, n: int, m: int, C_: int, num_steps: int):
 
 
 def run_chunked(model: "LFQBert", vqgan_model, labels: torch.Tensor, plan, randomize_temperature: float, **kw):
-    """run_loop over the whole run with the noise drawn chunk by chunk (same random streams as one whole-run draw)."""
+    """run_loop over the whole run with the noise drawn chunk by chunk (same random streams as one whole-run draw).  An ``EditPlan`` with
+    ``init_tokens=`` runs the edit loop: same draws, same chunks."""
     scale = plan[0]
     steps = len(scale)
     B = labels.shape[0]
@@ -164,17 +197,20 @@ def run_chunked(model: "LFQBert", vqgan_model, labels: torch.Tensor, plan, rando
 
 
 def plan_arrays(plan):
-    """The plan as the ctypes arrays ``mb_sample`` reads (+ whether any step is guided)."""
+    """The plan as the ctypes arrays ``mb_sample`` reads (+ whether any step is guided); of an ``EditPlan``, those ``mb_sample_edit`` reads."""
     scale, temp, mask_len = plan
     nsteps = len(scale)
     use_cfg = any(s != 0.0 for s in scale) or getattr(plan, "force_guidance", False)
-    return (C.c_float * nsteps)(*scale), (C.c_float * nsteps)(*temp), (C.c_int * nsteps)(*mask_len), use_cfg
+    third = C.c_float if getattr(plan, "edit", False) else C.c_int            # (an edit plan holds the float32 masking ratios there)
+    return (C.c_float * nsteps)(*scale), (C.c_float * nsteps)(*temp), (third * nsteps)(*mask_len), use_cfg
 
 
 def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan, exp_noise: torch.Tensor,
              conf_noise: torch.Tensor, want_steps: bool = True, want_image: bool = True, want_u8: bool = False,
-             step_range: Optional[Tuple[int, int]] = None, _cplan=None):
+             step_range: Optional[Tuple[int, int]] = None, _cplan=None, init_tokens: Optional[torch.Tensor] = None):
     """One ``mb_sample`` call.  -> (image or None, uint8 NHWC or None, step tokens [steps,B,n,m] or None, codes [B,n]).
+    ``init_tokens`` (int64 [B,n,m] on the model's device, ``model.mask_token`` at the slots to regenerate) with an ``EditPlan``: one ``mb_sample_edit``
+    call -- the run starts from those tokens instead of the all-masked state (read by the chunk that starts the run).
     ``step_range`` = (begin, end): only those steps of the plan, with ``exp_noise`` / ``conf_noise`` holding that chunk's noise; chunk (0, e)
     starts the run, later chunks continue from the engine's token state, the chunk ending at the last step combines and decodes (image / codes
     are meaningful only then)."""
@@ -187,6 +223,11 @@ def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.T
         raise ValueError(f"noise holds {exp_noise.shape[0]} steps, the step range {steps}")
     B = labels.shape[0]
     n, m = model.seq_len, model.splits
+    edit = getattr(plan, "edit", False)
+    if edit != (init_tokens is not None):
+        raise ValueError("an edit plan (build_edit_plan) and init_tokens go together")
+    if edit and (init_tokens.shape != (B, n, m) or init_tokens.dtype != torch.int64 or init_tokens.device.type != dev.type or not init_tokens.is_contiguous()):
+        raise ValueError(f"init_tokens must be a contiguous int64 [{B}, {n}, {m}] tensor on {dev}")
     c_scale, c_temp, c_len, use_cfg = _cplan if _cplan is not None else plan_arrays(plan)
     labels = labels.to(device=dev, dtype=torch.int64).contiguous()
     step_tokens = torch.empty((steps, B, n, m), dtype=torch.int64, device=dev) if want_steps else None
@@ -203,9 +244,15 @@ def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.T
             u8 = torch.empty((B, res, res, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
         hdec = vqgan_model.engine(B, side)
     hgen = model.engine(2 * B if use_cfg else B)
-    cplan = _lib.SamplePlan(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_len, sb if step_range is not None else 0, se if step_range is not None else 0)
+    cplan = (_lib.EditPlan if edit else _lib.SamplePlan)(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_len, sb if step_range is not None else 0,
+                                                         se if step_range is not None else 0)
     ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(dev):
+        if edit:
+            _lib.check(_lib.load().mb_sample_edit(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, init_tokens.data_ptr(), exp_noise.data_ptr(),
+                                                  conf_noise.data_ptr(), ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
+                                                  torch.cuda.current_stream().cuda_stream), "mb_sample_edit")
+            return img, u8, step_tokens, codes
         _lib.check(_lib.load().mb_sample(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, exp_noise.data_ptr(),
                                          conf_noise.data_ptr(), ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
                                          torch.cuda.current_stream().cuda_stream), "mb_sample")
