@@ -230,6 +230,34 @@ int mb_eval_images(const float* real, const float* fake, int B, int C, int H, in
  * number. */
 int mb_eval_codebook(const int64_t* indices, int64_t n, int K, int64_t* hist, unsigned* out_of_range, mb_stream stream);
 
+/* ---- masked-token validation: the forward half of the training step, scripts/train_maskbit.py:372-381 ------------------------------------ *
+ * Stateless like the tokenizer evaluation above: caller-owned buffers, no allocation, no synchronisation.
+ * get_mask_tokens (modeling/modules/masking.py:34-37) after its draws: mask uint8 [B,n,m] = uniforms < val_to_mask[b] (fp32 compare; uniforms fp32
+ * [B,n,m] and val_to_mask fp32 [B] are the caller's draws and schedule values, masking.py:22-30,35) and masked_tokens int64 [B,n,m] = mask ?
+ * mask_token : tokens, in place of the clone / boolean-index / full_like / index_put chain.  tokens is not modified and must not alias
+ * masked_tokens. */
+int mb_mlm_mask(const int64_t* tokens, const float* uniforms, const float* val_to_mask, int64_t mask_token, int64_t* masked_tokens, uint8_t* mask,
+                int B, int n, int m, mb_stream stream);
+/* Bytes of workspace mb_mlm_loss needs for this shape (one 48-byte slot per workgroup and per sample); 0 for a shape it does not take. */
+size_t mb_mlm_workspace_bytes(int B, int n, int m, int C);
+/* Bytes of the pooled state of mb_mlm_loss: 37 words of 8 bytes, zeroed once by the caller --
+ *   [0] double sum of the loss over all rows, [1] double sum over the masked rows,
+ *   [2..5] int64 rows, masked rows, correct rows, correct masked rows,
+ *   [6 + 3 k .. 8 + 3 k], k = 0..9: double masked-loss sum, int64 masked correct, int64 masked rows of the samples whose realised mask fraction
+ *   falls in decile k = min(9, 10 * masked / (n * m)) (integer division),
+ *   [36] int64 targets outside [0, C). */
+size_t mb_mlm_state_bytes(void);
+/* MLMLoss.forward (modeling/modules/losses.py:319-326) from one read of logits fp32 [B,n,m,C] (contiguous, any C >= 2): per row the label-smoothed
+ * cross entropy of torch.nn.CrossEntropyLoss(label_smoothing) against targets int64 [B,n,m] and whether the first index of the row's maximum
+ * (torch.argmax) equals the target, summed over all rows and over the rows with mask uint8 [B,n,m] != 0 -- in place of the reshape / log-softmax /
+ * gather / smoothing mean / argmax chain, its boolean-index copy inputs[masks] (a host synchronisation) and the same chain on the copy.
+ * sample_sums double [B][2] = sum of the row losses over all / over the masked rows of each sample; sample_counts int64 [B][3] = correct rows,
+ * correct masked rows, masked rows (either may be NULL).  state (may be NULL) += the samples in sample order: deterministic, no floating-point
+ * atomics; a sample's figures do not depend on B, and consecutive calls on the parts of a batch leave the bits of one call on the whole.  A row
+ * whose target lies outside [0, C) enters no figure and is counted in the state's last word; memory is never indexed by a target. */
+int mb_mlm_loss(const float* logits, const int64_t* targets, const uint8_t* mask, float label_smoothing, int B, int n, int m, int C,
+                void* workspace, double* sample_sums, int64_t* sample_counts, void* state, mb_stream stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */
 int mb_prof_read(char* buf, int buflen); /* host buffer; writes "name calls total_ms\n" lines */

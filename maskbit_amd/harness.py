@@ -19,7 +19,9 @@ import torch
 
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
+from .factorization import split_factorized_tokens
 from .sampling import build_plan, check_tokenizer, run_chunked, _ForcedPlan
+from .validation import MaskedTokenEvaluator, get_mask_tokens
 
 
 def eval_labels(device, nclass: int = 1000, repeats: int = 50) -> torch.Tensor:
@@ -111,4 +113,46 @@ def eval_reconstruction(model: ConvVQModel, loader, evaluator):
         images = batch["image"].to(dev, memory_format=torch.contiguous_format, non_blocking=True)
         reconstructed_images, model_dict = model(images)
         evaluator.update(images, reconstructed_images, model_dict["min_encoding_indices"], clamp=True)
+    return evaluator.result()
+
+
+@torch.no_grad()
+def eval_masked_prediction(model: LFQBert, vqgan_model: ConvVQModel, loader, evaluator: Optional[MaskedTokenEvaluator] = None, *,
+                           mask_schedule_strategy: Text = "arccos", min_masking_ratio: float = 0.0, class_label_dropout: float = 0.0,
+                           generator: Optional[torch.Generator] = None):
+    """The forward half of the reference's training step as a validation pass (scripts/train_maskbit.py:356-381, without gradients): per batch
+    ``vqgan_model.encode(images)`` -> ``min_encoding_indices`` -> ``split_factorized_tokens`` -> ``get_mask_tokens`` with
+    ``mask_token_for(codebook_size, splits)`` -> ``model(masked_tokens, class_ids, drop_label_mask)`` -> ``evaluator.update(logits, tokens,
+    masks)``, and ``evaluator.result()`` at the end (the evaluator is reset first; a ``MaskedTokenEvaluator()`` with the reference's defaults when
+    none is given).  ``loader`` yields dicts with ``"image"`` [B, 3, H, W] and ``"class_id"`` [B] as the reference's data loader does.  ``model``:
+    ``LFQBert`` or ``Bert``; ``vqgan_model``: a lookup-free tokenizer whose codebook the generator was built for.
+
+    Random numbers: the masks are drawn as ``get_mask_tokens`` documents (CPU generator: ``generator``, or the global one).  The label-drop mask
+    is drawn only when ``class_label_dropout`` > 0, then as ``torch.rand(B) < class_label_dropout`` from the SAME CPU generator after the
+    batch's masks -- the reference draws it with ``rand_like`` on the labels' device (train_maskbit.py:379), a stream this engine does not
+    reproduce.  Nothing in the loop synchronises with the host."""
+    if not isinstance(model, LFQBert) or not isinstance(vqgan_model, ConvVQModel):
+        raise TypeError("eval_masked_prediction() needs a maskbit_amd generator and tokenizer")
+    check_tokenizer(model, vqgan_model)
+    dev = model._require_cuda("eval_masked_prediction")
+    model.eval()
+    vqgan_model.eval()
+    if evaluator is None:
+        evaluator = MaskedTokenEvaluator()
+    evaluator.reset_metrics()
+    codebook_size, splits = 2 ** model.bits, model.splits
+    mask_token = mask_token_for(codebook_size, splits)
+    for batch in loader:
+        images = batch["image"].to(dev, memory_format=torch.contiguous_format, non_blocking=True)
+        class_tokens = batch["class_id"].to(dev, non_blocking=True)
+        _, encoder_dict = vqgan_model.encode(images)
+        input_tokens = encoder_dict["min_encoding_indices"]
+        input_tokens = split_factorized_tokens(input_tokens.reshape(input_tokens.shape[0], -1), codebook_size=codebook_size, splits=splits)
+        masked_tokens, masks = get_mask_tokens(input_tokens, mask_token, mode=mask_schedule_strategy, min_masking_ratio=min_masking_ratio,
+                                               generator=generator)
+        drop_label_mask = None
+        if class_label_dropout > 0:
+            drop_label_mask = torch.rand(class_tokens.shape[0], generator=generator) < class_label_dropout
+        logits = model(masked_tokens, class_tokens, drop_label_mask)
+        evaluator.update(logits, input_tokens, masks)
     return evaluator.result()

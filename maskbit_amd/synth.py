@@ -308,3 +308,18 @@ def make_eval_indices(kind: str, K: int, shape, seed: int) -> Tensor:
     if kind == "skew":
         return (torch.rand(tuple(shape), generator=g).pow(3) * (K // 3)).long()
     raise ValueError(f"unknown index kind {kind!r}")
+
+
+def make_mlm_case(b: int, n: int, m: int, C: int, seed: int) -> Tuple[Tensor, Tensor]:
+    """Seeded inputs of the masked-token validation fixtures: logits fp32 [b, n, m, C] = 4 * randn, and targets int64 [b, n, m] = the row's
+    argmax on a seeded half of the rows, a uniform draw elsewhere -- accuracies near 0.5, so that ``accuracy ** m`` is not degenerate."""
+    g = torch.Generator().manual_seed(seed)
+    logits = 4.0 * torch.randn(b, n, m, C, generator=g)
+    easy = torch.rand(b, n, m, generator=g) < 0.5
+    other = torch.randint(0, C, (b, n, m), generator=g)
+    return logits.contiguous(), torch.where(easy, logits.argmax(-1), other)
+
+
+def make_mlm_tokens(b: int, n: int, m: int, C: int, seed: int) -> Tensor:
+    """Seeded int64 tokens [b, n, m] in [0, C) for the masking fixtures."""
+    return torch.randint(0, C, (b, n, m), generator=torch.Generator().manual_seed(seed))
