@@ -11,6 +11,15 @@
 
 namespace mb {
 
+// logits_c + scale * (logits_c - logits_u) in the reference's three roundings (sampling.py:98-99).  The __f*_rn functions are plain operators in the HIP
+// headers and contract to an fma under the compiler's default; the pragma is what keeps the product and the sum apart.
+__device__ __forceinline__ float cfg_combine(float c, float u, float scale) {
+#pragma clang fp contract(off)
+  const float d = c - u;
+  const float m = scale * d;
+  return c + m;
+}
+
 // Two launches (round 3; one workgroup per image did both parts, i.e. 64 of 256 CUs ran 32 latency-bound rows per wave: 100 us per step):
 //   sample_rows_kernel   -- one wave per (image, position, group) row, 16 rows per 4-wave workgroup over the whole chip: guidance, softmax, draw,
 //                           confidence.  Result packed into the int64 slot of tokens_out: low dword = the confidence's float bits, high dword = pred.
@@ -38,7 +47,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
       float v = -INFINITY;
       if (c < C) {
         v = lc[c];
-        if (lu) v = __fadd_rn(v, __fmul_rn(a.scale, __fsub_rn(v, lu[c])));   // sampling.py:98-99, no FMA contraction
+        if (lu) v = cfg_combine(v, lu[c], a.scale);
         v = v / a.temperature;                          // :105
       }
       l[i] = v;
