@@ -66,6 +66,40 @@ def gemm_mini(lib, epi, A, W, bias, res, out32, out16, rows, pair, N, K, lo_sets
                                 len(lo_sets), arr, torch.cuda.current_stream().cuda_stream), "mb_gemm_mini")
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def gemm(lib, epi, A, W, bias, res, out32, out16, M, N, K, period=0, variant=0):
+    """mb_gemm (include/maskbit_hip_diag.h): one GEMM of the trunk family on caller buffers; the outputs the epilogue does not write are None."""
+    from maskbit_amd import _lib
+    _lib.check(lib.mb_gemm(epi, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out32), _ptr(out16), M, N, K, period, variant,
+                           torch.cuda.current_stream().cuda_stream), "mb_gemm")
+
+
+def gemm_ex(lib, epi, A, W, bias, res, out32, out16, M, N, K, ln_stats, ln_g, ln_b, period=0, variant=0):
+    """mb_gemm_ex: mb_gemm whose residual is LayerNorm(res rows) re-derived from ln_stats = {mean, rstd}[M] (epilogue 2; res may be out32: in place)."""
+    from maskbit_amd import _lib
+    _lib.check(lib.mb_gemm_ex(epi, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out32), _ptr(out16), M, N, K, _ptr(ln_stats), _ptr(ln_g), _ptr(ln_b),
+                              period, variant, torch.cuda.current_stream().cuda_stream), "mb_gemm_ex")
+
+
+def gemm_act_split(lib, epi, A_hi, A_lo, W, bias, res, out32, out16, M, N, kw, variant=0):
+    """mb_gemm_act_split: out = (A_hi + A_lo) . W^T + bias over fp16 hi + lo activation halves [M, kw]."""
+    from maskbit_amd import _lib
+    _lib.check(lib.mb_gemm_act_split(epi, _ptr(A_hi), _ptr(A_lo), _ptr(W), _ptr(bias), _ptr(res), _ptr(out32), _ptr(out16), M, N, kw, variant,
+                                     torch.cuda.current_stream().cuda_stream), "mb_gemm_act_split")
+
+
+def gemm_mini_split(lib, epi, A_hi, A_lo, W, bias, out16, out4, out4s, rows, N, kw, lo_set):
+    """mb_gemm_mini_split: plain sequence tiles over hi + lo activation halves and one mini-tile operand set lo_set = (A4, a_scale, W4, w_scale)."""
+    import ctypes as C
+    from maskbit_amd import _lib
+    arr = (C.c_void_p * 4)(*[t.data_ptr() for t in lo_set])
+    _lib.check(lib.mb_gemm_mini_split(epi, _ptr(A_hi), _ptr(A_lo), _ptr(W), _ptr(bias), _ptr(out16), _ptr(out4), _ptr(out4s), rows, N, kw, arr,
+                                      torch.cuda.current_stream().cuda_stream), "mb_gemm_mini_split")
+
+
 _F4V = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], dtype=torch.float64)
 
 

@@ -4,6 +4,8 @@ plain PyTorch fp32 matmul of the same fp16 operands.  Tolerance: fp32 accumulati
 import pytest
 import torch
 
+from hip_helpers import gemm, gemm_act_split, gemm_ex
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -16,9 +18,7 @@ def _run(epi, A, W, bias, res, variant, period=0):
     rows = M if epi != 4 else (M // period) * (period - 1)
     out32 = torch.full((rows, N), float("nan"), device=DEV, dtype=torch.float32) if epi in (2, 3, 4) else None
     out16 = torch.full((M, N), float("nan"), device=DEV, dtype=torch.float16) if epi in (0, 1) else None
-    _lib.check(lib.mb_gemm(epi, A.data_ptr(), W.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None,
-                           out32.data_ptr() if out32 is not None else None, out16.data_ptr() if out16 is not None else None,
-                           M, N, K, period, variant, torch.cuda.current_stream().cuda_stream))
+    gemm(lib, epi, A, W, bias, res, out32, out16, M, N, K, period, variant)
     torch.cuda.synchronize()
     return out32 if out32 is not None else out16
 
@@ -118,8 +118,7 @@ def test_layernorm_residual_epilogue(variant, M, N, K):
     assert torch.equal(x16, x32.half())
     plain = _run(2, A, W, bias, x32, variant)
     buf = y.clone()                                                   # in place: residual == out
-    _lib.check(lib.mb_gemm_ex(2, A.data_ptr(), W.data_ptr(), bias.data_ptr(), buf.data_ptr(), buf.data_ptr(), None, M, N, K,
-                              stats.data_ptr(), g.data_ptr(), b.data_ptr(), 0, variant, st))
+    gemm_ex(lib, 2, A, W, bias, buf, buf, None, M, N, K, stats, g, b, 0, variant)
     torch.cuda.synchronize()
     assert torch.equal(buf, plain)
     ref = A.float() @ W.float().t() + bias + ref_ln
@@ -128,7 +127,8 @@ def test_layernorm_residual_epilogue(variant, M, N, K):
 
 @pytest.mark.parametrize("epi,M,N,K", [(0, 1300, 512, 256), (1, 1024, 256, 128), (2, 771, 768, 192), (3, 600, 256, 64 * 5)])
 def test_four_wave_variant_matches_half_tile_kernel(epi, M, N, K):
-    """The experimental 4-wave kernel (variant 4) accumulates in the same order: bit-identical to the production kernel."""
+    """Variant 4 once selected an experimental 4-wave kernel.  That kernel is gone: gemm_ht now treats 4, like any value other than 6 / 8 / 257, as
+    "auto" (the tile height that wastes fewer CU rounds).  Whatever tile height that picks accumulates in the same order: bit-identical to variant 8."""
     torch.manual_seed(epi)
     A = torch.randn(M, K, device=DEV).half()
     W = (torch.randn(N, K, device=DEV) * 0.05).half()
@@ -165,9 +165,7 @@ def test_split_activation_gemm(variant, epi, M, N, K):
     res = torch.randn(M, N, device=DEV) if epi == 2 else None
     out32 = torch.full((M, N), float("nan"), device=DEV) if epi == 2 else None
     out16 = torch.full((M, N), float("nan"), device=DEV, dtype=torch.float16) if epi != 2 else None
-    _lib.check(lib.mb_gemm_act_split(epi, xh.data_ptr(), xl.data_ptr(), W.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None,
-                                     out32.data_ptr() if out32 is not None else None, out16.data_ptr() if out16 is not None else None,
-                                     M, N, K, variant, st))
+    gemm_act_split(lib, epi, xh, xl, W, bias, res, out32, out16, M, N, K, variant)
     torch.cuda.synchronize()
     ref = x32.double() @ W.double().t() + bias.double()
     if epi == 1:
