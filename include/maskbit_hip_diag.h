@@ -55,7 +55,8 @@ int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float
 /* Attention of a CFG pair batch (the generator's guided forward, bert.py:84,137 on both streams): qkv [2 pairs N, 3d] fp16 packed in_proj rows, the
  * conditional sequences first, their unconditional twins `pairs` sequences later.  out rows of conditional sequences = softmax(QK^T/sqrt(dh))V in
  * fp16; rows of unconditional sequences = fp16(o_u - o_c), the difference operand of the out-proj pair GEMM (the conditional output tiles stay in
- * registers in between).  N <= 288: one head's K / V in LDS; longer sequences: the streaming kernel. */
+ * registers in between).  Every N >= 1 is computed: 256 <= N <= 288 with one head's K / V in LDS (that kernel masks keys 256 .. 287 only); shorter
+ * and longer sequences by the streaming kernel, which masks every key >= N.  Refused (negative return, message): head widths other than 32 / 64. */
 int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, int heads, mb_stream stream);
 /* The same launch as the engine issues it at precision >= 2: + out4 [2 pairs N, 2 d] (first d / 2 bytes of a row used) = e2m1 of the CONDITIONAL outputs, two
  * values per byte, and out4_scale = one E8M0 byte per (row, head) in the lane order of the mini-tile passes (mb_kernels.h fp4_scale_index with (N - 1) / 64
@@ -63,6 +64,12 @@ int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, i
  * (N - 1) % 64 == 0 beyond 288. */
 /* out4l / out4l_scale (optional, both or neither; precision 4): the same for the fp16 lo halves o_c - fp16(o_c) of the conditional outputs. */
 int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_scale, void* out4l, void* out4l_scale, int pairs, int N, int d, int heads, mb_stream stream);
+/* The plain forward's attention launch (mb::attention, as the engine issues it): qkv [nb N, 3d] -> out_h16 [nb N, d] = softmax(QK^T/sqrt(dh))V, every
+ * N >= 1 (kernel choice as above); head width d / heads = 32 or 64, anything else is refused.  out4 / out4_scale (optional, both or neither): the e2m1
+ * copy of the token rows of EVERY sequence, written for head width 64 at N = 257 or (N - 1) % 64 == 0 beyond 288; at other shapes no copy is made. */
+int mb_attention(const void* qkv, void* out_h16, void* out4, void* out4_scale, int nb, int N, int d, int heads, mb_stream stream);
+/* The head-averaged softmax weights of one layer (mb::attention_probs, return_attn): out_f32 [nb, N, N]; head width 32 / 64, N <= 5120. */
+int mb_attention_probs(const void* qkv, float* out_f32, int nb, int N, int d, int heads, mb_stream stream);
 /* Which GEMMs of the guided forward carry the ACTIVATION-LO sets of precision >= 3 (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down; every layer).  A handle is
  * created with the operands of its precision's own coverage (3: out-proj + FFN-up = 6; 4: + FFN-down = 14) and runs that; this can only narrow it.  The
  * product never calls this. */

@@ -564,13 +564,18 @@ int attention_probs(hipStream_t s, const h16* qkv, float* out, int nb, int N, in
   return 0;
 }
 
+// attention_kernel stages keys N .. 287 as copies of key N - 1 and masks them in its last two key tiles only (keys 256 .. 287): it computes N = 256 .. 288.
+// Shorter sequences (a 128-pixel model has 64 + 1 tokens) go to the streaming kernels, which mask every key >= N.
+static bool att_streams(int N) { return N > ATT_NP || N < ATT_NP - 32; }
+
 void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, int heads, uint8_t* out4, uint8_t* out4s) {
   const int dh = d / heads;
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-  if (N > ATT_NP) {                                           // longer than one head's K/V fits in LDS: streaming kernel
+  if (att_streams(N)) {                                       // longer than one head's K/V fits in LDS, or shorter than the one-block kernel masks
     const int nchunk = (N + 63) / 64;
+    const bool f4 = N > ATT_NP && (N - 1) % 64 == 0;          // (the e2m1 copy exists for 257 tokens and for whole 64-token groups beyond 288)
     dim3 grid(nb * heads * nchunk), block(256);
-    if (dh == 64) hipLaunchKernelGGL(attention_long_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, 0, (N - 1) % 64 ? nullptr : out4, (N - 1) % 64 ? nullptr : out4s, nb);
+    if (dh == 64) hipLaunchKernelGGL(attention_long_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, 0, f4 ? out4 : nullptr, f4 ? out4s : nullptr, nb);
     else hipLaunchKernelGGL(attention_long_kernel<32>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e);
     return;
   }
@@ -586,8 +591,8 @@ int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d,
   if (dh != 64 && dh != 32) return -1;
   if ((out4l || out4ls) && (!out4 || !out4s || !out4l || !out4ls)) return -1;   // the lo copy rides with the value copy
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-  if (N > ATT_NP) {                                           // the 1024 + 1-token models: streaming kernel, both streams of a pair in one workgroup
-    if (out4 && (dh != 64 || (N - 1) % 64)) return -1;
+  if (att_streams(N)) {                                       // the 1024 + 1-token models (and N < 256): streaming kernel, both streams of a pair in one workgroup
+    if ((out4 || out4s) && (dh != 64 || (N - 1) % 64 || N < ATT_NP)) return -1;
     const int nchunk = ((N + 15) / 16 + 3) / 4;
     dim3 grid(P * heads * nchunk), block(256);
     if (dh == 64) hipLaunchKernelGGL((attention_long_kernel<64, true>), grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, P, out4, out4s, P, out4l, out4ls);

@@ -117,6 +117,19 @@ int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float
   return launched();
 }
 
+int mb_attention(const void* qkv, void* out_h16, void* out4, void* out4_scale, int nb, int N, int d, int heads, mb_stream stream) {
+  if (!qkv || !out_h16 || (!out4) != (!out4_scale) || nb <= 0 || N <= 0 || d <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention: bad arguments");
+  if (d / heads != 32 && d / heads != 64) return fail(-3, "mb_attention: head width %d is outside the attention kernels (32 or 64)", d / heads);
+  ProfScope p("attention", (hipStream_t)stream);
+  mb::attention((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, nb, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale);
+  return launched();
+}
+int mb_attention_probs(const void* qkv, float* out_f32, int nb, int N, int d, int heads, mb_stream stream) {
+  if (!qkv || !out_f32 || nb <= 0 || N <= 0 || d <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_probs: bad arguments");
+  if (mb::attention_probs((hipStream_t)stream, (const h16*)qkv, out_f32, nb, N, d, heads))
+    return fail(-3, "mb_attention_probs: head width %d / N = %d tokens is outside the probabilities kernel (32 or 64; N <= 5120)", d / heads, N);
+  return launched();
+}
 int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, int heads, mb_stream stream) {
   if (!qkv || !out_h16 || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair: bad arguments");
   ProfScope p("attention", (hipStream_t)stream);

@@ -148,7 +148,7 @@ void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, in
                                                                       // bytes for the out-proj GEMM's mini-tile pass
 // "CFG pair" attention: sequences [0, P) are conditional, [P, 2P) their unconditional twins; one workgroup runs a (pair, head) -- conditional pass,
 // then the twin with the conditional output tiles kept in registers -- and writes out[r + P*N] = fp16(att_u - att_c), the difference operand of the
-// out-proj pair GEMM.  N <= 288: K / V of a head in LDS; longer sequences (the 1024 + 1-token models): the streaming kernel in pair form.
+// out-proj pair GEMM.  256 <= N <= 288: K / V of a head in LDS; longer sequences (the 1024 + 1-token models) and shorter ones: the streaming kernel in pair form.
 // out4 / out4s (head dimension 64 only): e2m1 of the conditional output values, row stride 2d bytes, + lane-ordered E8M0 scale bytes (GemmArgs.lo)
 // out4l / out4ls (optional, with out4; precision 4): the same for the fp16 lo halves o_c - fp16(o_c) of the conditional outputs (the out-proj GEMM's activation-lo pass)
 int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d, int heads, uint8_t* out4 = nullptr, uint8_t* out4s = nullptr,

@@ -100,6 +100,28 @@ def gemm_mini_split(lib, epi, A_hi, A_lo, W, bias, out16, out4, out4s, rows, N, 
                                       torch.cuda.current_stream().cuda_stream), "mb_gemm_mini_split")
 
 
+def attention(lib, qkv, out16, nb, N, d, heads, out4=None, out4s=None):
+    """mb_attention: the plain forward's attention launch on caller buffers (out4 / out4s: the optional e2m1 copy, both or neither)."""
+    from maskbit_amd import _lib
+    _lib.check(lib.mb_attention(_ptr(qkv), _ptr(out16), _ptr(out4), _ptr(out4s), nb, N, d, heads, torch.cuda.current_stream().cuda_stream), "mb_attention")
+
+
+def attention_pair(lib, qkv, out16, pairs, N, d, heads, out4=None, out4s=None, out4l=None, out4ls=None):
+    """mb_attention_pair, or mb_attention_pair_f4 when an e2m1 copy is asked for."""
+    from maskbit_amd import _lib
+    st = torch.cuda.current_stream().cuda_stream
+    if out4 is None:
+        _lib.check(lib.mb_attention_pair(_ptr(qkv), _ptr(out16), pairs, N, d, heads, st), "mb_attention_pair")
+    else:
+        _lib.check(lib.mb_attention_pair_f4(_ptr(qkv), _ptr(out16), _ptr(out4), _ptr(out4s), _ptr(out4l), _ptr(out4ls), pairs, N, d, heads, st), "mb_attention_pair_f4")
+
+
+def attention_probs(lib, qkv, out32, nb, N, d, heads):
+    """mb_attention_probs: the head-averaged softmax weights [nb, N, N] fp32."""
+    from maskbit_amd import _lib
+    _lib.check(lib.mb_attention_probs(_ptr(qkv), _ptr(out32), nb, N, d, heads, torch.cuda.current_stream().cuda_stream), "mb_attention_probs")
+
+
 _F4V = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], dtype=torch.float64)
 
 
