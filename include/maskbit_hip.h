@@ -26,6 +26,7 @@ enum { MB_PREC_FP16 = 0, MB_PREC_DIFF = 1, MB_PREC_WCORR = 2, MB_PREC_ALO = 3, M
 
 typedef struct mb_gen mb_gen; /* generator engine  (modeling/bert.py LFQBert)            */
 typedef struct mb_dec mb_dec; /* tokenizer decoder (modeling/conv_vqgan.py ConvVQModel)  */
+typedef struct mb_lpips mb_lpips; /* LPIPS network (modeling/modules/lpips.py LPIPS)        */
 typedef void* mb_stream;      /* hipStream_t                                              */
 
 /* LFQBert constructor arguments (modeling/bert.py:345-358). */
@@ -257,6 +258,26 @@ size_t mb_mlm_state_bytes(void);
  * whose target lies outside [0, C) enters no figure and is counted in the state's last word; memory is never indexed by a target. */
 int mb_mlm_loss(const float* logits, const int64_t* targets, const uint8_t* mask, float label_smoothing, int B, int n, int m, int C,
                 void* workspace, double* sample_sums, int64_t* sample_counts, void* state, mb_stream stream);
+
+/* ---- LPIPS: modeling/modules/lpips.py (the metric of evaluator/evaluator.py:336-341) ------------------------------------------------------- *
+ * A handle owns the VGG16 `features` weights (fp16, repacked for the MFMA convolutions of the tokenizer), the five 1x1 weight vectors and a
+ * workspace for max_pairs image pairs of up to max_h x max_w pixels (two fp16 buffers of 2 max_pairs max_h max_w 64 values).  max_h % 128 == 0,
+ * max_w % 256 == 0: the convolution tiles are 8 x 16 pixels and the deepest level runs at 1/16 resolution. */
+int mb_lpips_create(int max_pairs, int max_h, int max_w, mb_lpips** out);
+void mb_lpips_destroy(mb_lpips* h);
+/* One entry of the reference's LPIPS state dict (fp32, device): scaling_layer.shift / .scale, net.slice{1..5}.{0,2,5,7,10,12,14,17,19,21,24,26,28}.weight
+ * / .bias (torchvision's VGG16-D `features` indices inside the reference's five slices), lin{0..4}.model.1.weight (model.0 without dropout).  All 33
+ * must be given before a forward. */
+int mb_lpips_load(mb_lpips* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
+/* LPIPS.forward (lpips.py:39-52) of B pairs real / fake fp32 [B,3,H,W] in [0, 1] (clamp01 != 0: clamped to it on the load, eval_tokenizer.py:146-147):
+ * scaling layer, thirteen 3x3 convolutions + bias + ReLU and four max-pools on both images in one batch of 2B, and per tap one read of the two
+ * feature maps for sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 and its spatial mean.  per_image double [B] = the value of each pair;
+ * *sum (may be NULL) += those values in image order: deterministic, no floating-point atomics, a pair's value does not depend on B.  Features are
+ * stored as fp16 (DESIGN.md "Precision").  1 <= B <= max_pairs, H % 128 == 0, W % 256 == 0, H W <= max_h max_w; anything else is refused before
+ * any device work.  No allocation, no synchronisation. */
+int mb_lpips_forward(mb_lpips* h, const float* real, const float* fake, int B, int H, int W, int clamp01, double* per_image, double* sum, mb_stream stream);
+/* 4-channel activation groups of this handle's convolutions clamped at +-65504 since the last reset.  Synchronises `stream`. */
+int mb_lpips_saturation_count(mb_lpips* h, unsigned* count, int reset, mb_stream stream);
 
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */

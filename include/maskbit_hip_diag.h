@@ -107,6 +107,26 @@ int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta,
 int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
 int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
 
+/* ---- the pieces of the LPIPS forward (lpips.hip, decoder.hip) on caller buffers.
+ * mb_conv_relu_layer: one convolution + bias + ReLU as the VGG16 stack launches it (no GroupNorm prologue or partials, zero padding 1 for ks 3;
+ * ks 1 or 3): in_h16 fp16 NHWC [B, H, W, Cin] with the true channel count, w_oihw fp32 [Cout, Cin, ks, ks], bias fp32 [Cout] or NULL, out_h16
+ * [B, H, W, Cout] (Cout % 4 == 0), H % 8 == 0, W % 16 == 0; *saturated (host) as for mb_conv_layer.  Synchronises the stream. */
+int mb_conv_relu_layer(const void* in_h16, const float* w_oihw, const float* bias, void* out_h16, unsigned* saturated, int B, int H, int W, int Cin,
+                       int Cout, int ks, mb_stream stream);
+/* max_pool2d(2, 2) of x fp16 [B, H, W, C] -> [B, H/2, W/2, C]; C % 8 == 0. */
+int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
+/* The input kernel: real / fake fp32 [B,3,H,W] -> out_h16 fp16 [2B, H, W, 64] (real images first), channel ci * 9 + ky * 3 + kx < 27 = the scaled
+ * value ((2x - 1) - shift[ci]) / scale[ci] at pixel (y + ky - 1, x + kx - 1), 0 outside the image; channels 27 .. 63 are 0.  shift_scale = fp32
+ * {shift[3], scale[3]} on the device.  Any H, W. */
+int mb_lpips_input(const float* real, const float* fake, const float* shift_scale, void* out_h16, int B, int H, int W, int clamp01, mb_stream stream);
+/* The distance kernel and its finalize alone: feat_a / feat_b fp16 [B, HW, C], C in {64, 128, 256, 512}, w fp32 [C] ->
+ * per_image double [B] = mean over the pixels of sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2.  Synchronises the stream. */
+int mb_lpips_distance(const void* feat_a, const void* feat_b, const float* w, int B, int HW, int C, double* per_image, mb_stream stream);
+/* The five taps of a forward (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3) as fp16 NHWC [2B, H / 2^k, W / 2^k, {64, 128, 256, 512, 512}], real
+ * images first; arguments as for the forward. */
+int mb_lpips_features(mb_lpips* h, const float* real, const float* fake, int B, int H, int W, int clamp01, void* tap0, void* tap1, void* tap2, void* tap3,
+                      void* tap4, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

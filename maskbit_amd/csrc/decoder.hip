@@ -50,7 +50,8 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // a barrier and the LDS-DMA of its weight tile: per step 3 500 clocks for 512 clocks of matrix work.  A 16 x 16 tile on 8 waves keeps two
 // workgroups per CU (74 KiB each) but FOUR waves per SIMD at the same 125 VGPRs, stages each weight tile for twice the pixels and shrinks the
 // halo overhead from 1.41 to 1.27 pixels read per pixel written.
-template <int NI, int WN, int KS, bool UP, bool FINAL, int TH = 8>
+// RELU (the VGG16 stack of lpips.hip): max(v, 0) after bias, before the fp16 store.  Off by default: every instantiation without it compiles to the code it had.
+template <int NI, int WN, int KS, bool UP, bool FINAL, int TH = 8, bool RELU = false>
 __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
   constexpr int NTHR = 32 * TH, NWAVE = NTHR / 64;
   constexpr int WM = NWAVE / WN, MJ = TH / WM, BN = WN * NI * 16;
@@ -245,6 +246,7 @@ __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
               const h16x4 r = rv[j & 1][i];
               v[0] += (float)r[0]; v[1] += (float)r[1]; v[2] += (float)r[2]; v[3] += (float)r[3];
             }
+            if constexpr (RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             // activations are stored as fp16: values beyond +-65504 are clamped by to_h -- counted, so that a checkpoint whose decoder needs a
             // wider residual stream is noticed instead of silently clipped (random-init weights stay far inside the range)
             nsat += fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) > MB_H16_MAX ? 1u : 0u;
@@ -431,6 +433,22 @@ __global__ void avgpool2_kernel(const h16* __restrict__ x, h16* __restrict__ y, 
     *(h16x8*)(y + ((b * Ho + Y) * Wo + X) * C + sl * 8) = o;
   }
 }
+// F.max_pool2d(kernel 2, stride 2) (the VGG16 stack of lpips.hip): x[B,H,W,C] -> y[B,H/2,W/2,C]; the maximum of fp16 values is exact
+__global__ void maxpool2_kernel(const h16* __restrict__ x, h16* __restrict__ y, int B, int H, int W, int C) {
+  const int c8 = C / 8, Ho = H / 2, Wo = W / 2;
+  const size_t total = (size_t)B * Ho * Wo * c8;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int sl = (int)(i % c8); size_t p = i / c8;
+    const int X = (int)(p % Wo); p /= Wo; const int Y = (int)(p % Ho); const size_t b = p / Ho;
+    const h16* src = x + ((b * H + 2 * Y) * W + 2 * X) * C + sl * 8;
+    const h16x8 v00 = *(const h16x8*)src, v01 = *(const h16x8*)(src + C), v10 = *(const h16x8*)(src + (size_t)W * C),
+                v11 = *(const h16x8*)(src + (size_t)W * C + C);
+    h16x8 o;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = (h16)fmaxf(fmaxf((float)v00[c], (float)v01[c]), fmaxf((float)v10[c], (float)v11[c]));
+    *(h16x8*)(y + ((b * Ho + Y) * Wo + X) * C + sl * 8) = o;
+  }
+}
 // OIHW 3x3 stride-2 weights -> [tap (by,bx)][Cout_pad][4*Cin] for the 2x2 conv on the space-to-depth input:
 // tap (by,bx), channel (py*2+px)*Cin + ci  <-  w[co][ci][2by+py][2bx+px] (zero where that index is 3)
 __global__ void repack_down_kernel(const float* __restrict__ w, h16* __restrict__ out, int Cout, int Cin, int Cout_pad) {
@@ -597,6 +615,27 @@ void launch_conv(hipStream_t s, GnCtx* gc, const Conv& c, const h16* in, const f
   else hipLaunchKernelGGL((conv_kernel<4, 2, 3, false, false>), grid, block, 0, s, a);
 }
 
+}  // namespace
+
+// ---- what lpips.hip uses (mb_decoder.h): conv + bias + ReLU without GroupNorm prologue or partials, max-pool, weight repack ----
+void launch_conv_relu(hipStream_t s, const ConvRelu& q) {
+  ConvArgs a{(const h16*)q.in, nullptr, (const h16*)q.w, q.bias, nullptr, (h16*)q.out, nullptr, nullptr, q.B, q.H, q.W, q.cin_pad, q.cout, q.cout_pad, q.sat, nullptr};
+  const bool th16 = q.ks == 3 && q.H % 16 == 0 && q.H >= 32;          // launch_conv's rule: per image, never per batch
+  const int th = th16 ? 16 : TH8;
+  dim3 grid((unsigned)((size_t)q.B * (q.H / th) * (q.W / TW) * (q.cout_pad / 128))), block(32 * th);
+  if (q.ks == 1) hipLaunchKernelGGL((conv_kernel<4, 2, 1, false, false, 8, true>), grid, block, 0, s, a);
+  else if (th16) hipLaunchKernelGGL((conv_kernel<4, 2, 3, false, false, 16, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((conv_kernel<4, 2, 3, false, false, 8, true>), grid, block, 0, s, a);
+}
+void launch_maxpool2(hipStream_t s, const void* x, void* y, int B, int H, int W, int C) {
+  const size_t n8 = (size_t)B * H * W * (C / 8);
+  hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 / 4 + 255) / 256)), dim3(256), 0, s, (const h16*)x, (h16*)y, B, H, W, C);
+}
+void launch_repack_conv(hipStream_t s, const float* w_oihw, void* out, int cout, int cin, int ks, int cout_pad, int cin_pad) {
+  hipLaunchKernelGGL(repack_conv_kernel, dim3(512), dim3(256), 0, s, w_oihw, (h16*)out, cout, cin, ks, cout_pad, cin_pad);
+}
+
+namespace {
 void launch_gn(hipStream_t s, GnCtx* gc, const Norm& n, const h16* x, int B, int HW) {
   int nchunk = gc->ntile;
   if (gc->of != (const void*)x) {                   // not the tensor the last conv summed (average-pooled tensors of the encoder): sweep it
@@ -716,6 +755,41 @@ int diag_groupnorm(const void* x, const float* gamma, const float* beta, float* 
   launch_gn(s, &gc, n, (const h16*)x, B, HW);      // gc.of is null: the sweep (gn_partial_kernel) + gn_finalize_kernel
   if (hipMemcpyAsync(scale_shift, gc.ss, (size_t)B * C * sizeof(float2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) return fail(-10, "mb_groupnorm_stats: copy failed");
+  return 0;
+}
+
+int diag_maxpool(const void* x, void* y, int B, int H, int W, int C, hipStream_t s) {
+  if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8) return fail(-1, "mb_maxpool2: H and W must be even, C a multiple of 8");
+  launch_maxpool2(s, x, y, B, H, W, C);
+  return 0;
+}
+
+int diag_conv_relu(const void* in, const float* w, const float* bias, void* out, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, hipStream_t s) {
+  if (!in || !w || !out || B <= 0 || Cin <= 0 || Cout <= 0) return fail(-1, "mb_conv_relu_layer: null or empty argument");
+  if (ks != 1 && ks != 3) return fail(-1, "mb_conv_relu_layer: ks must be 1 or 3");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_conv_relu_layer: the output must be whole 8 x 16 pixel tiles");
+  if (Cout % 4) return fail(-1, "mb_conv_relu_layer: Cout must be a multiple of 4");
+  Conv c;
+  shape_conv(c, Cin, Cout, ks, true, false, false);
+  Scratch m;
+  const size_t npix = (size_t)B * H * W;
+  h16* staged = nullptr;
+  if (!m.get(&c.w, conv_weight_elems(c)) || !m.get(&c.b, (size_t)c.cout_pad) || !m.get(&c.sat, 1)) return fail(-10, "mb_conv_relu_layer: hipMalloc failed");
+  bool ok = hipMemsetAsync(c.b, 0, c.cout_pad * sizeof(float), s) == hipSuccess && hipMemsetAsync(c.sat, 0, sizeof(unsigned), s) == hipSuccess;
+  if (ok && bias) ok = hipMemcpyAsync(c.b, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  repack_weights(s, c, w);
+  if (c.cin_pad != Cin) {                           // channels padded with zeros to a whole chunk
+    if (!m.get(&staged, npix * c.cin_pad)) return fail(-10, "mb_conv_relu_layer: hipMalloc failed");
+    ok = ok && hipMemsetAsync(staged, 0, npix * c.cin_pad * sizeof(h16), s) == hipSuccess &&
+         hipMemcpy2DAsync(staged, c.cin_pad * sizeof(h16), in, Cin * sizeof(h16), Cin * sizeof(h16), npix, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    in = staged;
+  }
+  if (!ok) return fail(-10, "mb_conv_relu_layer: copy failed");
+  launch_conv_relu(s, ConvRelu{in, c.w, c.b, out, c.sat, B, H, W, c.cin_pad, c.cout, c.cout_pad, ks});
+  unsigned nsat = 0;
+  ok = hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_conv_relu_layer: copy failed");
+  if (saturated) *saturated = nsat;
   return 0;
 }
 

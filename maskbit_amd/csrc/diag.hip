@@ -169,4 +169,16 @@ int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta,
 int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", true, x_h16, y_h16, B, H, W, C, stream); }
 int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", false, x_h16, y_h16, B, H, W, C, stream); }
 
+// ---- the pieces of the LPIPS forward (mb_lpips_input / _distance / _features need lpips.hip's kernels and handle and are defined there) ----
+int mb_conv_relu_layer(const void* in_h16, const float* w_oihw, const float* bias, void* out_h16, unsigned* saturated, int B, int H, int W, int Cin,
+                       int Cout, int ks, mb_stream stream) {
+  if (int rc = mb::diag_conv_relu(in_h16, w_oihw, bias, out_h16, saturated, B, H, W, Cin, Cout, ks, (hipStream_t)stream)) return rc;
+  return launched();
+}
+int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) {
+  if (!x_h16 || !y_h16) return fail(-1, "mb_maxpool2: null argument");
+  if (int rc = mb::diag_maxpool(x_h16, y_h16, B, H, W, C, (hipStream_t)stream)) return rc;
+  return launched();
+}
+
 }  // extern "C"

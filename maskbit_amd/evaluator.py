@@ -8,7 +8,10 @@ metrics, then a small deterministic finalize) and one for the indices (``mb_eval
 calls and a ``.tolist()`` into a Python set); it enqueues on the current stream and never synchronises.  The running state -- four float64
 sums, an int64 histogram, an out-of-range counter -- stays on the device; ``result()`` makes one device-to-host copy.
 
-The network metrics (rFID, Inception score, LPIPS) are not built: they raise at construction.  There is no CPU path.
+rFID and the Inception score are not built: they raise at construction, and so does ``enable_lpips_score`` -- that flag means "build LPIPS
+with downloaded weights", which cannot be honoured here.  LPIPS itself is built (``maskbit_amd.LPIPS``, csrc/lpips.hip): attach a model that
+holds the user's weights with ``use_lpips(model)`` and ``update()`` also enqueues ``mb_lpips_forward`` on the same images into a float64 device
+sum; ``result()`` reports ``"LPIPS"`` where the reference does.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -41,7 +44,9 @@ class TokenizerEvaluator:
                 raise NotImplementedError(
                     f"{name}: rFID, Inception score and LPIPS need the Inception / LPIPS networks and their weights, which are out of scope here "
                     "(SURVEY.md section 2). Run them with the reference's own evaluator beside this one (evaluator.TokenizerEvaluator with only "
-                    "those flags set; both take the same update() arguments).")
+                    "those flags set; both take the same update() arguments)."
+                    + (" LPIPS itself runs here with your own weights: build a maskbit_amd.LPIPS, load it (load_vgg16, load_linear) and attach it "
+                       "with TokenizerEvaluator.use_lpips(model)." if name == "enable_lpips_score" else ""))
         self._device = torch.device(device)
         if self._device.type != "cuda":
             raise RuntimeError(f"TokenizerEvaluator runs only on an AMD GPU through libmaskbit_hip.so (device is {self._device}); "
@@ -63,6 +68,9 @@ class TokenizerEvaluator:
         self._hist: Optional[torch.Tensor] = None
         self._out_of_range: Optional[torch.Tensor] = None
         self.last_per_image: Optional[torch.Tensor] = None
+        self.last_lpips: Optional[torch.Tensor] = None
+        self._lpips = None
+        self._lpips_sum: Optional[torch.Tensor] = None
         if self._device.index is None:
             self._device = torch.device("cuda", torch.cuda.current_device())
         self.reset_metrics()
@@ -81,6 +89,27 @@ class TokenizerEvaluator:
             self._hist.zero_()
             self._out_of_range.zero_()
         self.last_per_image = None
+        self.last_lpips = None
+        if self._lpips_sum is not None:
+            self._lpips_sum.zero_()
+
+    def use_lpips(self, model) -> None:
+        """Attaches a loaded ``maskbit_amd.LPIPS`` on the evaluator's device (``None`` detaches): ``update()`` then also adds the batch's LPIPS
+        values to a float64 device sum (``last_lpips`` holds the batch's [B] values) and ``result()`` reports ``"LPIPS"``.  Takes the place of
+        the reference's ``enable_lpips_score`` (evaluator.py:223-226,366-368,453-455), whose weights cannot be fetched here.  Attach before the
+        first ``update()`` of a pass, or call ``reset_metrics()``: the mean is over all examples counted."""
+        if model is None:
+            self._lpips = None
+            return
+        from .lpips import LPIPS
+        if not isinstance(model, LPIPS):
+            raise TypeError(f"use_lpips() takes a maskbit_amd.LPIPS, got {type(model).__name__}")
+        dev = model._require_cuda("use_lpips")
+        if (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device.index:
+            raise ValueError(f"the LPIPS model is on {dev}, the evaluator on {self._device}")
+        self._lpips = model
+        if self._lpips_sum is None:
+            self._lpips_sum = torch.zeros(1, dtype=torch.float64, device=self._device)
 
     def update(self, real_images: torch.Tensor, fake_images: torch.Tensor, codebook_indices: Optional[torch.Tensor] = None, clamp: bool = False):
         """Adds a batch.  ``real_images`` / ``fake_images``: [B, C, H, W] of any float dtype (cast to contiguous fp32 only when needed), equal
@@ -103,6 +132,8 @@ class TokenizerEvaluator:
             raise ValueError("codebook_indices is required when a codebook metric is enabled")
         if self._codebook and (codebook_indices.is_floating_point() or codebook_indices.is_complex()):
             raise ValueError(f"codebook_indices must be an integer tensor, got {codebook_indices.dtype}")
+        if self._lpips is not None:
+            self._lpips.check_images(tuple(fake_images.shape), tuple(fake_images.shape))      # sizes the engine does not take: ValueError, no device work
         lib = _lib.load()
         need = int(lib.mb_eval_workspace_bytes(B, C, H, W)) if self._metrics else 0
         if self._metrics and need == 0:
@@ -120,6 +151,8 @@ class TokenizerEvaluator:
                 _lib.check(lib.mb_eval_images(real.data_ptr(), fake.data_ptr(), B, C, H, W, self._metrics, 1 if clamp else 0,
                                               self._workspace.data_ptr(), per_image.data_ptr(), self._sums.data_ptr(), stream), "mb_eval_images")
                 self.last_per_image = per_image
+            if self._lpips is not None:                                                          # evaluator.py:366-368
+                self.last_lpips = self._lpips._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._lpips_sum)
             if self._codebook:
                 idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
                 _lib.check(lib.mb_eval_codebook(idx.data_ptr(), idx.numel(), self._num_codebook_entries, self._hist.data_ptr(),
@@ -133,14 +166,18 @@ class TokenizerEvaluator:
             raise ValueError("No examples to evaluate.")
         entropy = None
         parts = [self._sums]
+        lp = self._lpips is not None
+        if lp:
+            parts.append(self._lpips_sum)
+        cb = 5 if lp else 4                                                                      # position of the codebook figures
         if self._codebook:
             counts = self._hist.double()
             probs = counts / counts.sum()
             entropy = (-torch.log2(probs + 1e-8) * probs).sum()                                # evaluator.py:462-463
             parts += [(self._hist != 0).sum().double().reshape(1), (self._out_of_range.long() & 0xFFFFFFFF).double()]
         host = torch.cat(parts).cpu()                                                           # the one copy
-        if self._codebook and host[5] != 0:
-            raise IndexError(f"{int(host[5])} codebook indices outside [0, {self._num_codebook_entries})")
+        if self._codebook and host[cb + 1] != 0:
+            raise IndexError(f"{int(host[cb + 1])} codebook indices outside [0, {self._num_codebook_entries})")
         eval_score = {}
         n = self._num_examples
         if self._enable_mae_error:
@@ -151,8 +188,10 @@ class TokenizerEvaluator:
             eval_score["PSNR"] = host[2].item() / n
         if self._enable_ssim_score:
             eval_score["SSIM"] = host[3].item() / n
+        if lp:
+            eval_score["LPIPS"] = host[4].item() / n                                            # evaluator.py:453-455
         if self._enable_codebook_usage_measure:
-            eval_score["CodebookUsage"] = float(int(host[4])) / self._num_codebook_entries
+            eval_score["CodebookUsage"] = float(int(host[cb])) / self._num_codebook_entries
         if self._enable_codebook_entropy_measure:
             eval_score["CodebookEntropy"] = entropy
         return eval_score

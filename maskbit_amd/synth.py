@@ -323,3 +323,35 @@ def make_mlm_case(b: int, n: int, m: int, C: int, seed: int) -> Tuple[Tensor, Te
 def make_mlm_tokens(b: int, n: int, m: int, C: int, seed: int) -> Tensor:
     """Seeded int64 tokens [b, n, m] in [0, C) for the masking fixtures."""
     return torch.randint(0, C, (b, n, m), generator=torch.Generator().manual_seed(seed))
+
+
+VGG16_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
+               (17, 256, 512), (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512))   # (features index, Cin, Cout)
+VGG16_GROWN_GAIN = 1.45
+
+
+def make_vgg16_weights(seed: int, style: str = "he") -> StateDict:
+    """Seeded weights of torchvision's VGG16-D ``features`` stack (thirteen 3x3 convolutions with bias) under bare ``N.weight`` / ``N.bias`` keys,
+    as ``nn.Sequential.load_state_dict`` and ``LPIPS.load_vgg16`` take them.  ImageNet VGG16 is not available here; these stand in for it.
+
+    ``"he"``: He-normal weights (std = sqrt(2 / fan_in)), bias N(0, 0.05): activations stay O(1) through the stack.  On
+    ``make_eval_images("noise", ...)`` inputs of 256 x 256 the five taps (relu1_2 .. relu5_3) have rms 1.4 / 2.4 / 3.2 / 3.1 / 3.0 and maxima
+    10 / 13 / 18 / 18 / 14 (seed 4100; on the ``"bright"`` family 1.7 / 1.8 / 1.8 / 1.3 / 0.7).
+    (The ``"kaiming"`` uniform init of the model classes would shrink activations about 0.4 x per layer into fp16 subnormals.)
+
+    ``"grown"``: the same draws with every layer's weights times 1.45 and its bias times the accumulated gain, so the activations grow as those
+    of ImageNet VGG16 do (unnormalised, large at the deep taps): tap rms 2.9 / 11 / 43 / 128 / 371, maxima 20 / 66 / 236 / 781 / 1 860 on the
+    same inputs -- what the fp16 range and the saturation counter have to see."""
+    if style not in ("he", "grown"):
+        raise ValueError(f"unknown VGG16 weight style {style!r}")
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+    gain = 1.0
+    for idx, cin, cout in VGG16_CONVS:
+        w = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cin * 9))
+        b = torch.randn(cout, generator=g) * 0.05
+        if style == "grown":
+            gain *= VGG16_GROWN_GAIN
+            w, b = w * VGG16_GROWN_GAIN, b * gain
+        sd[f"{idx}.weight"], sd[f"{idx}.bias"] = w.contiguous(), b.contiguous()
+    return sd
