@@ -77,6 +77,9 @@ int mb_gen_set_alo(mb_gen* g, int gemm_mask);
 /* Persistent kernels launch one workgroup per CU.  On a stream created with a CU mask (hipExtStreamCreateWithCUMask) fewer CUs serve the launch:
  * n = the CUs the following launches should size their grids for, 0 = the device's count (default).  Process-wide, not thread-safe. */
 int mb_set_cu_count(int n);
+/* Host only: 1 if the half-tile kernel (gemm_ht.hip) takes a plain M x N x K GEMM with this epilogue, 0 if the launcher falls back to the 128 x 128
+ * kernel -- among other rules, the kernel's 32-bit byte offsets need M * K * 2 and N * K * 2 below 2^32. */
+int mb_gemm_ht_supported(int epi, int M, int N, int K);
 
 /* The lookup quantizer's search on caller buffers (vq.hip): z fp32 [N, K], codebook fp32 [C, K] (K <= 256, 2 <= C <= 65 536), l2 = normalise both;
  * idx int64 [N] = argmin_j ||z - e_j||^2 (ties to the lowest index), dist fp32 [N] (may be NULL) = that squared distance; splits = codebook splits

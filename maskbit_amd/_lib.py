@@ -112,6 +112,7 @@ SIGNATURES = {
     "mb_lpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mb_lpips_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "mb_set_cu_count": (C.c_int, [C.c_int]),
+    "mb_gemm_ht_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mb_prof_enable": (C.c_int, [C.c_int]),
     "mb_prof_read": (C.c_int, [C.c_char_p, C.c_int]),
 }

@@ -40,6 +40,10 @@ int pool_entry(const char* what, bool avg, const void* x, void* y, int B, int H,
 extern "C" {
 
 int mb_set_cu_count(int n) { mb::set_cu_count(n); return 0; }
+int mb_gemm_ht_supported(int epi, int M, int N, int K) {
+  mb::GemmArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, K, 0};
+  return mb::gemm_ht_supported((mb::GemmEpi)epi, a) ? 1 : 0;
+}
 
 // ---- one GEMM of the trunk family on caller buffers (tests and tools/gemm_bench.py) ----
 int mb_gemm(int epi, const void* A, const void* W, const float* bias, const float* residual, float* out_f32, void* out_h16,

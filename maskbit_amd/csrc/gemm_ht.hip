@@ -91,7 +91,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   // Every instance walks the tile list persistently (round 1 kept the fp32+residual epilogue at one tile per workgroup: it spilled
   // VGPRs inside the K loop then; with the present epilogue it does not: 244-248 VGPRs, no scratch).
   constexpr bool PERSIST = true;
-  constexpr int AUX = 0;   // DMA cache policy: default beats nt (-14 %) and sc1 (-6 %) here, sc0 is equal (measured)
+  // (DMA cache policy: the default beats nt (-14 %) and sc1 (-6 %) here, sc0 is equal -- measured)
   constexpr int BM = 32 * MT, MH = MT / 2;
   constexpr int AH_ROWS = BM / 2;
   constexpr int AH_BYTES = AH_ROWS * 128, BH_BYTES = 128 * 128;
@@ -107,10 +107,12 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   const int wm = wave >> 2, wn = wave & 3;
   const int l15 = lane & 15, g = lane >> 4;
   const int K = a.K, nk = K / 64;
-  const int KA = a.kw ? a.kw : K, nka = KA / 64;       // split activations: A and A2 have kw = K/2 columns each
-  const int KW = a.kw ? a.kw : K, nkw = KW / 64;       // split activations: W has K/2 columns and is swept twice, A2 (lo halves) takes over from A
+  // (split activations exist for plain forwards only -- gemm_ht_supported refuses them on pair tiles -- so the pair kernels resolve them at compile time)
+  constexpr bool SPLIT = !PAIR;
+  const int KA = SPLIT && a.kw ? a.kw : K, nka = KA / 64;       // split activations: A and A2 have kw = K/2 columns each
+  const int KW = SPLIT && a.kw ? a.kw : K, nkw = KW / 64;       // split activations: W has K/2 columns and is swept twice, A2 (lo halves) takes over from A
   // split activations (A2 / kw): K-tiles >= nka read the lo halves A2 against the same W columns
-  const h16* const Alo = a.A2 ? a.A2 : a.A;
+  const h16* const Alo = SPLIT && a.A2 ? a.A2 : a.A;
   const h16* const Wlo = a.W;
   // sequence tiles: SQ rows per sequence (class token last), TPS tiles per sequence (pair) -- a power of two: (SQ - 1) / 128 pair tiles (2 or 8) of 2 groups
   // of 64 tokens, (SQ - 1) / 256 plain tiles (1 or 4) of 4 groups; the LAST tile of a sequence computes and stores the class-token row(s)
@@ -120,8 +122,12 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   const int ntiles = tiles_m * tiles_n;
 
   // ---- per-tile DMA plan of this wave: 2 instructions per half-tile; lane -> (row 8j + lane>>3, slot lane&7)
+  // Addressing rule of the whole operand stream: a DMA address is a wave-uniform 64-bit BASE (operand pointer + the K-tile's / mini-tile's byte
+  // offset, kept in an SGPR pair and moved by scalar adds) plus a per-lane 32-bit BYTE offset of the plan -- the scalar-base form of
+  // global_load_lds, no 64-bit VALU arithmetic in front of it.  The byte offsets fit 32 bits because gemm_ht_supported refuses every shape with
+  // M * K * 2 or N * K * 2 >= 2^32 (the engine's chunking rule, rows * mlp * 4 < 2^32, is the tighter one for the trunk).
   struct Plan {
-    uint32_t offA[2][2], offB[2][2], offX;   // element offsets into A / W
+    uint32_t offA[2][2], offB[2][2], offX;   // BYTE offsets into A / W (row * row bytes + swizzled 16-byte slot)
     int m0, n0;
     int cls;                                 // SEQ: the (conditional) class-token row of this tile's sequence (pair); its last tile stores it
     int q;                                   // SEQ: which 256-token (pair: 128-token) part of the sequence this tile covers
@@ -155,32 +161,36 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int gm = PAIR ? p.m0 + h * a.pair_rows + hra : min(p.m0 + wms * (16 * MT) + h * (8 * MT) + r, a.M - 1);
-        p.offA[h][j] = (uint32_t)gm * (uint32_t)KA + slot_a * 8;
+        p.offA[h][j] = (uint32_t)gm * (uint32_t)(2 * KA) + slot_a * 16;
         const int gn = min(p.n0 + wns * 64 + (HN ? p.hb * (64 / NS) : h * 32) + c, a.N - 1);
-        p.offB[h][j] = (uint32_t)gn * (uint32_t)KW + slot_b * 8;
+        p.offB[h][j] = (uint32_t)gn * (uint32_t)(2 * KW) + slot_b * 16;
       }
     }
     // X: the class-token row of this sequence, 8 identical source rows (only LDS row 0 is ever consumed)
-    p.offX = (uint32_t)(PAIR ? p.cls + ((lane_o >> 3) == 1 ? a.pair_rows : 0) : min(p.cls, a.M - 1)) * (uint32_t)KA + ((lane_o & 7) ^ MB_SWZ(lane_o >> 3)) * 8;
+    p.offX = (uint32_t)(PAIR ? p.cls + ((lane_o >> 3) == 1 ? a.pair_rows : 0) : min(p.cls, a.M - 1)) * (uint32_t)(2 * KA) + ((lane_o & 7) ^ MB_SWZ(lane_o >> 3)) * 16;
   };
-  auto dma_x = [&](const Plan& p, int t) {
-    if (SEQ && wave == 7) MB_GLDS16_AUX((t < nka ? a.A : Alo) + p.offX + (t < nka ? t : t - nka) * 64, smem + (t & 1) * PAR_BYTES + 2 * AH_BYTES + 2 * BH_BYTES, AUX);
+  // K-tile u of the A / W stream: the wave-uniform base (split activations, A2 / kw: K-tiles >= nka sweep the lo halves against the same W columns)
+  auto ktile_a = [&](int u) -> const char* { if constexpr (!SPLIT) return (const char*)a.A + u * 128; return (const char*)(u < nka ? a.A : Alo) + (u < nka ? u : u - nka) * 128; };
+  auto ktile_w = [&](int u) -> const char* { if constexpr (!SPLIT) return (const char*)a.W + u * 128; return (const char*)(u < nkw ? a.W : Wlo) + (u < nkw ? u : u - nkw) * 128; };
+  // (kp: the K-tile's base of that operand; parb: byte offset of the destination parity in LDS)
+  auto dma_x = [&](const Plan& p, const char* kp, int parb) {
+    if (SEQ && wave == 7) MB_GLDS16_SB(kp, p.offX, smem + parb + 2 * AH_BYTES + 2 * BH_BYTES);
   };
-  auto dma_a = [&](const Plan& p, int t, int h) {
-    char* buf = smem + (t & 1) * PAR_BYTES + h * AH_BYTES;
+  auto dma_a = [&](const Plan& p, const char* kp, int parb, int h) {
+    char* buf = smem + parb + h * AH_BYTES;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       // (a "compressed" plan -- one per-lane offset + uniform row steps instead of this table of four, 6-11 VGPRs less -- measured 3.5 % slower in the
       // pair mini-tile kernels and equal in the plain ones, round 5: the address arithmetic lands in the [L] phases)
-      MB_GLDS16_AUX((t < nka ? a.A : Alo) + p.offA[h][j] + (t < nka ? t : t - nka) * 64, buf + dstA[j], AUX);
+      MB_GLDS16_SB2(kp, p.offA[h][j], buf, dstA[j]);
     }
   };
-  auto dma_b = [&](const Plan& p, int t, int h) {
+  auto dma_b = [&](const Plan& p, const char* kp, int parb, int h) {
     if (HN && h == 1) return;                          // half-column tiles stage one B half (in the B0 slot)
-    char* buf = smem + (t & 1) * PAR_BYTES + 2 * AH_BYTES + h * BH_BYTES;
+    char* buf = smem + parb + 2 * AH_BYTES + h * BH_BYTES;
 #pragma unroll
     for (int j = 0; j < (QN ? 1 : 2); ++j) {
-      MB_GLDS16_AUX((t < nkw ? a.W : Wlo) + p.offB[h][j] + (t < nkw ? t : t - nkw) * 64, buf + dstB[j], AUX);
+      MB_GLDS16_SB2(kp, p.offB[h][j], buf, dstB[j]);
     }
   };
   // ---- mini-tiles (XP = 6).  nmk per operand set / row half; mini j: set or half ps = j / nmk, K-elements [128 jj, 128 jj + 128), jj = j % nmk.
@@ -189,65 +199,97 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   // choice, (row >> 2) & 3, read at half of it: SQ_LDS_BANK_CONFLICT 4.2 M cycles per FFN-up launch); the per-lane part of the address is the same
   // for both operands.
   // (KM: the K extent of the operands = of the corrections; with split activations -- A2 / kw, plain tiles -- the fp16 sweep is twice as long)
-  const int KM = a.kw ? a.kw : K;
+  const int KM = SPLIT && a.kw ? a.kw : K;
   const int nmk = KM / 128;
   const int nseq = PAIR ? a.pair_rows / SQ : a.M / SQ;
   const int grp_bytes = PAIR ? TPS * 128 : TPS * 256;    // scale bytes per (64-column block, sequence): 64 per 64-token group
   const bool mini_every = MINI && (PAIR ? a.nlo == 2 : !a.kw);   // one mini-tile per fp16 K-tile (else one per two)
-  auto mini_lane = [&]() -> uint32_t {
-    int lo_ = lane; asm volatile("" : "+v"(lo_));
-    return (uint32_t)((lo_ >> 2) * 2 * KM + (((lo_ & 3) ^ ((lo_ >> 3) & 3)) * 16));
+  // Mini-tile addressing follows the same rule (see Plan).  The per-lane byte offsets do not depend on the tile or the mini-tile; the wave-uniform
+  // bases of the NEXT mini-tile to issue are carried in SGPR pairs (MiniPos): set per tile and operand set / row half, moved by scalar adds per mini-tile.
+  struct MiniPos { const uint8_t *a4, *w4, *xs, *ws; };
+  const uint32_t ml_a = (uint32_t)((lane >> 2) * 2 * KM + (((lane & 3) ^ ((lane >> 3) & 3)) * 16));   // token operand: row lane >> 2, swizzled 16-byte chunk
+  // (the two cheap ones -- the weight operand's lane * 16: 1 KiB of contiguous memory per instruction, w4_packed_offset; and the weight scale's --
+  // are re-derived from an opaque copy of the lane id where they are used, 2 - 3 VALU operations each: as residents they cost the VGPRs that spill)
+  auto ml_w = [&]() -> uint32_t { int lo_ = lane; asm volatile("" : "+v"(lo_)); return (uint32_t)lo_ * 16; };
+  // the token operand's scale dword of this lane: its four m-tiles' bytes of block 2 jj + (lane >= 32) (GemmArgs.lo: lane order)
+  const uint32_t ml_xs = (uint32_t)(lane >> 5) * (uint32_t)nseq * (uint32_t)grp_bytes + (lane & 15) * 4;
+  // the weight operand's scale dword of this lane: the bytes of its four n-tiles for K-elements [128 jj, 128 jj + 128) (w4_scale_index; one scale
+  // per (weight row, mini-tile) since round 6 -- rounds 2-5 held one dword per operand set for the whole K loop)
+  auto ml_ws = [&]() -> uint32_t { int lo_ = lane; asm volatile("" : "+v"(lo_)); return (uint32_t)(lo_ & 15) * 4; };
+  auto mini_pos = [&](const Plan& p) -> MiniPos {          // mini-tile 0 of a tile
+    constexpr int si = 0, ps = 0;
+    const int m0 = p.m0, n0 = p.n0, hb = p.hb, tq = p.q, sq = p.seq;     // (wave-uniform: functions of the tile index)
+    const uint32_t row0 = PAIR ? m0 + wave * 16 : m0 + (wave >> 2) * 128 + ps * 64 + (wave & 3) * 16;
+    // weight rows of this wave's (first) instruction: 16 per instruction; column-split tiles stage block hb of every wave column only
+    const uint32_t wrow = QN ? wave * 4 + hb : HN ? (wave >> 1) * 4 + hb * 2 + (wave & 1) : wave;
+    const uint32_t gq = PAIR ? tq * 2 + wm : tq * 4 + wm * 2 + ps;
+    MiniPos m;
+    m.a4 = a.lo[si].A4 + (size_t)row0 * 2 * KM;
+    m.w4 = a.lo[si].W4 + (size_t)((n0 >> 4) + wrow) * nmk * 1024;
+    m.xs = a.lo[si].a_scale + ((uint32_t)sq * (uint32_t)grp_bytes + gq * 64);
+    m.ws = a.lo[si].w_scale + (uint32_t)(((n0 >> 6) + wn) * nmk) * 64;
+    // (functions of the tile index: wave-uniform.  Said explicitly, so that the bases live in SGPRs whatever the compiler proves about the plan)
+    auto uni = [](const uint8_t* q) -> const uint8_t* {
+      const uint64_t v = (uint64_t)q;
+      return (const uint8_t*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
+    };
+    m.a4 = uni(m.a4); m.w4 = uni(m.w4); m.xs = uni(m.xs); m.ws = uni(m.ws);
+    return m;
   };
-  auto mini_dma_a = [&](const Plan& p, int j) {          // 1 instruction per wave
-    const int ps = j >= nmk ? 1 : 0, jj = j - ps * nmk;
-    const uint8_t* base = a.lo[PAIR ? ps : 0].A4;
-    const uint32_t row0 = PAIR ? p.m0 + wave * 16 : p.m0 + (wave >> 2) * 128 + ps * 64 + (wave & 3) * 16;
-    MB_GLDS16_AUX(base + (size_t)row0 * 2 * KM + jj * 64 + mini_lane(), smem + MINI_OFF + wave * 1024, AUX);
+  const uint32_t xs_step = 2u * (uint32_t)nseq * (uint32_t)grp_bytes;
+  auto mini_step = [&](MiniPos& m) { m.a4 += 64; m.w4 += 1024; m.xs += xs_step; m.ws += 64; };
+  // Mini-tile nmk of a tile starts over at K-element 0: of the second operand set (pair tiles) or of the tile's second 64 rows per wave row (plain
+  // tiles).  A move of the carried bases as well -- back by the nmk steps taken, on by the distance between the sets / the row halves.  The pair
+  // kernels read the eight set pointers from the kernel arguments HERE (scalar loads through an opaque copy of the argument pointer), once per tile:
+  // as residents of the K loop they are 16 SGPRs the loop does not have.
+  auto mini_switch = [&](MiniPos& m) {
+    const size_t back = (size_t)nmk;
+    if constexpr (PAIR) {
+      auto ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();   // (GemmArgs is the kernel's first argument)
+      asm volatile("" : "+s"(ka));
+      auto l = (const GemmArgs::LoSet __attribute__((address_space(4)))*)(ka + offsetof(GemmArgs, lo));
+      m.a4 += ((uintptr_t)l[1].A4 - (uintptr_t)l[0].A4) - back * 64;
+      m.w4 += ((uintptr_t)l[1].W4 - (uintptr_t)l[0].W4) - back * 1024;
+      m.xs += ((uintptr_t)l[1].a_scale - (uintptr_t)l[0].a_scale) - back * xs_step;
+      m.ws += ((uintptr_t)l[1].w_scale - (uintptr_t)l[0].w_scale) - back * 64;
+    } else {
+      m.a4 += (size_t)64 * 2 * KM - back * 64;         // token rows + 64
+      m.w4 -= back * 1024;
+      m.xs += 64 - back * xs_step;                       // the next 64-token group's scale bytes
+      m.ws -= back * 64;
+    }
   };
-  auto mini_dma_b = [&](const Plan& p, int j) {          // 2 instructions per wave, 1 KiB of contiguous memory each (w4_packed_offset)
-    const int ps = j >= nmk ? 1 : 0, jj = j - ps * nmk;
-    const uint8_t* base = a.lo[PAIR ? ps : 0].W4;
-    int lo_ = lane; asm volatile("" : "+v"(lo_));
+  auto mini_dma_a = [&](const MiniPos& m) {              // 1 instruction per wave: 16 rows x 64 B
+    MB_GLDS16_SB(m.a4, ml_a, smem + MINI_OFF + wave * 1024);
+  };
+  auto mini_dma_b = [&](const MiniPos& m) {              // 2 instructions per wave
     if constexpr (QN) {                                  // 64 weight rows: waves 0..3 stage the 16 rows of block hb of wave column w
-      if (wave < 4) MB_GLDS16_AUX(base + ((size_t)((p.n0 >> 4) + wave * 4 + p.hb) * nmk + jj) * 1024 + lo_ * 16, smem + MINI_OFF + MINI_A + wave * 1024, AUX);
+      if (wave < 4) MB_GLDS16_SB(m.w4, ml_w(), smem + MINI_OFF + MINI_A + wave * 1024);
       return;
     }
     if constexpr (HN) {                                  // 128 weight rows: wave w stages rows [16 (w & 1), +16) of half hb of wave column w >> 1
-      MB_GLDS16_AUX(base + ((size_t)((p.n0 >> 4) + (wave >> 1) * 4 + p.hb * 2 + (wave & 1)) * nmk + jj) * 1024 + lo_ * 16, smem + MINI_OFF + MINI_A + wave * 1024, AUX);
+      MB_GLDS16_SB(m.w4, ml_w(), smem + MINI_OFF + MINI_A + wave * 1024);
       return;
     }
+    const uint32_t mlw = ml_w();
 #pragma unroll
     for (int jx = 0; jx < 2; ++jx)
-      MB_GLDS16_AUX(base + ((size_t)((p.n0 >> 4) + wave + 8 * jx) * nmk + jj) * 1024 + lo_ * 16, smem + MINI_OFF + MINI_A + (wave + 8 * jx) * 1024, AUX);
-  };
-  // the token operand's scale dword of this lane for mini j: its four m-tiles' bytes of block 2 jj + (lane >= 32) (GemmArgs.lo: lane order)
-  auto mini_scale_off = [&](const Plan& p, int j) -> uint32_t {
-    const int ps = j >= nmk ? 1 : 0, jj = j - ps * nmk;
-    const int gq = PAIR ? p.q * 2 + wm : p.q * 4 + wm * 2 + ps;
-    int lo_ = lane; asm volatile("" : "+v"(lo_));
-    if constexpr (!PAIR) return ((((uint32_t)(2 * jj + (lo_ >> 5)) * nseq + p.seq) << tps_sh) << 8) + gq * 64 + (lo_ & 15) * 4;   // (grp_bytes = 256 TPS)
-    return ((uint32_t)(2 * jj + (lo_ >> 5)) * nseq + p.seq) * grp_bytes + gq * 64 + (lo_ & 15) * 4;
-  };
-  // the weight operand's scale dword of this lane for mini j: the bytes of its four n-tiles for K-elements [128 jj, 128 jj + 128) (w4_scale_index; one scale
-  // per (weight row, mini-tile) since round 6 -- rounds 2-5 held one dword per operand set for the whole K loop)
-  auto mini_wscale_off = [&](const Plan& p, int j) -> uint32_t {
-    const int ps = j >= nmk ? 1 : 0, jj = j - ps * nmk;
-    int lo_ = lane; asm volatile("" : "+v"(lo_));
-    return (uint32_t)((((p.n0 >> 6) + wn) * nmk + jj) * 64 + (lo_ & 15) * 4);
+      MB_GLDS16_SB(m.w4 + (size_t)(8 * jx) * nmk * 1024, mlw, smem + MINI_OFF + MINI_A + (wave + 8 * jx) * 1024);
   };
   int mws = 0, mxs = 0;                                 // MINI: the current mini's weight / token scale dwords
-  auto mini_scale_issue = [&](const Plan& p, int j) {    // inline asm: counted by the K loop's own vmcnt wait, which the registers are tied through
-    const int ps = PAIR ? (j >= nmk ? 1 : 0) : 0;
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(mxs) : "v"(mini_scale_off(p, j)), "s"(a.lo[ps].a_scale) : "memory");
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(mws) : "v"(mini_wscale_off(p, j)), "s"(a.lo[ps].w_scale) : "memory");
+  auto mini_scale_issue = [&](const MiniPos& m) {        // inline asm: counted by the K loop's own vmcnt wait, which the registers are tied through
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(mxs) : "v"(ml_xs), "s"(m.xs) : "memory");
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(mws) : "v"(ml_ws()), "s"(m.ws) : "memory");
   };
   // all of K-tiles 0 and 1 of a tile (both LDS parities must be free)
   // (nk >= 2 is a precondition of this kernel: gemm_ht_supported)
   auto prologue_rest = [&](const Plan& p) {            // 16 instructions per wave
-    dma_a(p, 0, 0); dma_b(p, 0, 0); dma_b(p, 0, 1); dma_a(p, 0, 1);
-    dma_a(p, 1, 0); dma_b(p, 1, 1); dma_a(p, 1, 1); dma_b(p, 1, 0);
+    const char *a0 = ktile_a(0), *a1 = ktile_a(1), *w0 = ktile_w(0), *w1 = ktile_w(1);
+    dma_a(p, a0, 0, 0); dma_b(p, w0, 0, 0); dma_b(p, w0, 0, 1); dma_a(p, a0, 0, 1);
+    dma_a(p, a1, PAR_BYTES, 0); dma_b(p, w1, PAR_BYTES, 1); dma_a(p, a1, PAR_BYTES, 1); dma_b(p, w1, PAR_BYTES, 0);
   };
-  auto prologue = [&](const Plan& p) { dma_x(p, 0); dma_x(p, 1); prologue_rest(p); if constexpr (MINI) { mini_dma_a(p, 0); mini_dma_b(p, 0); } };
+  auto prologue_x = [&](const Plan& p) { dma_x(p, ktile_a(0), 0); dma_x(p, ktile_a(1), PAR_BYTES); };
+  auto prologue = [&](const Plan& p) { prologue_x(p); prologue_rest(p); if constexpr (MINI) { const MiniPos m0 = mini_pos(p); mini_dma_a(m0); mini_dma_b(m0); } };
 
   // ---- fragment read offsets inside a half-tile (rows 128 B, slot swizzled with (row>>1)&7)
   int foff[2], xoffe[2];
@@ -259,6 +301,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
     // A-fragment addresses instead of the X buffer -- 16 lanes on the 8 X rows was a 2-way bank conflict on every read
     xoffe[ks] = (l15 == 0 || (PAIR && l15 == 1)) ? 2 * AH_BYTES + 2 * BH_BYTES + foff[ks] : foff[ks];
   }
+  const int mfo = (lane & 15) * 64 + (((lane >> 4) ^ ((lane >> 1) & 3)) * 16);   // MINI: fragment read offset inside a 16-row block of 64-byte rows
   const int xbase = wm * (8 * MT) * 128;              // this wave's rows inside an A half-tile
   const int wbase = 2 * AH_BYTES + wn * 32 * 128;     // this wave's rows inside a B half-tile (from the parity base)
 
@@ -316,10 +359,9 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   int vb = blockIdx.x;
   make_plan(vb, cur);
   auto scales_load = [&](const Plan& p) {             // plain loads; scales_pack() after a vmcnt(0) that the loaded registers are tied through
-    int lo_ = lane; asm volatile("" : "+v"(lo_));
-    (void)lo_;
-    mws = *(const int*)(a.lo[0].w_scale + mini_wscale_off(p, 0));          // (mini 0 of a tile comes with the prologue)
-    mxs = *(const int*)(a.lo[0].a_scale + mini_scale_off(p, 0));
+    const MiniPos m0 = mini_pos(p);                                     // (mini 0 of a tile comes with the prologue)
+    mws = *(const int*)(m0.ws + ml_ws());
+    mxs = *(const int*)(m0.xs + ml_xs);
   };
   auto scales_pack = [&]() {
     if constexpr (MINI) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(mws), "+v"(mxs) :: "memory"); return; }
@@ -341,11 +383,13 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
     const bool cls_on = __builtin_amdgcn_readfirstlane(cur.q) == TPS - 1;
     h16x16 xa[MH], wb[2][2];      // wb[0] (the B0 fragments) is kept from phase 0 to phase 3: every operand fragment is read once per K-tile
 
+    MiniPos mp = {};
+    if constexpr (MINI) { mp = mini_pos(cur); mini_step(mp); }   // mini 0 came with the prologue: the next one to issue is mini 1
     if (grp == 1) __builtin_amdgcn_s_barrier();        // stagger: group 1 runs one barrier behind
 #define MB_KTILE MB_KTILE_(0)
 #define MB_KTILE_(MAH)              /* MAH: plain tiles with mini-tiles: the accumulator half this K loop's mini-tiles update (compile time) */ \
     {                                                                                                    \
-      const char* par = smem + (t & 1) * PAR_BYTES; \
+      const char* par = smem + parb; \
       int fo[2], xo[2]; \
       _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) { fo[ks] = foff[ks]; xo[ks] = xoffe[ks]; } \
       /* DMA issue is placed where the read phase is short (a global_load_lds blocks the issuing wave until the address unit takes */ \
@@ -363,22 +407,21 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       if constexpr (!HN) { MB_LOAD_B(1) } \
       if (!HN && SEQ && wm == 1 && cls_on) { xe = frag_set(xe, *(const h16x8*)(par + xo[0]), 0); xe = frag_set(xe, *(const h16x8*)(par + xo[1]), 1); } \
       /* MINI: the next mini-tile's scale dword and A part go out first (older than everything the phase-3 wait leaves in flight) */ \
-      const bool mini_issue = MINI && t >= 1 && (mini_every || !(t & 1)); \
-      const int mini_j = mini_every ? t : (t >> 1); \
-      if (MINI && mini_issue) { mini_scale_issue(cur, mini_j); mini_dma_a(cur, mini_j); } \
-      if (n1) dma_a(cur, t + 1, 1); \
+      const bool mini_issue = MINI && t >= 1 && mdue != 0; \
+      if (MINI && mini_issue) { if (mj == nmk) mini_switch(mp); mini_scale_issue(mp); mini_dma_a(mp); } \
+      if (n1) dma_a(cur, pa1, PAR_BYTES - parb, 1); \
       MB_SYNC_L() \
       if (!HN && SEQ && wm == 1 && cls_on) { _Pragma("unroll") for (int n = 0; n < 2; ++n) acce[n] = mma_tile(acce[n], wb[1][n], xe); } \
       if constexpr (!HN) { MB_MMA_DO(0, 1) } MB_MMA_END \
       /* ---- phase 2: (A1, B1); refill A0 of this parity with K-tile t+2 */ \
       MB_LOAD_A(1) \
-      if (MINI && mini_issue) { mini_dma_b(cur, mini_j); } \
-      if (n2) dma_a(cur, t + 2, 0); \
+      if (MINI && mini_issue) { mini_dma_b(mp); mini_step(mp); ++mj; } \
+      if (n2) dma_a(cur, pa2, parb, 0); \
       MB_SYNC_L() if (!HN) { MB_MMA_DO(1, 1) } MB_MMA_END \
       /* ---- phase 3: (A1, B0), B0 still in registers: no LDS reads; refill B1, X and B0 of this parity with K-tile t+2; K-tile t+1 must have landed. */ \
       /* In K-tile 0 nothing is waited for: K-tile 1 arrived with the prologue, and the previous tile's output */ \
       /* stores stay in flight until the wait of K-tile 1. */ \
-      if (n2) { dma_b(cur, t + 2, 1); dma_x(cur, t + 2); dma_b(cur, t + 2, 0); } \
+      if (n2) { dma_b(cur, pw2, parb, 1); dma_x(cur, pa2, parb); dma_b(cur, pw2, parb, 0); } \
       if (t >= 1) { \
         if (MINI) {                               /* the mini-tile's scale dword (requested in phase 1) is older than those: tied through, */ \
           /* ONE asm statement for the three cases: with one statement per case the compiler copied the still-in-flight register to its */ \
@@ -404,15 +447,13 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       MB_SYNC_L() MB_MMA_DO(1, 0) MB_MMA_END \
       /* ---- phase 4 (MINI): the mini-tile that landed under this (or the previous) K-tile's wait x the accumulators of its 128 token rows */ \
       if constexpr (MINI) { \
-        if (mini_every || (t & 1)) { \
-          const int mj = mini_every ? t : (t >> 1); \
-          int lo_ = lane; \
-          asm volatile("" : "+v"(lo_)); \
-          const int mfo = (lo_ & 15) * 64 + (((lo_ >> 4) ^ ((lo_ >> 1) & 3)) * 16); \
-          const char* mbuf = smem + MINI_OFF; \
+        if (mrun != 0) { \
+          int mfo_ = mfo; \
+          asm volatile("" : "+v"(mfo_)); \
+          const char* mbuf = smem + MINI_OFF + mfo_; \
           i32x4 mxa[4], mwb[4]; \
-          _Pragma("unroll") for (int n = 0; n < NTW; ++n) mwb[n] = *(const i32x4*)(mbuf + MINI_A + (wn * (64 / NS) + n * 16) * 64 + mfo); \
-          _Pragma("unroll") for (int i = 0; i < 4; ++i) mxa[i] = *(const i32x4*)(mbuf + (wm * 64 + i * 16) * 64 + mfo); \
+          _Pragma("unroll") for (int n = 0; n < NTW; ++n) mwb[n] = *(const i32x4*)(mbuf + MINI_A + (wn * (64 / NS) + n * 16) * 64); \
+          _Pragma("unroll") for (int i = 0; i < 4; ++i) mxa[i] = *(const i32x4*)(mbuf + (wm * 64 + i * 16) * 64); \
           const int mwsel = HN ? (int)((uint32_t)mws >> ((32 / NS) * cur.hb)) : mws;   /* (column-split tiles: the bytes of this tile's n-tiles) */ \
           MB_SYNC_L() \
           if constexpr (QN) { MB_MINI_MMA_QN(MAH) } else if constexpr (HN) { MB_MINI_MMA_HN(MAH) } else { MB_MINI_MMA(MAH) } \
@@ -421,9 +462,24 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
           MB_MMA_END \
         } \
       } \
+      /* ---- the stream moves on by one K-tile: scalar adds (split activations: the lo halves take over at K-tile nka) */ \
+      pa1 = pa2; \
+      pa2 = SPLIT && t + 3 == nka ? (const char*)Alo : pa2 + 128; \
+      pw2 = SPLIT && t + 3 == nkw ? (const char*)Wlo : pw2 + 128; \
+      parb = PAR_BYTES - parb; \
+      mdue ^= mflip; mrun ^= mflip; \
     }
     {
       int t = 0;
+      // carried through the K loop in SGPRs: the LDS parity of K-tile t and the bases of K-tile t + 1 of A (refilled in phase 1) and of
+      // K-tile t + 2 of A and W (phases 2 and 3)
+      int parb = 0;
+      const char *pa1 = ktile_a(1), *pa2 = ktile_a(2), *pw2 = ktile_w(2);
+      // MINI: a mini-tile is issued in the K-tiles t >= 1 with mdue != 0 (every one, or every other one: mflip) and multiplied in those with
+      // mrun != 0; mj: the next mini-tile to issue (mini 0 came with the prologue).  Scalar counters: no per-K-tile arithmetic on t.
+      const int mflip = mini_every ? 0 : 1;
+      int mdue = 1, mrun = mini_every ? 1 : 0, mj = 1;
+      (void)mj;
       if constexpr (MINI && !PAIR) {        // plain tiles: mini-tile t belongs to K-tile t; the first K / 128 update rows 0..127 of the tile, the others rows 128..255
         for (; t < nk / 2; ++t) MB_KTILE_(0)
         for (; t < nk; ++t) MB_KTILE_(1)
@@ -461,7 +517,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
     const int nvb = vb + gridDim.x;
     const bool has_next = PERSIST && nvb < ntiles;
     Plan nxt;
-    if (has_next) { make_plan(nvb, nxt); dma_x(nxt, 0); dma_x(nxt, 1); }
+    if (has_next) { make_plan(nvb, nxt); prologue_x(nxt); }
     f32x4 bias4[4], bcls[2];           // bcls: class-token row (indexing bias4 by wave id would put the array in scratch)
     if constexpr (MINI) {
       // The mini-tile kernels run at the 256-VGPR limit, where the allocator may move registers around: an asm load whose result it does
@@ -474,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
       if (has_next) scales_load(nxt);                                        // this tile's K loops are over: the scale registers are free
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(bias4[0]), "+v"(bias4[1]), "+v"(bias4[2]), "+v"(bias4[3]), "+v"(bcls[0]), "+v"(bcls[1]) :: "memory");
       if (has_next) scales_pack();
-      if (has_next) { prologue_rest(nxt); if constexpr (MINI) { mini_dma_a(nxt, 0); mini_dma_b(nxt, 0); } }
+      if (has_next) { prologue_rest(nxt); const MiniPos m0 = mini_pos(nxt); mini_dma_a(m0); mini_dma_b(m0); }
     } else {
 #define MB_LDG16(dst, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(ptr) : "memory")
 #pragma unroll
@@ -783,7 +839,7 @@ bool gemm_ht_supported(GemmEpi epi, const GemmArgs& a) {
   const int sqr = a.seq_rows ? a.seq_rows : 257;
   const int tok = a.pair_rows ? 128 : 256;                                                                  // tokens of a sequence tile
   if (a.seq_rows && ((sqr - 1) % tok || ((sqr - 1) / tok & ((sqr - 1) / tok - 1)) || (!a.pair_rows && a.M % sqr))) return false;   // sequence tiles: whole tiles, a power of two per sequence
-  if (a.pair_rows && (a.pair_rows % sqr || a.M != 2 * a.pair_rows || a.A2 || epi == EPI_GELU_F32)) return false;
+  if (a.pair_rows && (a.pair_rows % sqr || a.M != 2 * a.pair_rows || a.A2 || a.kw || epi == EPI_GELU_F32)) return false;   // (no split activations on pair tiles)
   // (plain tiles may combine the mini-tiles with split activations: A2 / kw, K = 2 kw -- hi + lo LayerNorm outputs AND the weight correction)
   if (a.nlo && (a.nlo > 2 || (a.pair_rows ? a.pair_rows % sqr : a.M % sqr) || (a.kw ? a.kw : a.K) % 128 || (!a.pair_rows && a.nlo != 1) ||
                 ((a.A2 || a.kw) && (a.pair_rows || !a.A2 || a.K != 2 * a.kw)) ||
@@ -791,8 +847,8 @@ bool gemm_ht_supported(GemmEpi epi, const GemmArgs& a) {
                 (a.nlo == 2 && (!a.lo[1].A4 || !a.lo[1].W4 || !a.lo[1].a_scale || !a.lo[1].w_scale)) || (uint64_t)a.M * a.K * 2 >= (1ull << 32) ||
                 epi == EPI_GELU_F32)) return false;
   return epi != EPI_LOGITS_F32 && a.N % 256 == 0 && a.K % 64 == 0 && a.K >= 128 && (a.M >= 512 || a.nlo) &&
-         (uint64_t)a.M * a.K < (1ull << 32) && (uint64_t)a.N * a.K < (1ull << 32) &&
-         (uint64_t)a.M * a.N * 4 < (1ull << 32);      // 32-bit element / byte offsets inside the kernel
+         (uint64_t)a.M * a.K * 2 < (1ull << 32) && (uint64_t)a.N * a.K * 2 < (1ull << 32) &&   // the DMA plan's 32-bit BYTE offsets into A and W
+         (uint64_t)a.M * a.N * 4 < (1ull << 32);      // 32-bit byte offsets into the output
 }
 
 void gemm_ht(hipStream_t s, GemmEpi epi, const GemmArgs& a, int mt) {

@@ -26,6 +26,23 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(gptr),       \
                                    (void __attribute__((address_space(3)))*)(ldsptr), 16, 0, aux)
 #define MB_GLDS16(gptr, ldsptr) MB_GLDS16_AUX(gptr, ldsptr, 0)
+// The same DMA in its scalar-base form: wave-uniform 64-bit base in an SGPR pair + a per-lane 32-bit BYTE offset, so no 64-bit VALU add stands in
+// front of it (the compiler hoists the zero-extension of a loop-invariant offset out of the loop and then selects the 64-bit VGPR form of the builtin).
+// Inline asm: M0 (the LDS destination) is written here and declared clobbered; like the builtin, the instruction counts in vmcnt and its LDS write is
+// covered by the caller's own counted waits and barriers.
+#define MB_GLDS16_SB(sbase, voff, ldsptr)                                                                      \
+  _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winline-asm\"")                        \
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                                 \
+               :: "v"((uint32_t)(voff)), "s"((const void*)(sbase)),                                             \
+                  "s"((uint32_t)(uintptr_t)(void __attribute__((address_space(3)))*)(ldsptr)) : "memory", "m0");       \
+  _Pragma("clang diagnostic pop")
+// ... with the LDS destination given as the sum of two scalars (a base that changes from step to step + this wave's fixed offset): the add writes M0
+#define MB_GLDS16_SB2(sbase, voff, ldsptr, ldsoff)                                                             \
+  _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winline-asm\"")                        \
+  asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                             \
+               :: "v"((uint32_t)(voff)), "s"((const void*)(sbase)),                                             \
+                  "s"((uint32_t)(uintptr_t)(void __attribute__((address_space(3)))*)(ldsptr)), "s"((int)(ldsoff)) : "memory", "m0", "scc"); \
+  _Pragma("clang diagnostic pop")
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
