@@ -86,7 +86,7 @@ int mb_gemm_ht_supported(int epi, int M, int N, int K);
  * across workgroups (0 = automatic; clamped to [1, min(64, C / 64 rounded up)]). */
 int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream);
 
-/* ---- single tokenizer layers (decoder.hip) on caller buffers, through the handle's own launch_conv / launch_gn / weight repack on a scratch
+/* ---- single tokenizer layers (conv.hip) on caller buffers, through the handle's own launch_conv / launch_gn / weight repack on a scratch
  * context.  These four synchronise the stream.
  * mb_conv_layer: one convolution.  in_h16 = fp16 NHWC [B, Hin, Win, Cin] with the TRUE channel count (padded to 64-channel chunks inside);
  * (Hin, Win) = (H, W), or (H / 2, W / 2) with `up` (nearest-2x upsampling fused into the 3x3 conv), or (2 H, 2 W) for ks 2 = the stride-2 3x3 TF-"same"
@@ -110,7 +110,7 @@ int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta,
 int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
 int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
 
-/* ---- the pieces of the LPIPS forward (lpips.hip, decoder.hip) on caller buffers.
+/* ---- the pieces of the LPIPS forward (lpips.hip, conv.hip) on caller buffers.
  * mb_conv_relu_layer: one convolution + bias + ReLU as the VGG16 stack launches it (no GroupNorm prologue or partials, zero padding 1 for ks 3;
  * ks 1 or 3): in_h16 fp16 NHWC [B, H, W, Cin] with the true channel count, w_oihw fp32 [Cout, Cin, ks, ks], bias fp32 [Cout] or NULL, out_h16
  * [B, H, W, Cout] (Cout % 4 == 0), H % 8 == 0, W % 16 == 0; *saturated (host) as for mb_conv_layer.  Synchronises the stream. */

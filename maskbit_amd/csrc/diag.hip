@@ -1,11 +1,12 @@
 // Diagnostic entry points (include/maskbit_hip_diag.h): single kernels and single layers on caller buffers, for the tests and the tools.
-// No host binding of the product needs them.  Argument checks and the launchers' own calls only: this file holds no kernel.
+// No host binding of the product needs them.  Argument checks, a scratch arena (mb::DevArena) where a layer needs one, and the launchers' own calls
+// only: this file holds no kernel.
 // (mb_gen_set_alo, the one entry of that header that needs the generator handle's members, is in engine.hip.)
 #include <hip/hip_runtime.h>
 
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
-#include "mb_decoder.h"
+#include "mb_conv.h"
 #include "mb_kernels.h"
 #include "mb_vq.h"
 
@@ -29,9 +30,10 @@ int w4_entry(const char* what, decltype(mb::w4_from_f32)* pack, const float* W, 
   return launched();
 }
 
-int pool_entry(const char* what, bool avg, const void* x, void* y, int B, int H, int W, int C, mb_stream stream) {
+int pool_entry(const char* what, decltype(mb::launch_s2d)* launch, const void* x, void* y, int B, int H, int W, int C, mb_stream stream) {
   if (!x || !y) return fail(-1, "%s: null argument", what);
-  if (int rc = mb::diag_pool(what, avg, x, y, B, H, W, C, (hipStream_t)stream)) return rc;
+  if (B <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8) return fail(-1, "%s: H and W must be even, C a multiple of 8", what);
+  launch((hipStream_t)stream, (const h16*)x, (h16*)y, B, H, W, C);
   return launched();
 }
 
@@ -155,34 +157,126 @@ int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int
   return launched();
 }
 
-// ---- single tokenizer layers on caller buffers (the handle's own launch helpers: mb::diag_* in decoder.hip) ----
+// ---- single tokenizer layers on caller buffers: the handle's own launchers (mb_conv.h) on a scratch arena instead of a handle.  The ones that
+// allocate synchronise the stream before they return (the scratch is freed on return); where a later allocation fails after work was queued, it is
+// the arena's hipFree that waits for that work, as hipFree does. ----
 int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
                   void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
-                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
+                  float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up_, int final_layer,
                   mb_stream stream) {
-  mb::ConvDiag q{in_h16, w_oihw, bias, gn_gamma, gn_beta, residual_h16, out_h16, img_nchw, img_nhwc_u8, out_gamma, out_beta, out_scale_shift,
-                 out_gn_part, part_tiles, saturated, B, H, W, Cin, Cout, ks, up, final_layer};
-  if (int rc = mb::diag_conv(q, (hipStream_t)stream)) return rc;
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
+  const bool fin = final_layer != 0, up = up_ != 0;
+  if (!in_h16 || !w_oihw || B <= 0 || Cin <= 0 || Cout <= 0) return fail(-1, "mb_conv_layer: null or empty argument");
+  if (ks < 1 || ks > 3) return fail(-1, "mb_conv_layer: ks must be 1, 2 or 3");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_conv_layer: the output must be whole 8 x 16 pixel tiles");
+  if (fin && (ks != 3 || up || Cout > 4 || residual_h16 || !(img_nchw || img_nhwc_u8))) return fail(-1, "mb_conv_layer: final layer: ks 3, at most 4 channels, no residual, an image output");
+  if (!fin && (!out_h16 || Cout % 4)) return fail(-1, "mb_conv_layer: fp16 output: Cout must be a multiple of 4");
+  if (up && ks != 3) return fail(-1, "mb_conv_layer: upsampling goes with ks 3");
+  if (ks == 2 && (Cin % 16 || gn_gamma)) return fail(-1, "mb_conv_layer: ks 2 (stride-2 conv): Cin must be a multiple of 16, no prologue");
+  if ((gn_gamma != nullptr) != (gn_beta != nullptr) || (gn_gamma && (Cin % CK || Cin > 2048))) return fail(-1, "mb_conv_layer: prologue: gamma and beta, Cin a multiple of 64 up to 2048");
+  if (out_scale_shift && (fin || !out_gamma || !out_beta || Cout % 32 || Cout > 2048)) return fail(-1, "mb_conv_layer: output statistics: gamma and beta, Cout a multiple of 32 up to 2048");
+  Conv c;
+  if (ks == 2) shape_down_conv(c, Cin); else shape_conv(c, Cin, Cout, ks, bias != nullptr, up, fin);
+  if (ks == 2) { c.cout = Cout; c.cout_w = Cout; c.cout_pad = (Cout + 127) / 128 * 128; c.has_bias = bias != nullptr; }
+  DevArena m;
+  GnCtx gc;
+  const int Hin = ks == 2 ? 2 * H : (up ? H / 2 : H), Win = ks == 2 ? 2 * W : (up ? W / 2 : W);   // the caller's input tensor
+  if (up && (H % 2 || W % 2)) return fail(-1, "mb_conv_layer: upsampling needs even H and W");
+  const size_t npix_in = (size_t)B * Hin * Win;
+  h16* staged = nullptr;
+  m.get(&c.w, conv_weight_elems(c)); m.get(&c.b, (size_t)c.cout_pad); m.get(&c.sat, 1);
+  m.get(&gc.part, gn_part_elems(B, std::max(H, Hin), std::max(W, Win))); m.get(&gc.ss, (size_t)B * std::max(c.cin_pad, std::max(Cout, 1)));
+  if (int rc = m.failed("mb_conv_layer")) return rc;
+  bool ok = hipMemsetAsync(c.b, 0, c.cout_pad * sizeof(float), s) == hipSuccess && hipMemsetAsync(c.sat, 0, sizeof(unsigned), s) == hipSuccess;
+  if (ok && bias) ok = hipMemcpyAsync(c.b, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  launch_repack_conv(s, c, w_oihw);
+  const h16* in = (const h16*)in_h16;
+  if (ks == 2) {                                    // [B, 2H, 2W, Cin] -> [B, H, W, 4 Cin]
+    if (!m.get(&staged, npix_in * Cin)) return m.failed("mb_conv_layer");
+    launch_s2d(s, in, staged, B, Hin, Win, Cin);
+    in = staged;
+  } else if (c.cin_pad != Cin) {                    // channels padded with zeros to a whole chunk, as pack_image_kernel / latent_kernel leave them
+    if (!m.get(&staged, npix_in * c.cin_pad)) return m.failed("mb_conv_layer");
+    ok = ok && hipMemsetAsync(staged, 0, npix_in * c.cin_pad * sizeof(h16), s) == hipSuccess &&
+         hipMemcpy2DAsync(staged, c.cin_pad * sizeof(h16), in, Cin * sizeof(h16), Cin * sizeof(h16), npix_in, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    in = staged;
+  }
+  if (!ok) return fail(-10, "mb_conv_layer: copy failed");
+  const float2* gn = nullptr;
+  if (gn_gamma) {
+    Norm n; n.c = Cin; n.g = const_cast<float*>(gn_gamma); n.b = const_cast<float*>(gn_beta);
+    launch_gn(s, &gc, n, in, B, Hin * Win);
+    gn = gc.ss;
+  }
+  launch_conv(s, &gc, c, in, gn, (const h16*)residual_h16, (h16*)out_h16, img_nchw, img_nhwc_u8, B, H, W, fin);
+  const int tiles = gc.of == (const void*)out_h16 && !fin ? gc.ntile : 0;      // the epilogue wrote GroupNorm partials of the output
+  if (part_tiles) *part_tiles = tiles;
+  if (out_gn_part && tiles) ok = hipMemcpyAsync(out_gn_part, gc.part, (size_t)B * tiles * 64 * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (ok && out_scale_shift) {
+    Norm n; n.c = Cout; n.g = const_cast<float*>(out_gamma); n.b = const_cast<float*>(out_beta);
+    launch_gn(s, &gc, n, (const h16*)out_h16, B, H * W);                      // from the epilogue's partials when there are any, else the sweep
+    ok = hipMemcpyAsync(out_scale_shift, gc.ss, (size_t)B * Cout * sizeof(float2), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  }
+  unsigned nsat = 0;
+  ok = ok && hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_conv_layer: copy failed");
+  if (saturated) *saturated = nsat;
   return launched();
 }
 int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream) {
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
   if (!x_h16 || !gamma || !beta || !scale_shift) return fail(-1, "mb_groupnorm_stats: null argument");
-  if (int rc = mb::diag_groupnorm(x_h16, gamma, beta, scale_shift, B, HW, C, (hipStream_t)stream)) return rc;
+  if (B <= 0 || HW <= 0 || C < 32 || C > 2048 || C % 32 || (C / 8) > 256) return fail(-1, "mb_groupnorm_stats: C must be a multiple of 32 in [32, 2048]");
+  DevArena m;
+  GnCtx gc;
+  m.get(&gc.part, gn_part_elems(B, 0, 0)); m.get(&gc.ss, (size_t)B * C);
+  if (int rc = m.failed("mb_groupnorm_stats")) return rc;
+  Norm n; n.c = C; n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta);
+  launch_gn(s, &gc, n, (const h16*)x_h16, B, HW);   // gc.of is null: the sweep (gn_partial_kernel) + gn_finalize_kernel
+  if (hipMemcpyAsync(scale_shift, gc.ss, (size_t)B * C * sizeof(float2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) return fail(-10, "mb_groupnorm_stats: copy failed");
   return launched();
 }
-int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", true, x_h16, y_h16, B, H, W, C, stream); }
-int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", false, x_h16, y_h16, B, H, W, C, stream); }
+int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", mb::launch_avgpool2, x_h16, y_h16, B, H, W, C, stream); }
+int mb_s2d(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_s2d", mb::launch_s2d, x_h16, y_h16, B, H, W, C, stream); }
 
 // ---- the pieces of the LPIPS forward (mb_lpips_input / _distance / _features need lpips.hip's kernels and handle and are defined there) ----
+// w fp32 OIHW, bias fp32 [Cout] or null, in / out fp16 NHWC with the true channel counts
 int mb_conv_relu_layer(const void* in_h16, const float* w_oihw, const float* bias, void* out_h16, unsigned* saturated, int B, int H, int W, int Cin,
                        int Cout, int ks, mb_stream stream) {
-  if (int rc = mb::diag_conv_relu(in_h16, w_oihw, bias, out_h16, saturated, B, H, W, Cin, Cout, ks, (hipStream_t)stream)) return rc;
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
+  if (!in_h16 || !w_oihw || !out_h16 || B <= 0 || Cin <= 0 || Cout <= 0) return fail(-1, "mb_conv_relu_layer: null or empty argument");
+  if (ks != 1 && ks != 3) return fail(-1, "mb_conv_relu_layer: ks must be 1 or 3");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_conv_relu_layer: the output must be whole 8 x 16 pixel tiles");
+  if (Cout % 4) return fail(-1, "mb_conv_relu_layer: Cout must be a multiple of 4");
+  Conv c;
+  shape_conv(c, Cin, Cout, ks, true, false, false);
+  DevArena m;
+  const size_t npix = (size_t)B * H * W;
+  const h16* in = (const h16*)in_h16;
+  h16* staged = nullptr;
+  m.get(&c.w, conv_weight_elems(c)); m.get(&c.b, (size_t)c.cout_pad); m.get(&c.sat, 1);
+  if (int rc = m.failed("mb_conv_relu_layer")) return rc;
+  bool ok = hipMemsetAsync(c.b, 0, c.cout_pad * sizeof(float), s) == hipSuccess && hipMemsetAsync(c.sat, 0, sizeof(unsigned), s) == hipSuccess;
+  if (ok && bias) ok = hipMemcpyAsync(c.b, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  launch_repack_conv(s, c, w_oihw);
+  if (c.cin_pad != Cin) {                           // channels padded with zeros to a whole chunk
+    if (!m.get(&staged, npix * c.cin_pad)) return m.failed("mb_conv_relu_layer");
+    ok = ok && hipMemsetAsync(staged, 0, npix * c.cin_pad * sizeof(h16), s) == hipSuccess &&
+         hipMemcpy2DAsync(staged, c.cin_pad * sizeof(h16), in, Cin * sizeof(h16), Cin * sizeof(h16), npix, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    in = staged;
+  }
+  if (!ok) return fail(-10, "mb_conv_relu_layer: copy failed");
+  launch_conv_relu(s, ConvRelu{in, c.w, c.b, (h16*)out_h16, c.sat, B, H, W, c.cin_pad, c.cout, c.cout_pad, ks});
+  unsigned nsat = 0;
+  ok = hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_conv_relu_layer: copy failed");
+  if (saturated) *saturated = nsat;
   return launched();
 }
-int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) {
-  if (!x_h16 || !y_h16) return fail(-1, "mb_maxpool2: null argument");
-  if (int rc = mb::diag_maxpool(x_h16, y_h16, B, H, W, C, (hipStream_t)stream)) return rc;
-  return launched();
-}
+int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_maxpool2", mb::launch_maxpool2, x_h16, y_h16, B, H, W, C, stream); }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   edit_init_kernel       -- the encoder's codes + the token mask -> grouped tokens with the mask token at the slots to regenerate, and their count.
 //   edit_load_kernel       -- a caller's grouped tokens -> the engine's token state (clamped to [0, C]) and the count of mask tokens per sample.
 //   edit_composite_kernel  -- generated and original image + pixel mask -> the image that keeps the original pixels outside the mask, as fp32 NCHW
-//                             and / or uint8 NHWC (the decoder's own conversion, decoder.hip: trunc(clamp(x, 0, 1) * 255)).
+//                             and / or uint8 NHWC (the decoder's own conversion, conv.hip: trunc(clamp(x, 0, 1) * 255)).
 // Stateless: the caller owns every buffer; nothing is allocated, nothing synchronises.
 #include <algorithm>
 

@@ -1,7 +1,7 @@
 // The generator handle of libmaskbit_hip.so (include/maskbit_hip.h): checkpoint ingest with h16 repack, the two forward schedules (plain and
 // differential CFG), the fused sampling step and the whole sampling loop; and the three ABI-wide entries (mb_abi_version, mb_last_error, mb_prof_*).
 // The tokenizer handle's entry points are in decoder.hip, the diagnostic ones (include/maskbit_hip_diag.h) in diag.hip -- all but mb_gen_set_alo,
-// which needs struct mb_gen; the error path and the profiling scopes they all share are in mb_abi.h.
+// which needs struct mb_gen; the error path, the device-allocation arena and the profiling scopes they all share are in mb_abi.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,16 +18,6 @@ using mb::fail;
 using mb::g_prof;
 using mb::launched;
 using mb::ProfScope;
-
-namespace {
-
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  return 0;
-}
-
-}  // namespace
 
 // ================================================================================================
 // generator
@@ -90,26 +80,16 @@ struct mb_gen {
   int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
   uint8_t* drop_cfg = nullptr;
   float* logits = nullptr;
-  std::vector<void*> owned;
+  mb::DevArena mem;
   int loaded = 0;
 };
 
 namespace {
 
-template <typename T>
-int galloc(mb_gen* g, T** p, size_t n) {
-  int rc = dev_alloc(p, n);
-  if (rc == 0) g->owned.push_back((void*)*p);
-  return rc;
-}
-
 // rows x width e2m1 values and the scale bytes of ntok = sequences x tokens rows, zeroed
-int galloc_f4(mb_gen* g, F4Buf* b, size_t rows, size_t width, size_t ntok) {
-  const size_t nv = rows * 2 * width, ns = (width / 64) * ntok + 256;
-  int rc = galloc(g, &b->v, nv);
-  rc |= galloc(g, &b->s, ns);
-  if (!rc) { (void)hipMemset(b->v, 0, nv); (void)hipMemset(b->s, 0, ns); }
-  return rc;
+void alloc_f4(mb::DevArena& m, F4Buf* b, size_t rows, size_t width, size_t ntok) {
+  m.zeroed(&b->v, rows * 2 * width);
+  m.zeroed(&b->s, (width / 64) * ntok + 256);
 }
 
 // The head (bert.py:411-417, 500-503): last_layer.0 + GELU, LayerNorm, prediction layer, on the hi + lo rows the trunk's last LayerNorm left in
@@ -428,29 +408,28 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   const size_t max_rows = ((1ull << 32) - 1) / (4 * widest);
   g->chunk_seqs = (int)std::min<size_t>((size_t)max_seqs, std::max<size_t>(1, max_rows / g->N));
   const size_t d = c.hidden, f = c.mlp, M = (size_t)g->chunk_seqs * g->N;
-  int rc = 0;
+  mb::DevArena& m = g->mem;
   g->layers.resize(c.depth);
-  rc |= galloc(g, &g->split_tmp, 1);
-  rc |= galloc(g, &g->sat, 1);
-  if (!rc) (void)hipMemset(g->sat, 0, sizeof(unsigned));
+  m.get(&g->split_tmp, 1);
+  m.zeroed(&g->sat, 1);
   for (auto& L : g->layers) {
-    rc |= galloc(g, &L.wqkv, 3 * d * d); rc |= galloc(g, &L.bqkv, 3 * d);
-    rc |= galloc(g, &L.wo, d * d); rc |= galloc(g, &L.bo, d);
-    rc |= galloc(g, &L.w1, f * d); rc |= galloc(g, &L.b1, f);
-    rc |= galloc(g, &L.w2, d * f); rc |= galloc(g, &L.b2, d);
-    rc |= galloc(g, &L.ln1g, d); rc |= galloc(g, &L.ln1b, d); rc |= galloc(g, &L.ln2g, d); rc |= galloc(g, &L.ln2b, d);
+    m.get(&L.wqkv, 3 * d * d); m.get(&L.bqkv, 3 * d);
+    m.get(&L.wo, d * d); m.get(&L.bo, d);
+    m.get(&L.w1, f * d); m.get(&L.b1, f);
+    m.get(&L.w2, d * f); m.get(&L.b2, d);
+    m.get(&L.ln1g, d); m.get(&L.ln1b, d); m.get(&L.ln2g, d); m.get(&L.ln2b, d);
   }
-  rc |= galloc(g, &g->w_in, d * c.bits); rc |= galloc(g, &g->b_in, d);
-  if (c.prenorm) { rc |= galloc(g, &g->lnag, d); rc |= galloc(g, &g->lnab, d); }
-  if (c.embed_tables) { rc |= galloc(g, &g->tables, (size_t)c.splits * (C + 1) * d); rc |= galloc(g, &g->bias_pos, (size_t)c.seq * c.splits * C); }
-  rc |= galloc(g, &g->class_emb, (size_t)(c.nclass + 1) * d); rc |= galloc(g, &g->pos, (size_t)g->N * d);
-  rc |= galloc(g, &g->ln0g, d); rc |= galloc(g, &g->ln0b, d);
-  rc |= galloc(g, &g->wl, d * d); rc |= galloc(g, &g->wl_lo, d * d); rc |= galloc(g, &g->bl, d); rc |= galloc(g, &g->lnhg, d); rc |= galloc(g, &g->lnhb, d);
-  rc |= galloc(g, &g->wp, (size_t)c.splits * C * d); rc |= galloc(g, &g->bp, (size_t)c.splits * C); rc |= galloc(g, &g->head_scale, 2);
-  if (!c.embed_tables) rc |= galloc(g, &g->wp_lo, (size_t)c.splits * C * d);
-  rc |= galloc(g, &g->y_f32, M * d); rc |= galloc(g, &g->ln_stats, M * 2); rc |= galloc(g, &g->x_h16, M * d);
-  rc |= galloc(g, &g->x_lo, M * d);   // lo halves of the LayerNorm outputs: always for the head GEMMs, precision >= 1 for QKV / FFN-up of plain forwards
-  rc |= galloc(g, &g->qkv, M * 3 * d); rc |= galloc(g, &g->att, M * d); rc |= galloc(g, &g->h, M * f);
+  m.get(&g->w_in, d * c.bits); m.get(&g->b_in, d);
+  if (c.prenorm) { m.get(&g->lnag, d); m.get(&g->lnab, d); }
+  if (c.embed_tables) { m.get(&g->tables, (size_t)c.splits * (C + 1) * d); m.get(&g->bias_pos, (size_t)c.seq * c.splits * C); }
+  m.get(&g->class_emb, (size_t)(c.nclass + 1) * d); m.get(&g->pos, (size_t)g->N * d);
+  m.get(&g->ln0g, d); m.get(&g->ln0b, d);
+  m.get(&g->wl, d * d); m.get(&g->wl_lo, d * d); m.get(&g->bl, d); m.get(&g->lnhg, d); m.get(&g->lnhb, d);
+  m.get(&g->wp, (size_t)c.splits * C * d); m.get(&g->bp, (size_t)c.splits * C); m.get(&g->head_scale, 2);
+  if (!c.embed_tables) m.get(&g->wp_lo, (size_t)c.splits * C * d);
+  m.get(&g->y_f32, M * d); m.get(&g->ln_stats, M * 2); m.get(&g->x_h16, M * d);
+  m.get(&g->x_lo, M * d);   // lo halves of the LayerNorm outputs: always for the head GEMMs, precision >= 1 for QKV / FFN-up of plain forwards
+  m.get(&g->qkv, M * 3 * d); m.get(&g->att, M * d); m.get(&g->h, M * f);
   // MX-fp4 mini-tile passes (precision 2 / 3): 257- / 1025-token sequences, vector LayerNorm widths, heads of 64 (the attention kernels' e2m1 output), whole mini-tiles
   g->mini_ok = c.precision >= 2 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && c.hidden / c.heads == 64;   // (FFN-up's N = mlp: whole 256-column tiles)
   // differential CFG forward: 257-token sequences (pair tiles = 2 x 128 tokens + the class pair), vector LayerNorm widths, plain fp16 operands
@@ -461,39 +440,35 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
                (c.precision == 1 || g->mini_ok);
   if (g->mini_ok) {
     const size_t ntok = (size_t)g->chunk_seqs * c.seq;
-    rc |= galloc_f4(g, &g->x4, M, d, ntok);
-    rc |= galloc_f4(g, &g->att4, M, d, ntok);
-    rc |= galloc_f4(g, &g->h4, M, f, ntok);
-    if (g->alo_mask_built & 5) rc |= galloc_f4(g, &g->xl4, M, d, ntok);
-    if (g->alo_mask_built & 2) rc |= galloc_f4(g, &g->attl4, M, d, ntok);
-    if (g->alo_mask_built & 8) rc |= galloc_f4(g, &g->hl4, M, f, ntok);
+    alloc_f4(m, &g->x4, M, d, ntok);
+    alloc_f4(m, &g->att4, M, d, ntok);
+    alloc_f4(m, &g->h4, M, f, ntok);
+    if (g->alo_mask_built & 5) alloc_f4(m, &g->xl4, M, d, ntok);
+    if (g->alo_mask_built & 2) alloc_f4(m, &g->attl4, M, d, ntok);
+    if (g->alo_mask_built & 8) alloc_f4(m, &g->hl4, M, f, ntok);
     g->w4lo.assign((size_t)4 * c.depth, nullptr); g->w4los.assign((size_t)4 * c.depth, nullptr);
     g->w4.assign((size_t)4 * c.depth, nullptr); g->w4s.assign((size_t)4 * c.depth, nullptr);
     // mini-tile-packed e2m1 of the four weights of a layer: half a byte per weight, one scale byte per (weight row, 128 columns)
     const size_t wn[4] = {3 * d * d, d * d, f * d, d * f};
     for (int i = 0; i < 4 * c.depth; ++i) {
       const size_t n = wn[i & 3];
-      rc |= galloc(g, &g->w4lo[i], n / 2); rc |= galloc(g, &g->w4los[i], n / 128);
+      m.get(&g->w4lo[i], n / 2); m.get(&g->w4los[i], n / 128);
       // e2m1 of the fp16 weight VALUES for the GEMMs that carry an activation-lo set (precision >= 3)
-      if ((g->alo_mask_built >> (i & 3)) & 1) { rc |= galloc(g, &g->w4[i], n / 2); rc |= galloc(g, &g->w4s[i], n / 128); }
+      if ((g->alo_mask_built >> (i & 3)) & 1) { m.get(&g->w4[i], n / 2); m.get(&g->w4s[i], n / 128); }
     }
   }
   const size_t P = (size_t)c.seq * c.splits, B = max_seqs;
-  rc |= galloc(g, &g->tok_a, B * P); rc |= galloc(g, &g->tok_b, B * P); rc |= galloc(g, &g->tok_cfg, B * P);
-  rc |= galloc(g, &g->pred, B * P); rc |= galloc(g, &g->codes, B * c.seq);
-  rc |= galloc(g, &g->lab_cfg, B); rc |= galloc(g, &g->drop_cfg, B); rc |= galloc(g, &g->logits, B * P * C);
-  rc |= galloc(g, &g->num_regen, B);
-  if (g->chunk_seqs < max_seqs) rc |= galloc(g, &g->logits_tmp, (size_t)g->chunk_seqs * P * C);
-  if (rc) { mb_gen_destroy(g); return rc; }
+  m.get(&g->tok_a, B * P); m.get(&g->tok_b, B * P); m.get(&g->tok_cfg, B * P);
+  m.get(&g->pred, B * P); m.get(&g->codes, B * c.seq);
+  m.get(&g->lab_cfg, B); m.get(&g->drop_cfg, B); m.get(&g->logits, B * P * C);
+  m.get(&g->num_regen, B);
+  if (g->chunk_seqs < max_seqs) m.get(&g->logits_tmp, (size_t)g->chunk_seqs * P * C);
+  if (int rc = m.failed("mb_gen_create")) { delete g; return rc; }
   *out = g;
   return 0;
 }
 
-void mb_gen_destroy(mb_gen* g) {
-  if (!g) return;
-  for (void* p : g->owned) (void)hipFree(p);
-  delete g;
-}
+void mb_gen_destroy(mb_gen* g) { delete g; }
 
 int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
   if (!g || !name || !data) return fail(-1, "mb_gen_load: bad arguments");

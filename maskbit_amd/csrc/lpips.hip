@@ -6,7 +6,7 @@
 // taps outside the image 0 (zero padding AFTER the scaling, as conv2d pads), padded to the 64-channel chunk of conv_kernel.  The padded 3x3 on 3 of
 // 64 channels would spend 21 x the arithmetic.
 //
-// The thirteen convolutions are decoder.hip's conv_kernel with its bias + ReLU epilogue (mb_decoder.h launch_conv_relu), the four pools its
+// The thirteen convolutions are conv.hip's conv_kernel with its bias + ReLU epilogue (mb_conv.h launch_conv_relu), the four pools its
 // maxpool2_kernel; activations are fp16 NHWC.  Tiles are per image, so an image's features do not depend on the batch it sits in.
 //
 // lpips_distance_kernel<C> (HBM-bound, one read of both feature maps of a tap): a pixel's C channels are held by C / 8 lanes, 16 bytes each.  With
@@ -31,8 +31,7 @@
 #include "../../include/maskbit_hip.h"
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
-#include "mb_common.h"
-#include "mb_decoder.h"
+#include "mb_conv.h"
 
 namespace mb {
 
@@ -184,7 +183,7 @@ struct mb_lpips {
   double* part = nullptr;          // [max_pairs][LP_MAXBLK]
   unsigned* sat = nullptr;
   uint64_t loaded = 0;             // one bit per checkpoint entry: 13 weights, 13 biases, 5 lin vectors, shift, scale
-  std::vector<void*> owned;
+  mb::DevArena mem;
 };
 
 using namespace mb;
@@ -192,13 +191,6 @@ using namespace mb;
 namespace {
 
 constexpr uint64_t LP_ALL = (1ull << 33) - 1;
-
-template <typename T>
-bool lp_alloc(mb_lpips* h, T** p, size_t n) {
-  if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) return false;
-  h->owned.push_back((void*)*p);
-  return true;
-}
 
 const char* size_rule = "H must be a multiple of 128 and W a multiple of 256 (whole 8 x 16-pixel tiles at 1/16 resolution)";
 
@@ -247,33 +239,25 @@ int mb_lpips_create(int max_pairs, int max_h, int max_w, mb_lpips** out) {
   if (max_h < 128 || max_w < 256 || max_h % 128 || max_w % 256) return fail(-1, "mb_lpips_create: capacity %d x %d: %s", max_h, max_w, size_rule);
   mb_lpips* h = new mb_lpips();
   h->max_pairs = max_pairs; h->max_h = max_h; h->max_w = max_w;
-  bool ok = lp_alloc(h, &h->sat, 1) && lp_alloc(h, &h->sc, 6) && lp_alloc(h, &h->part, (size_t)max_pairs * LP_MAXBLK);
-  if (ok) ok = hipMemset(h->sat, 0, sizeof(unsigned)) == hipSuccess;
+  DevArena& m = h->mem;
+  m.zeroed(&h->sat, 1); m.get(&h->sc, 6); m.get(&h->part, (size_t)max_pairs * LP_MAXBLK);
   int cin = 3;
-  for (int l = 0; ok && l < LP_NCONV; ++l) {
+  for (int l = 0; l < LP_NCONV; ++l) {
     LpConv& c = h->conv[l];
     c.cin = cin; c.cout = LP_COUT[l];
     c.ks = l == 0 ? 1 : 3;                                 // conv1_1 on the 27-value patches
     c.cin_pad = l == 0 ? 64 : cin; c.cout_pad = (c.cout + 127) / 128 * 128;
-    ok = lp_alloc(h, &c.w, (size_t)c.ks * c.ks * c.cout_pad * c.cin_pad) && lp_alloc(h, &c.b, (size_t)c.cout_pad);
-    if (ok) ok = hipMemset(c.b, 0, c.cout_pad * sizeof(float)) == hipSuccess;
+    m.get(&c.w, (size_t)c.ks * c.ks * c.cout_pad * c.cin_pad); m.zeroed(&c.b, (size_t)c.cout_pad);
     cin = c.cout;
   }
-  for (int k = 0; ok && k < LP_NTAP; ++k) ok = lp_alloc(h, &h->lin[k], (size_t)LP_TAPC[k]);
-  for (int i = 0; ok && i < 2; ++i) ok = lp_alloc(h, &h->buf[i], (size_t)2 * max_pairs * max_h * max_w * 64);
-  if (!ok) {
-    mb_lpips_destroy(h);
-    return fail(-1, "mb_lpips_create: hipMalloc failed");
-  }
+  for (int k = 0; k < LP_NTAP; ++k) m.get(&h->lin[k], (size_t)LP_TAPC[k]);
+  for (int i = 0; i < 2; ++i) m.get(&h->buf[i], (size_t)2 * max_pairs * max_h * max_w * 64);
+  if (int rc = m.failed("mb_lpips_create")) { delete h; return rc; }
   *out = h;
   return 0;
 }
 
-void mb_lpips_destroy(mb_lpips* h) {
-  if (!h) return;
-  for (void* p : h->owned) (void)hipFree(p);
-  delete h;
-}
+void mb_lpips_destroy(mb_lpips* h) { delete h; }
 
 int mb_lpips_load(mb_lpips* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
   if (!h || !name || !data || !shape || ndim < 0) return fail(-1, "mb_lpips_load: bad arguments");
@@ -348,8 +332,10 @@ int mb_lpips_distance(const void* feat_a, const void* feat_b, const float* w, in
   if (!feat_a || !feat_b || !w || !per_image || B < 1 || B > 65535 || HW < 1) return fail(-1, "mb_lpips_distance: bad arguments");
   if (C != 64 && C != 128 && C != 256 && C != 512) return fail(-1, "mb_lpips_distance: C must be 64, 128, 256 or 512");
   hipStream_t s = (hipStream_t)stream;
+  DevArena m;
   double* part = nullptr;
-  if (hipMalloc((void**)&part, (size_t)B * LP_MAXBLK * sizeof(double)) != hipSuccess) return fail(-10, "mb_lpips_distance: hipMalloc failed");
+  m.get(&part, (size_t)B * LP_MAXBLK);
+  if (int rc = m.failed("mb_lpips_distance")) return rc;
   for (int b0 = 0; b0 < B; b0 += LP_THREADS) {              // (the finalize is one workgroup; any B is fine, chunked only to keep it short)
     const int nb = std::min(LP_THREADS, B - b0);
     launch_distance(s, (const h16*)feat_a + (size_t)b0 * HW * C, (const h16*)feat_b + (size_t)b0 * HW * C, w, nb, HW, C, part + (size_t)b0 * LP_MAXBLK, 1, 0,
@@ -357,7 +343,6 @@ int mb_lpips_distance(const void* feat_a, const void* feat_b, const float* w, in
   }
   const int rc = launched();
   const bool ok = hipStreamSynchronize(s) == hipSuccess;    // the scratch is freed on return
-  (void)hipFree(part);
   if (rc) return rc;
   return ok ? 0 : fail(-10, "mb_lpips_distance: synchronise failed");
 }

@@ -1,8 +1,10 @@
-// Host-side plumbing of the C ABI, shared by every translation unit that defines an entry point (engine.hip, diag.hip, decoder.hip, vq.hip):
-// the library's one error path (fail -> mb_last_error), the check after a launch, and the optional per-kernel device timing.
+// Host-side plumbing of the C ABI, shared by every translation unit that defines an entry point (engine.hip, diag.hip, decoder.hip, lpips.hip, vq.hip, ...):
+// the library's one error path (fail -> mb_last_error), the one owner of device allocations (DevArena), the check after a launch, and the optional
+// per-kernel device timing.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <map>
@@ -28,6 +30,50 @@ inline int fail(int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                                        \
     if (e_ != hipSuccess) return mb::fail(-10, "%s failed: %s", #expr, hipGetErrorString(e_));     \
   } while (0)
+
+// The owner of a handle's (or of one diagnostic call's) device allocations: hipMalloc through get / zeroed, everything freed in reverse order by
+// the destructor.  Failure is sticky -- after the first failed call nothing more is allocated and every later *p stays null -- so a create function
+// allocates straight through and asks failed() once at the end.  (vq.hip's stream-ordered hipMallocAsync scratch must not synchronise and is not this.)
+struct DevArena {
+  DevArena() = default;
+  DevArena(const DevArena&) = delete;
+  DevArena& operator=(const DevArena&) = delete;
+  ~DevArena() { for (auto it = owned.rbegin(); it != owned.rend(); ++it) (void)hipFree(*it); }
+  // n elements (0: 1, so that every pointer of a live arena is valid); *p is null after any failure
+  template <class T>
+  bool get(T** p, size_t n) {
+    *p = nullptr;
+    if (err != hipSuccess) return false;
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    void* q = nullptr;
+    if (!ok(hipMalloc(&q, bytes), "hipMalloc", bytes)) return false;
+    owned.push_back(q);
+    *p = (T*)q;
+    return true;
+  }
+  // the same, zero-filled (a failed fill leaves *p null too; the memory stays the arena's until it goes)
+  template <class T>
+  bool zeroed(T** p, size_t n) {
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    if (get(p, n) && !ok(hipMemset(*p, 0, bytes), "hipMemset", bytes)) *p = nullptr;
+    return *p != nullptr;
+  }
+  // 0, or the first failure in the name of the entry `who`: -10, the code of HIP_TRY
+  int failed(const char* who) const {
+    return err == hipSuccess ? 0 : fail(-10, "%s: %s of %zu bytes failed: %s", who, err_call, err_bytes, hipGetErrorString(err));
+  }
+
+ private:
+  std::vector<void*> owned;
+  hipError_t err = hipSuccess;     // of the call that failed ...
+  const char* err_call = "";       // ... its name ...
+  size_t err_bytes = 0;            // ... and its size
+  bool ok(hipError_t e, const char* call, size_t bytes) {
+    if (e == hipSuccess) return true;
+    err = e; err_call = call; err_bytes = bytes;
+    return false;
+  }
+};
 
 // the end of an entry point that launched kernels: 0, or the launch error
 inline int launched() {

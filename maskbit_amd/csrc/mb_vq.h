@@ -1,5 +1,5 @@
 // Lookup (VQ) quantizer kernels (vq.hip): nearest-codeword search fused with its argmin, code -> latent gather and the latent pack of
-// ConvVQModel with quantizer_type = "lookup" (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119).  Used by decoder.hip and by the
+// ConvVQModel with quantizer_type = "lookup" (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119).  Used by the tokenizer handle (decoder.hip) and by the
 // diagnostic entry mb_vq_argmin (diag.hip).
 #pragma once
 #include <hip/hip_runtime.h>

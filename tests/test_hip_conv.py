@@ -1,4 +1,4 @@
-"""The tokenizer's kernels (maskbit_amd/csrc/decoder.hip) layer by layer against an fp64 reference of the same operation.
+"""The tokenizer's kernels (maskbit_amd/csrc/conv.hip) layer by layer against an fp64 reference of the same operation.
 
 Every case runs ONE layer through the diagnostic entries of include/maskbit_hip_diag.h (mb_conv_layer, mb_groupnorm_stats, mb_avgpool2, mb_s2d), which
 call the product's own launch_conv / launch_gn / weight repack on a scratch context.  The reference is torch on the CPU in float64, fed the same

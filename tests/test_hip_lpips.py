@@ -1,4 +1,4 @@
-"""LPIPS on the HIP path (maskbit_amd/csrc/lpips.hip, the ReLU convolution and the max-pool of decoder.hip): every kernel alone on its smallest
+"""LPIPS on the HIP path (maskbit_amd/csrc/lpips.hip, the ReLU convolution and the max-pool of conv.hip): every kernel alone on its smallest
 shapes through the diagnostic entries of include/maskbit_hip_diag.h, the whole network against the float64 restatement of the reference
 (tests/lpips_reference.py) and the reference's own recorded float64 run (tests/golden/lpips.npz), and the state of ``TokenizerEvaluator.use_lpips``.
 

@@ -306,3 +306,44 @@ def test_bench_dump_outputs_float32_and_a_fixed_sample_above_the_limit(tmp_path,
     r = rows.astype(np.int64)
     assert (np.load(tmp_path / "b" / "images.npy") == img.numpy()[r]).all() and (np.load(tmp_path / "b" / "codes.npy") == codes.numpy()[r]).all()
     assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="needs the absence of a device: every device allocation must fail")
+def test_allocation_failure_reports_one_way_from_every_entry():
+    """mb::DevArena (csrc/mb_abi.h) owns every device allocation of the library.  Without a device the first hipMalloc of each create entry, and of the
+    layer diagnostics whose scratch allocation is their first device call, fails: each returns -10 (the code of a failed HIP call, not the -1 of bad
+    arguments), leaves the out handle null and reports "<its own name>: hipMalloc of N bytes failed: <the runtime's error string>" -- twice over
+    (nothing is left behind by the first failure)."""
+    import ctypes as C
+    from maskbit_amd import _lib
+    lib = _lib.load()
+    # the runtime the library is bound to, as this process has it loaded (torch loaded it): whatever its version
+    hip_path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
+    hip = C.CDLL(hip_path)
+    hip.hipGetErrorString.restype = C.c_char_p
+    p = C.c_void_p()
+    err = hip.hipMalloc(C.byref(p), C.c_size_t(16))
+    assert err != 0
+    why = hip.hipGetErrorString(err).decode()
+    gen = _lib.GenCfg(bits=12, splits=2, hidden=128, heads=4, depth=2, mlp=256, seq=256, nclass=10, prenorm=0, embed_tables=0, precision=2)
+    dec = _lib.DecCfg(token_size=12, hidden_channels=64, num_resolutions=2, num_res_blocks=1, num_channels=3, channel_mult=(C.c_int * 8)(1, 2),
+                      latent_size=16, build_encoder=1, sample_with_conv=1, enc_res_blocks=0)
+    creates = {
+        "mb_gen_create": lambda h: lib.mb_gen_create(C.byref(gen), 2, C.byref(h)),
+        "mb_dec_create": lambda h: lib.mb_dec_create(C.byref(dec), 2, C.byref(h)),
+        "mb_dec_create_vq": lambda h: lib.mb_dec_create_vq(C.byref(dec), 64, 0, 2, C.byref(h)),
+        "mb_lpips_create": lambda h: lib.mb_lpips_create(1, 128, 256, C.byref(h)),
+    }
+    buf = (C.c_float * 65536)()                        # any non-null pointers: the scratch allocation comes before they are touched
+    sat = C.c_uint(0)
+    layers = {
+        "mb_groupnorm_stats": lambda h: lib.mb_groupnorm_stats(buf, buf, buf, buf, 1, 128, 64, None),
+        "mb_conv_relu_layer": lambda h: lib.mb_conv_relu_layer(buf, buf, buf, buf, C.byref(sat), 1, 8, 16, 64, 64, 3, None),
+    }
+    for name, call in {**creates, **layers}.items():
+        for _ in range(2):
+            h = C.c_void_p()
+            assert call(h) == -10, name
+            assert h.value is None, name
+            msg = lib.mb_last_error().decode()
+            assert re.fullmatch(re.escape(name) + r": hipMalloc of \d+ bytes failed: " + re.escape(why), msg), msg
