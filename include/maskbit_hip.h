@@ -212,6 +212,47 @@ int mb_edit_token_mask(const uint8_t* pixel_mask, uint8_t* token_mask, int B, in
 int mb_edit_composite(const float* gen_nchw, const float* orig_nchw, const uint8_t* pixel_mask, float* out_nchw, uint8_t* out_nhwc_u8,
                       int B, int C, int H, int W, mb_stream stream);
 
+/* ---- per-sample seeded sampling: the step kernel generates its own noise ------------------------------------------------------------------- *
+ * No counterpart in the reference, whose noise is drawn by torch outside the loop (sampling.py:107,113-117) and therefore depends on a sample's
+ * position in the batch, the batch size and the generators' history.  Here every noise value is a pure function of (the sample's 64-bit seed, the
+ * absolute step index of the run, the slot, the class): nothing is drawn, stored, chunked or copied, and a sample's tokens depend only on its seed,
+ * its label and the sampling arguments -- not on the batch it runs in, its position there, the step chunks or the number of devices.
+ *
+ * THE NOISE DEFINITION (all integers unsigned 32-bit, all floating point IEEE binary32 with round-to-nearest, no fused multiply-add):
+ *   generator  Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123): ten rounds of
+ *                (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),  M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+ *              hi / lo = the upper / lower 32 bits of the 64-bit product; between rounds k0 += 0x9E3779B9, k1 += 0xBB67AE85 (mod 2^32).
+ *   key        (k0, k1) = (low dword, high dword) of the sample's seed (int64 on the device: the bit pattern of an unsigned 64-bit value).
+ *   counter    slot = position * m + group within the sample (0 .. n m - 1), step = the absolute step index of the run (a step chunk does not
+ *              change it), class c in 0 .. C - 1:
+ *                categorical stream: (c0, c1, c2, c3) = (c >> 2, slot, step, 0); class c takes output word c & 3;
+ *                confidence stream : (c0, c1, c2, c3) = (0, slot, step, 1); output word 0.
+ *              Nothing batch-dependent enters: no row index, batch size or chunk offset.
+ *   uniform    of an output word x: u = float((x >> 8) | 1) * 2^-24 -- exact in binary32, in [2^-24, 1 - 2^-24], never 0 or 1.
+ *   categorical draw   q = -logf(u) takes the place of exp_noise[row, c] in argmax((p / psum) / q).  u has 2^23 levels: the race is biased by about
+ *              1e-7 relative, far below what any test of the distribution resolves.
+ *   confidence noise   g = -logf(-logf(u)); the value added to log p[pred] is (g * randomize_temperature) * w_i, two separately rounded products in
+ *              the reference's order (sampling.py:117), w_i = float32(1 - (i + 1) / num_steps) evaluated on the host.
+ *   logf is the accurate single-precision logarithm (at most 3 ulp, the OpenCL bound; in practice 1), as in the confidence itself.
+ *
+ * THE THRESHOLD RULE of a seeded step is the per-sample rule of the edit step above; a run that starts all-masked has num_regen[b] = n m.  The
+ * reference's rule reads sample 0's masked count for the whole batch -- the one remaining coupling between the samples of a batch.  From an
+ * all-masked state every sample has the same masked count as long as no confidence ties at the threshold, so the two rules can differ only on exact
+ * confidence ties (a tie re-masks both slots, and that sample's count then differs from sample 0's).
+ *
+ * mb_sample_step_edit with generated noise: seeds int64 [B] (device), `step` >= 0, conf_weight = w_step.  pred_out may be NULL and must not alias a
+ * token buffer. */
+int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float scale, float temperature, const int64_t* seeds, int step,
+                          float randomize_temperature, float conf_weight, float mask_ratio, const int32_t* num_regen,
+                          const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream);
+/* mb_sample_edit with generated noise, one call for the whole run: init_tokens NULL = every slot masked (then num_regen[b] = n m); seeds int64 [B]
+ * (device); conf_weight = HOST array [num_steps] of the w_i above, indexed by the absolute step like the plan's arrays.  Zero-scale steps, precision
+ * modes, step chunks and their checks, outputs: as in mb_sample_edit (step_tokens holds the steps of this call's chunk); a chunk continues only a
+ * run that a seeded call began. */
+int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
+                     float randomize_temperature, const float* conf_weight, int64_t* step_tokens, int64_t* tokens_out,
+                     float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
+
 /* ---- tokenizer evaluation: TokenizerEvaluator.update, evaluator/evaluator.py:262-375 (scripts/eval_tokenizer.py:137-149) ---------------- *
  * Stateless: the caller owns every buffer (and zeroes its running state once); nothing is allocated, nothing synchronises.
  * Bytes of workspace mb_eval_images needs for this shape (one slot of three doubles per 32 x 32 tile of every image plane); 0 for a shape it

@@ -81,6 +81,12 @@ int mb_set_cu_count(int n);
  * kernel -- among other rules, the kernel's 32-bit byte offsets need M * K * 2 and N * K * 2 below 2^32. */
 int mb_gemm_ht_supported(int epi, int M, int N, int K);
 
+/* The noise a seeded step (mb_sample_step_seeded) generates for itself, from the step kernel's own device function, in the layout of the explicit
+ * path: exp_noise fp32 [B*P, C] = -logf(u) and conf_noise fp32 [B*P] = (-logf(-logf(u)) * randomize_temperature) * conf_weight for samples with seeds
+ * int64 [B], slots 0 .. P - 1, at `step`; exp_u / conf_u (optional, same shapes) = the uniforms themselves.  C <= 4096, P <= 8192. */
+int mb_seeded_noise(const int64_t* seeds, int step, float randomize_temperature, float conf_weight, float* exp_u, float* exp_noise, float* conf_u,
+                    float* conf_noise, int B, int P, int C, mb_stream stream);
+
 /* The lookup quantizer's search on caller buffers (vq.hip): z fp32 [N, K], codebook fp32 [C, K] (K <= 256, 2 <= C <= 65 536), l2 = normalise both;
  * idx int64 [N] = argmin_j ||z - e_j||^2 (ties to the lowest index), dist fp32 [N] (may be NULL) = that squared distance; splits = codebook splits
  * across workgroups (0 = automatic; clamped to [1, min(64, C / 64 rounded up)]). */

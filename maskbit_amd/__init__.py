@@ -5,14 +5,14 @@ from .bert import Bert, LFQBert
 from .conv_vqgan import ConvVQModel
 from .factorization import combine_factorized_tokens, split_factorized_tokens
 from .masking import get_masking_ratio
-from .sampling import sample
+from .sampling import sample, sample_seeded
 from .evaluator import TokenizerEvaluator
 from .lpips import LPIPS
 from .editing import inpaint, sample_from_tokens
 from .validation import MLMLoss, MaskedTokenEvaluator, get_mask_tokens
 from .harness import eval_labels, eval_masked_prediction, eval_reconstruction, generate_uint8, mask_token_for, to_evaluator_uint8
 
-__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "sample", "get_masking_ratio",
+__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "sample", "sample_seeded", "get_masking_ratio",
            "combine_factorized_tokens", "split_factorized_tokens", "eval_labels", "generate_uint8", "mask_token_for", "to_evaluator_uint8",
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS"]

@@ -151,6 +151,16 @@ int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_
   return launched();
 }
 
+int mb_seeded_noise(const int64_t* seeds, int step, float randomize_temperature, float conf_weight, float* exp_u, float* exp_noise, float* conf_u,
+                    float* conf_noise, int B, int P, int C, mb_stream stream) {
+  if (!seeds || !exp_noise || !conf_noise) return fail(-1, "mb_seeded_noise: null argument");
+  if (B <= 0 || P <= 0 || C <= 0 || step < 0) return fail(-1, "mb_seeded_noise: bad sizes");
+  if (exp_u == exp_noise || conf_u == conf_noise) return fail(-1, "mb_seeded_noise: the uniforms and the noise must not alias");
+  if (mb::seeded_noise_dump((hipStream_t)stream, seeds, step, randomize_temperature, conf_weight, exp_u, exp_noise, conf_u, conf_noise, B, P, C))
+    return fail(-1, "mb_seeded_noise: C=%d or P=%d too large", C, P);
+  return launched();
+}
+
 int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream) {
   if (!z || !codebook || !idx) return fail(-1, "mb_vq_argmin: null argument");
   if (int rc = mb::vq_argmin(z, codebook, N, C, K, l2, splits, idx, dist, (hipStream_t)stream)) return rc;

@@ -66,7 +66,8 @@ struct mb_gen {
   // loop state for mb_sample
   // the run mb_sample is in the middle of (step chunks): samples, total steps, guidance flag, the step the next chunk must begin with (-1: no run)
   int loop_B = 0, loop_steps = 0, loop_guided = 0, loop_next = -1;
-  // ... and whether it is an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample, [max_seqs])
+  // ... and its kind: 0 plain, 1 an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample,
+  // [max_seqs]), 2 a SEEDED run (mb_sample_seeded: an edit run whose steps generate their noise)
   int loop_edit = 0;
   int* num_regen = nullptr;
   // precision >= 3: which GEMMs carry the activation-lo set (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down).  Coverage measured on the reference's own runs in round 6
@@ -592,15 +593,18 @@ int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels,
   return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
 }
 
-// (who: the entry point's name in the messages; num_regen != null: the edit step, which reads mask_ratio instead of k_mask_len)
+// (who: the entry point's name in the messages; num_regen != null: the edit step, which reads mask_ratio instead of k_mask_len; seeds != null: the seeded
+// step, which generates its noise from (seeds, step, rand_temp, conf_w) instead of reading exp_noise / conf_noise)
 static int sample_step_checked(const char* who, const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise,
                                const float* conf_noise, int k_mask_len, float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in,
-                               int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  if (!logits_c || !exp_noise || !conf_noise || !tokens_in || !tokens_out) return fail(-1, "%s: null argument", who);
+                               int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream, const int64_t* seeds = nullptr,
+                               int step = 0, float rand_temp = 0.f, float conf_w = 0.f) {
+  if (!logits_c || (!seeds && (!exp_noise || !conf_noise)) || !tokens_in || !tokens_out) return fail(-1, "%s: null argument", who);
   if (tokens_in == tokens_out) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
   if (B <= 0 || n <= 0 || m <= 0 || C <= 0) return fail(-1, "%s: bad sizes", who);
   mb::StepArgs a{logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, tokens_out, pred_out, B, n * m, C};
-  ProfScope p(num_regen ? "sample_step_edit" : "sample_step", (hipStream_t)stream);
+  a.seeds = seeds; a.step = step; a.rand_temp = rand_temp; a.conf_w = conf_w;
+  ProfScope p(seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", (hipStream_t)stream);
   if (mb::sample_step((hipStream_t)stream, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, C, n * m);
   return launched();
 }
@@ -620,16 +624,37 @@ int mb_sample_step_edit(const float* logits_c, const float* logits_u, float scal
                              tokens_out, pred_out, B, n, m, C, stream);
 }
 
+int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float scale, float temperature, const int64_t* seeds, int step,
+                          float randomize_temperature, float conf_weight, float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in,
+                          int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
+  if (!seeds || !num_regen) return fail(-1, "mb_sample_step_seeded: null argument");
+  if (step < 0) return fail(-1, "mb_sample_step_seeded: step = %d is negative", step);
+  if (pred_out && (pred_out == tokens_out || pred_out == tokens_in)) return fail(-1, "mb_sample_step_seeded: pred_out must not alias tokens_in or tokens_out");
+  return sample_step_checked("mb_sample_step_seeded", logits_c, logits_u, scale, temperature, nullptr, nullptr, 0, mask_ratio, num_regen, tokens_in,
+                             tokens_out, pred_out, B, n, m, C, stream, seeds, step, randomize_temperature, conf_weight);
+}
+
 // ================================================================================================
 // whole loop (sampling.py:55-136)
 // ================================================================================================
-// mb_sample (init_tokens = null: the run starts all-masked, the step reads mask_len) and mb_sample_edit (the run starts from init_tokens, the step reads
-// mask_ratio and the per-sample counts the first chunk left in g->num_regen)
+// Where a run's noise comes from: the caller's tensors of this chunk's steps (mb_sample, mb_sample_edit), or the samples' seeds (mb_sample_seeded: the
+// step kernel generates it; conf_weight = host [num_steps], indexed by the absolute step like the plan's arrays)
+struct RunNoise {
+  const float* exp_noise = nullptr; const float* conf_noise = nullptr;
+  const int64_t* seeds = nullptr; float rand_temp = 0.f; const float* conf_weight = nullptr;
+};
+static const char* const kRunKind[3] = {"plain", "edit", "seeded"};
+
+// mb_sample (init_tokens = null: the run starts all-masked, the step reads mask_len), mb_sample_edit (the run starts from init_tokens, the step reads
+// mask_ratio and the per-sample counts the first chunk left in g->num_regen) and mb_sample_seeded (an edit run whose steps generate their noise; null
+// init_tokens: all-masked, num_regen[b] = n m)
 static int sample_run(const char* who, mb_gen* g, mb_dec* d, int num_steps, int use_guidance, const float* scale, const float* temperature, const int* mask_len,
-                      const float* mask_ratio, int step_begin, int step_end, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
-                      const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
-  const bool edit = mask_ratio != nullptr;
-  if (!g || !labels || !exp_noise || !conf_noise || (edit && !init_tokens)) return fail(-1, "%s: null argument", who);
+                      const float* mask_ratio, int step_begin, int step_end, const int64_t* labels, int B, const int64_t* init_tokens, const RunNoise& nz,
+                      int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
+  const bool edit = mask_ratio != nullptr, seeded = nz.seeds != nullptr;
+  const int kind = seeded ? 2 : edit ? 1 : 0;
+  if (!g || !labels || (seeded ? !nz.conf_weight : (!nz.exp_noise || !nz.conf_noise || (edit && !init_tokens)))) return fail(-1, "%s: null argument", who);
+  if (seeded && !edit) return fail(-1, "%s: incomplete plan", who);
   if (!scale || !temperature || !(edit ? (const void*)mask_ratio : (const void*)mask_len) || num_steps <= 0) return fail(-1, "%s: incomplete plan", who);
   const int nbf = use_guidance ? 2 * B : B;
   if (B <= 0 || nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
@@ -644,15 +669,18 @@ static int sample_run(const char* who, mb_gen* g, mb_dec* d, int num_steps, int 
   const int s0 = step_end > 0 ? step_begin : 0, s1 = step_end > 0 ? step_end : num_steps;
   if (s0 < 0 || s1 > num_steps || s0 >= s1) return fail(-1, "%s: step chunk [%d, %d) outside [0, %d)", who, s0, s1, num_steps);
   // A run fed in chunks keeps its token state in the engine: a chunk is accepted only as the exact continuation of the run in progress (same batch,
-  // plan length, guidance flag and kind -- plain or edit --, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
+  // plan length, guidance flag and kind -- plain, edit or seeded --, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
   if (s0 == 0) {
-    if (edit) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
-    else mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
-    g->loop_B = B; g->loop_steps = num_steps; g->loop_guided = use_guidance != 0; g->loop_edit = edit;
+    if (init_tokens) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
+    else {
+      mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
+      if (seeded) mb::edit_load_tokens(s, g->tok_a, nullptr, g->num_regen, B, (int)P, C);          // the per-sample rule from the all-masked state: num_regen[b] = n m
+    }
+    g->loop_B = B; g->loop_steps = num_steps; g->loop_guided = use_guidance != 0; g->loop_edit = kind;
   }
-  else if (g->loop_next != s0 || g->loop_B != B || g->loop_steps != num_steps || g->loop_guided != (use_guidance != 0) || g->loop_edit != (int)edit)
-    return fail(-1, "%s: step chunk [%d, %d) of a %d-step %s run with B = %d does not continue the run in progress (next step %d of %d, B = %d, %s)",
-                who, s0, s1, num_steps, edit ? "edit" : "plain", B, g->loop_next, g->loop_steps, g->loop_B, g->loop_edit ? "an edit run" : "a plain run");
+  else if (g->loop_next != s0 || g->loop_B != B || g->loop_steps != num_steps || g->loop_guided != (use_guidance != 0) || g->loop_edit != kind)
+    return fail(-1, "%s: step chunk [%d, %d) of a %d-step %s run with B = %d does not continue the run in progress (next step %d of %d, B = %d, %s %s run)",
+                who, s0, s1, num_steps, kRunKind[kind], B, g->loop_next, g->loop_steps, g->loop_B, g->loop_edit == 1 ? "an" : "a", kRunKind[g->loop_edit]);
   g->loop_next = -1;                                   // (set again below when this chunk has been enqueued and more follow)
   int64_t* cur = (s0 & 1) ? g->tok_b : g->tok_a;
   int64_t* nxt = (s0 & 1) ? g->tok_a : g->tok_b;
@@ -677,10 +705,12 @@ static int sample_run(const char* who, mb_gen* g, mb_dec* d, int num_steps, int 
     if (rc) { g->cfg_labels_ready = nullptr; return rc; }
     const size_t k = (size_t)(i - s0);                 // the noise / step_tokens buffers hold this chunk's steps
     int64_t* pred = step_tokens ? step_tokens + k * B * P : g->pred;
-    rc = edit ? mb_sample_step_edit(lc, lu, scale[i], temperature[i], exp_noise + k * B * P * C, conf_noise + k * B * P, mask_ratio[i], g->num_regen,
-                                    cur, nxt, pred, B, n, m, C, stream)
-              : mb_sample_step(lc, lu, scale[i], temperature[i], exp_noise + k * B * P * C, conf_noise + k * B * P, mask_len[i], cur, nxt, pred, B, n, m,
-                               C, stream);
+    if (seeded) rc = mb_sample_step_seeded(lc, lu, scale[i], temperature[i], nz.seeds, i, nz.rand_temp, nz.conf_weight[i], mask_ratio[i], g->num_regen,
+                                           cur, nxt, pred, B, n, m, C, stream);
+    else rc = edit ? mb_sample_step_edit(lc, lu, scale[i], temperature[i], nz.exp_noise + k * B * P * C, nz.conf_noise + k * B * P, mask_ratio[i], g->num_regen,
+                                         cur, nxt, pred, B, n, m, C, stream)
+                   : mb_sample_step(lc, lu, scale[i], temperature[i], nz.exp_noise + k * B * P * C, nz.conf_noise + k * B * P, mask_len[i], cur, nxt, pred, B, n, m,
+                                    C, stream);
     if (rc) { g->cfg_labels_ready = nullptr; return rc; }
     last_pred = pred;
     int64_t* t = cur; cur = nxt; nxt = t;
@@ -706,14 +736,25 @@ int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* l
               uint8_t* img_nhwc_u8, mb_stream stream) {
   if (!plan) return fail(-1, "mb_sample: null argument");
   return sample_run("mb_sample", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, plan->mask_len, nullptr, plan->step_begin,
-                    plan->step_end, labels, B, nullptr, exp_noise, conf_noise, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+                    plan->step_end, labels, B, nullptr, RunNoise{exp_noise, conf_noise}, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
 }
 
 int mb_sample_edit(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
                    const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
   if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_edit: %s", plan ? "incomplete plan" : "null argument");
   return sample_run("mb_sample_edit", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, nullptr, plan->mask_ratio, plan->step_begin,
-                    plan->step_end, labels, B, init_tokens, exp_noise, conf_noise, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+                    plan->step_end, labels, B, init_tokens, RunNoise{exp_noise, conf_noise}, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+}
+
+int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
+                     float randomize_temperature, const float* conf_weight, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
+                     uint8_t* img_nhwc_u8, mb_stream stream) {
+  if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_seeded: %s", plan ? "incomplete plan" : "null argument");
+  if (!seeds || !conf_weight) return fail(-1, "mb_sample_seeded: null argument");
+  RunNoise nz;
+  nz.seeds = seeds; nz.rand_temp = randomize_temperature; nz.conf_weight = conf_weight;
+  return sample_run("mb_sample_seeded", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, nullptr, plan->mask_ratio, plan->step_begin,
+                    plan->step_end, labels, B, init_tokens, nz, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
 }
 
 }  // extern "C"

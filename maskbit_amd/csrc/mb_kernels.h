@@ -166,10 +166,20 @@ struct StepArgs {
   int64_t* tokens;           // [B, n*m] out (must not alias tokens_in)
   int64_t* pred;             // [B, n*m] out (may be null)
   int B, P /* n*m */, C;
+  // seeds != null: the SEEDED step (mb_sample_step_seeded) -- exp_noise / conf_noise are not read; the kernel computes both values from
+  // (seeds[b], step, slot, class) as include/maskbit_hip.h defines them: int64 [B] (device) = the samples' 64-bit seeds, step = the absolute step of
+  // the run, rand_temp = randomize_temperature, conf_w = float32(1 - (step + 1) / num_steps).  Needs the per-sample threshold rule (num_regen).
+  const int64_t* seeds = nullptr;
+  int step = 0;
+  float rand_temp = 0.f, conf_w = 0.f;
 };
 // num_regen != null: the EDIT step (mb_sample_step_edit) -- per sample b the mask length is floor(mask_ratio * num_regen[b]), the masked count is the
 // sample's own, and a sample with fewer than two masked slots is not re-masked; a.k_mask_len is not read.
 int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in, const int* num_regen = nullptr, float mask_ratio = 0.f);
+// The noise of a seeded step in the explicit path's layout, from the step kernel's own device function: exp_u / exp_noise [B*P, C], conf_u / conf_noise
+// [B*P] (each may be null).  -1: C or P beyond the step kernel's.
+int seeded_noise_dump(hipStream_t s, const int64_t* seeds, int step, float rand_temp, float conf_w, float* exp_u, float* exp_noise, float* conf_u,
+                      float* conf_noise, int B, int P, int C);
 
 // ---- small integer helpers of the loop (sampling.py:65, factorization.py:7-24) -------------------
 void fill_i64(hipStream_t s, int64_t* dst, int64_t value, size_t n);

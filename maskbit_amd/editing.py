@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
-from .sampling import EditPlan, build_edit_plan, check_tokenizer, run_chunked
+from .sampling import EditPlan, build_edit_plan, check_seeds, check_tokenizer, run_chunked, run_seeded
 
 __all__ = ["sample_from_tokens", "inpaint", "build_edit_plan"]
 
@@ -63,12 +63,15 @@ def sample_from_tokens(
     guidance_annealing: Text = "none",
     use_sampling_annealing: bool = False,
     scale_pow: float = 4.0,
+    seeds=None,
 ) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """``sample()`` from a partly known token map: ``init_tokens`` int64 [B, n, m] holds ``model.mask_token`` at the slots to regenerate and a token
     in [0, mask_token) everywhere else; known slots come back unchanged in every step's prediction.  Same return value as ``sample()``
     -- ``(image [B,3,H,W] float32 unclamped, [pred tokens per step])`` -- and the same random-number protocol (a full [B*n*m, C] exponential and a
     [B, n, m] Gumbel draw per step, whatever the mask): with every slot masked the call equals ``sample()`` under the same seed.
-    Host-resident tokens are range-checked; device-resident ones are clamped to [0, mask_token] on the device, with no host synchronisation."""
+    Host-resident tokens are range-checked; device-resident ones are clamped to [0, mask_token] on the device, with no host synchronisation.
+    ``seeds`` (one per sample, as for ``sample_seeded``): the steps generate their noise from the seeds instead -- nothing is drawn, no generator is
+    consumed, and with every slot masked the call equals ``sample_seeded``."""
     _check_models(model, vqgan_model, "sample_from_tokens")
     n, m = model.seq_len, model.splits
     if not isinstance(init_tokens, torch.Tensor) or init_tokens.dtype != torch.int64:
@@ -79,11 +82,16 @@ def sample_from_tokens(
     if init_tokens.device.type == "cpu" and init_tokens.numel() and (int(init_tokens.min()) < 0 or int(init_tokens.max()) > model.mask_token):
         raise ValueError(f"token outside [0, {model.mask_token}] (mask_token = {model.mask_token} marks a slot to regenerate)")
     _check_edit_labels(model, labels, B)
+    if seeds is not None:
+        seeds = check_seeds(seeds, B)
     plan = _edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     dev = model._require_cuda("sample_from_tokens")
     model.eval()
     vqgan_model.eval()
     tokens = init_tokens.to(dev).contiguous()
+    if seeds is not None:
+        img, _, step_tokens, _ = run_seeded(model, vqgan_model, labels.to(dev), plan, seeds, randomize_temperature, init_tokens=tokens)
+        return img, list(step_tokens.unbind(0))
     img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, init_tokens=tokens)
     return img, list(step_tokens.unbind(0))
 
@@ -117,13 +125,14 @@ def inpaint(
     guidance_annealing: Text = "none",
     use_sampling_annealing: bool = False,
     scale_pow: float = 4.0,
+    seeds=None,
 ):
     """Regenerate the pixels of ``images`` (float [B, C, H, W] in [0, 1]) where ``regenerate`` (bool or uint8 [B, H, W] or [B, 1, H, W]) is set,
     class-conditionally on ``labels``; the rest of the image is the context.  A token is regenerated when any pixel of its stride x stride block is.
     -> ``(image, codes int64 [B, n], token_mask bool [B, H/stride, W/stride])``; ``image`` is float32 NCHW (unclamped inside the mask, as ``sample()``
     returns it), or uint8 NHWC = trunc(clamp(x, 0, 1) * 255) with ``return_uint8``.  ``keep_known_pixels`` puts the input's own pixels back outside
     the mask (bit for bit); without it the image is the decoder's output for ``codes`` everywhere -- kept tokens reconstruct their region, they do not
-    copy it."""
+    copy it.  ``seeds`` (one per sample, as for ``sample_seeded``): the steps generate their noise from the seeds instead of torch's generators."""
     _check_models(model, vqgan_model, "inpaint")
     if vqgan_model.quantizer_type == "lookup" and vqgan_model.codebook_size != 2 ** model.bits:
         raise ValueError(f"the tokenizer's codebook holds {vqgan_model.codebook_size} entries, the generator reads codes of 2**{model.bits}: "
@@ -139,6 +148,8 @@ def inpaint(
     B, ch, H, W = images.shape
     regenerate = _pixel_mask(regenerate, B, H, W)
     _check_edit_labels(model, labels, B)
+    if seeds is not None:
+        seeds = check_seeds(seeds, B)
     plan = _edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     dev = model._require_cuda("inpaint")
     model.eval()
@@ -161,8 +172,12 @@ def inpaint(
         slot_mask = token_mask.reshape(B, n, 1).expand(B, n, m).contiguous()         # every group of a regenerated cell
         _lib.check(lib.mb_edit_init(idx.data_ptr(), slot_mask.data_ptr(), tokens.data_ptr(), num_regen.data_ptr(), B, n, m, C_, stream), "mb_edit_init")
     direct_u8 = return_uint8 and not keep_known_pixels                                # the decoder's own uint8 epilogue
-    gen, u8, _, codes = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, init_tokens=tokens, want_steps=False,
-                                    want_image=not direct_u8, want_u8=direct_u8)
+    if seeds is not None:
+        gen, u8, _, codes = run_seeded(model, vqgan_model, labels.to(dev), plan, seeds, randomize_temperature, want_steps=False,
+                                       want_image=not direct_u8, want_u8=direct_u8, init_tokens=tokens)
+    else:
+        gen, u8, _, codes = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, init_tokens=tokens, want_steps=False,
+                                        want_image=not direct_u8, want_u8=direct_u8)
     if keep_known_pixels:
         out = None if return_uint8 else torch.empty_like(gen)
         u8 = torch.empty((B, H, W, ch), dtype=torch.uint8, device=dev) if return_uint8 else None

@@ -20,7 +20,7 @@ import torch
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
 from .factorization import split_factorized_tokens
-from .sampling import build_plan, check_tokenizer, run_chunked, _ForcedPlan
+from .sampling import build_plan, check_seeds, check_tokenizer, run_chunked, run_seeded, seeded_plan, _ForcedPlan
 from .validation import MaskedTokenEvaluator, get_mask_tokens
 
 
@@ -39,11 +39,14 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
                    softmax_temperature: float = 1.0, randomize_temperature: float = 4.5, mask_schedule_strategy: Text = "linear",
                    num_steps: int = 12, guidance_scale: float = 3.0, guidance_annealing: Text = "none",
                    use_sampling_annealing: bool = False, scale_pow: float = 4.0,
-                   total_samples: Optional[int] = None, return_codes: bool = False) -> Iterator[np.ndarray]:
+                   total_samples: Optional[int] = None, return_codes: bool = False, seed: Optional[int] = None) -> Iterator[np.ndarray]:
     """Yield ``total_samples // batchsize`` arrays ``uint8 [batchsize, H, W, 3]`` (host memory), batch *i* generated for
     ``labels[batchsize * i : batchsize * (i + 1)]`` exactly as eval_maskbit.py:111-135 does.  Each yielded array is a fresh copy
     (the reference appends them to a list).  ``return_codes=True`` yields ``(images, codes int64 [batchsize, n])`` -- the combined
-    tokens each image was decoded from (what the reference's evaluator takes as ``codebook_indices``, evaluator.py:536)."""
+    tokens each image was decoded from (what the reference's evaluator takes as ``codebook_indices``, evaluator.py:536).
+    ``seed`` (an int in [0, 2**64)): seeded sampling (``sample_seeded``) -- image ``j`` of the run (global index) is generated from the seed
+    ``(seed + j) mod 2**64``, so the images do not depend on ``batchsize`` and any one of them can be regenerated alone; torch's generators are not
+    consumed."""
     if not isinstance(model, LFQBert) or not isinstance(vqgan_model, ConvVQModel):
         raise TypeError("generate_uint8() needs a maskbit_amd generator and tokenizer")
     check_tokenizer(model, vqgan_model)
@@ -60,6 +63,10 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
                       use_sampling_annealing, mask_schedule_strategy)
     if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
         plan = _ForcedPlan(plan)
+    if seed is not None:
+        check_seeds([seed], 1)
+        run_seeds = check_seeds([(seed + j) % (1 << 64) for j in range(nbatch * batchsize)], nbatch * batchsize).to(dev)      # one copy for the whole run
+        plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     pinned = [None, None]
@@ -73,7 +80,10 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
 
     for i in range(nbatch):
         y = labels[batchsize * i: batchsize * (i + 1)].long()
-        _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, want_steps=False, want_image=False, want_u8=True)
+        if seed is not None:
+            _, u8, _, codes = run_seeded(model, vqgan_model, y, plan, run_seeds[batchsize * i: batchsize * (i + 1)], randomize_temperature, want_steps=False, want_image=False, want_u8=True)
+        else:
+            _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, want_steps=False, want_image=False, want_u8=True)
         slot = i & 1
         if pinned[slot] is None or pinned[slot].shape != u8.shape:
             pinned[slot] = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)

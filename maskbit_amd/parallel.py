@@ -14,6 +14,9 @@ draw is ~12 ms per step at a global batch of 512), so it is the mode for REPRODU
 the throughput mode.  ``noise="rank"`` (the default) draws only the local shard's noise: the cost per rank does
 not grow with the world size; the caller seeds each rank differently (``torch.manual_seed(seed + rank)``, as
 bench.py does), otherwise all ranks would sample the same images.
+``noise="seeded"`` with ``seeds=`` (one 64-bit seed per sample of the GLOBAL batch) needs none of this: the step kernel computes each sample's
+noise from its seed (``sample_seeded``), so a rank runs ``seeds[lo:hi]``, no rank draws another's noise, an empty shard has no generator to keep in
+step, and the images are identical for any world size.
 When the batch divides evenly over the ranks a batch costs exactly ONE collective (``all_gather_into_tensor``
 of the uint8 block) and no host synchronisation; only ragged batches exchange block sizes first.
 """
@@ -78,15 +81,21 @@ def gather_images(local: torch.Tensor, group=None, equal: Optional[bool] = None)
 def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Optional[str] = None, group=None,
                    num_steps: int = 64, guidance_scale: float = 7.1, guidance_annealing: str = "cosine", scale_pow: float = 3.0,
                    softmax_temperature: float = 1.0, use_sampling_annealing: bool = False, randomize_temperature: float = 8.2,
-                   mask_schedule_strategy: str = "arccos") -> torch.Tensor:
+                   mask_schedule_strategy: str = "arccos", seeds=None) -> torch.Tensor:
     """Sample ``len(global_labels)`` images across the process group; every rank returns all images,
     uint8 NHWC, identical on every rank (and, with ``noise="batch"``, identical to a 1-GPU run of the same seed; see the module docstring).
     ``noise`` left at None means "rank" (every rank draws its own shard's noise from ITS generators): with more than one rank this warns once,
     because a caller that seeds every rank identically -- what ``noise="batch"``, the default until round 3, wanted -- would then draw the same
-    noise on every rank.  Pass ``noise="rank"`` (and seed the ranks differently) or ``noise="batch"`` explicitly."""
+    noise on every rank.  Pass ``noise="rank"`` (and seed the ranks differently) or ``noise="batch"`` explicitly.
+    ``noise="seeded"`` with ``seeds`` (one per global sample, as for ``sample_seeded``): sample ``j`` is generated from ``seeds[j]`` on whichever
+    rank owns it -- the same images for any world size, and torch's generators are not consumed."""
     import torch.distributed as dist
-    from .sampling import _ForcedPlan, build_plan, check_tokenizer, draw_noise, plan_arrays, run_loop, step_chunks
+    from .sampling import _ForcedPlan, build_plan, check_seeds, check_tokenizer, draw_noise, plan_arrays, run_loop, run_seeded, seeded_plan, step_chunks
     check_tokenizer(model, vqgan_model)
+    if (noise == "seeded") != (seeds is not None):
+        raise ValueError("noise='seeded' and seeds= go together")
+    if seeds is not None:
+        seeds = check_seeds(seeds, int(global_labels.numel()))
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     B = int(global_labels.numel())
@@ -97,6 +106,14 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
     if guidance_scale != 0.0 and not any(a != 0.0 for a in plan[0]):
         plan = _ForcedPlan(plan)                      # as sample(): the CFG forward runs even when every annealed scale is 0
     dev = model.device
+    if noise == "seeded":
+        if hi == lo:                                  # more ranks than samples: an empty block, and no generator to keep in step
+            side = int(round(n ** 0.5)) << (vqgan_model.num_resolutions - 1)
+            return gather_images(torch.empty((0, side, side, vqgan_model.num_channels), dtype=torch.uint8, device=dev), group)
+        splan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+        _, u8, _, _ = run_seeded(model, vqgan_model, global_labels[lo:hi].to(dev), splan, seeds[lo:hi].contiguous(), randomize_temperature,
+                                 want_steps=False, want_image=False, want_u8=True)
+        return gather_images(u8, group, equal=(B % world == 0) or None)
     if noise is None:
         noise = "rank"
         global _WARNED_DEFAULT_NOISE
@@ -106,7 +123,7 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
                           "seed the ranks differently (torch.manual_seed(seed + rank)), or pass noise='batch' for the single-device-identical mode",
                           stacklevel=2)
     if noise not in ("batch", "rank"):
-        raise ValueError("noise must be 'batch' or 'rank'")
+        raise ValueError("noise must be 'batch', 'rank' or 'seeded'")
     nb = B if noise == "batch" else hi - lo           # the batch the noise is drawn for; chunked by steps to bound its memory (sampling.step_chunks)
     if hi == lo:                                      # more ranks than samples: this rank contributes an empty block to the gather
         if noise == "batch":

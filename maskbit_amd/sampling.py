@@ -259,6 +259,125 @@ def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.T
     return img, u8, step_tokens, codes
 
 
+def check_seeds(seeds, num_samples: int) -> torch.Tensor:
+    """``seeds`` -- a length-``num_samples`` sequence of Python ints in [0, 2**64), or a one-dimensional int64 tensor holding those bit patterns -- as
+    the int64 tensor ``mb_sample_seeded`` reads (a tensor stays on its device: nothing is copied or synchronised).  A wrong length, type or range
+    raises ``ValueError``; no device is touched."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int64 or seeds.dim() != 1:
+            raise ValueError(f"a seeds tensor must be one-dimensional int64 (the bit patterns of the 64-bit seeds), got {seeds.dtype} {tuple(seeds.shape)}")
+        if seeds.shape[0] != num_samples:
+            raise ValueError(f"{seeds.shape[0]} seeds for {num_samples} samples")
+        return seeds.detach().contiguous()
+    try:
+        seeds = list(seeds)
+    except TypeError:
+        raise ValueError(f"seeds must be a sequence of {num_samples} ints or an int64 tensor, got {type(seeds).__name__}") from None
+    if len(seeds) != num_samples:
+        raise ValueError(f"{len(seeds)} seeds for {num_samples} samples")
+    out = []
+    for v in seeds:
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"a seed must be an int in [0, 2**64), got {type(v).__name__}")
+        if not 0 <= v < 1 << 64:
+            raise ValueError(f"seed {v} outside [0, 2**64)")
+        out.append(v - (1 << 64) if v >= 1 << 63 else v)
+    return torch.tensor(out, dtype=torch.int64)
+
+
+def run_seeded(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan, seeds: torch.Tensor, randomize_temperature: float,
+               want_steps: bool = True, want_image: bool = True, want_u8: bool = False, step_range: Optional[Tuple[int, int]] = None,
+               init_tokens: Optional[torch.Tensor] = None):
+    """One ``mb_sample_seeded`` call: ``run_loop`` for an ``EditPlan`` whose steps generate their own noise from ``seeds`` (int64 [B], what
+    ``check_seeds`` returns).  No noise tensor exists, no generator is consumed, nothing is drawn on the host.  ``init_tokens`` None: the run starts
+    all-masked.  -> (image or None, uint8 NHWC or None, step tokens or None, codes [B,n] or None), as ``run_loop``."""
+    dev = model._require_cuda("sample_seeded")
+    if not getattr(plan, "edit", False):
+        raise ValueError("a seeded run takes an edit plan (build_edit_plan): it re-masks by the per-sample rule")
+    scale, temp, ratio = plan
+    nsteps = len(scale)
+    sb, se = step_range if step_range is not None else (0, nsteps)
+    B = labels.shape[0]
+    n, m = model.seq_len, model.splits
+    if seeds.shape != (B,) or seeds.dtype != torch.int64:
+        raise ValueError(f"seeds must be int64 [{B}]")
+    if init_tokens is not None and (init_tokens.shape != (B, n, m) or init_tokens.dtype != torch.int64 or init_tokens.device.type != dev.type
+                                    or not init_tokens.is_contiguous()):
+        raise ValueError(f"init_tokens must be a contiguous int64 [{B}, {n}, {m}] tensor on {dev}")
+    c_scale, c_temp, c_ratio, use_cfg = plan_arrays(plan)
+    conf_w = (C.c_float * nsteps)(*[1 - (i + 1) / nsteps for i in range(nsteps)])       # float32(1 - progress), sampling.py:117
+    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    # (host-resident seeds: a pageable-memory copy would hold the host until the device has run everything enqueued before it -- the previous batch --
+    # and the device then idles while this run is enqueued; pinned and asynchronous, as _to_device_early's)
+    seeds = seeds.to(dev) if seeds.device.type != "cpu" else seeds.pin_memory().to(dev, non_blocking=True)
+    step_tokens = torch.empty((se - sb, B, n, m), dtype=torch.int64, device=dev) if want_steps else None
+    last = se == nsteps
+    codes = torch.empty((B, n), dtype=torch.int64, device=dev) if last else None
+    img = u8 = hdec = None
+    if last and vqgan_model is not None and (want_image or want_u8):
+        side = int(round(n ** 0.5))
+        res = side << (vqgan_model.num_resolutions - 1)
+        if want_image:
+            img = torch.empty((B, vqgan_model.num_channels, res, res), dtype=torch.float32, device=dev)
+        if want_u8:
+            u8 = torch.empty((B, res, res, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
+        hdec = vqgan_model.engine(B, side)
+    hgen = model.engine(2 * B if use_cfg else B)
+    cplan = _lib.EditPlan(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_ratio, sb if step_range is not None else 0, se if step_range is not None else 0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mb_sample_seeded(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, ptr(init_tokens), seeds.data_ptr(),
+                                                float(randomize_temperature), conf_w, ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
+                                                torch.cuda.current_stream().cuda_stream), "mb_sample_seeded")
+    return img, u8, step_tokens, codes
+
+
+def seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy) -> EditPlan:
+    """The plan of a seeded run: ``build_edit_plan`` (per-sample masking ratios), with the CFG forward forced when every annealed scale is 0, as in ``sample()``."""
+    plan = build_edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
+        plan = EditPlan(plan, force_guidance=True)
+    return plan
+
+
+@torch.no_grad()
+def sample_seeded(
+    model,
+    vqgan_model,
+    seeds,
+    labels: torch.Tensor,
+    *,
+    softmax_temperature: float = 1.0,
+    randomize_temperature: float = 4.5,
+    mask_schedule_strategy: Text = "linear",
+    num_steps: int = 12,
+    guidance_scale: float = 3.0,
+    guidance_annealing: Text = "none",
+    use_sampling_annealing: bool = False,
+    scale_pow: float = 4.0,
+) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """``sample()`` with per-sample seeds: sample ``b`` is generated for ``labels[b]`` from ``seeds[b]`` (a Python int in [0, 2**64), or the int64 bit
+    pattern in a tensor), and its tokens and image depend on that seed, that label and the sampling arguments alone -- not on the batch size, its
+    position in the batch or anything drawn before.  The step kernel computes its noise from (seed, step, slot, class) with a counter-based generator
+    (include/maskbit_hip.h): no noise tensor is created, neither the CPU nor the device torch generator is consumed, and the whole run is one
+    ``mb_sample_seeded`` call.  The samples are re-masked by the per-sample rule of the edit step.  Same return value as ``sample()``; the noise is
+    NOT the reference's, so a seeded run does not reproduce a ``sample()`` run."""
+    if not isinstance(model, LFQBert):
+        raise TypeError(f"sample_seeded() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
+    if not isinstance(vqgan_model, ConvVQModel):
+        raise TypeError(f"sample_seeded() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
+    check_tokenizer(model, vqgan_model)
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"labels must be a tensor of class ids, got {type(labels).__name__}")
+    seeds = check_seeds(seeds, int(labels.numel()))
+    model._check_labels(labels)
+    plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    model.eval()
+    vqgan_model.eval()
+    img, _, step_tokens, _ = run_seeded(model, vqgan_model, labels.reshape(-1), plan, seeds, randomize_temperature)
+    return img, list(step_tokens.unbind(0))
+
+
 @torch.no_grad()
 def sample(
     model,
