@@ -63,12 +63,19 @@ struct mb_gen {
   std::vector<uint8_t*> w4lo, w4los;                                                     // [4 * layer + {qkv, o, 1, 2}]
   F4Buf att4, h4;                                       // e2m1 of the conditional attention outputs / FFN hiddens
   F4Buf attl4, hl4;                                     // precision 4: e2m1 of their fp16 LO HALVES (activation-lo sets of out-proj / FFN-down)
-  // loop state for mb_sample
-  // the run mb_sample is in the middle of (step chunks): samples, total steps, guidance flag, the step the next chunk must begin with (-1: no run)
-  int loop_B = 0, loop_steps = 0, loop_guided = 0, loop_next = -1;
-  // ... and its kind: 0 plain, 1 an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample,
-  // [max_seqs]), 2 a SEEDED run (mb_sample_seeded: an edit run whose steps generate their noise)
-  int loop_edit = 0;
+  // The run the sampling loop is in the middle of (step chunks).  id = what every chunk of one run shares: samples, total steps, guidance flag and
+  // kind -- 0 plain, 1 an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample, [max_seqs]),
+  // 2 a SEEDED run (mb_sample_seeded: an edit run whose steps generate their noise); next = the step the next chunk must begin with (-1: no run).
+  // cfg_labels / cfg_B: during one call of the loop, gen_forward_cfg's lab_cfg / drop_cfg already hold [labels | labels] / [0 | 1] for this many pairs.
+  struct Run {
+    struct Id {
+      int B = 0, steps = 0, guided = 0, kind = 0;
+      bool operator==(const Id& o) const { return B == o.B && steps == o.steps && guided == o.guided && kind == o.kind; }
+    } id;
+    int next = -1;
+    const int64_t* cfg_labels = nullptr;
+    int cfg_B = 0;
+  } run;
   int* num_regen = nullptr;
   // precision >= 3: which GEMMs carry the activation-lo set (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down).  Coverage measured on the reference's own runs in round 6
   // (profiles/r06_coverage.md: four 14-bit / 256-step runs, four 12-bit runs, three trained-like runs; mismatches / guided-forward time of 64 pairs):
@@ -76,8 +83,6 @@ struct mb_gen {
   //   out-proj + FFN-up + FFN-down 241 / 115 / 203 at 33.4;  all four 228 / 116 / 200 at 34.3 -- the QKV set buys nothing (as round 5 found for precision 3).
   // precision 3 = out-proj + FFN-up of every layer (6); precision 4 = + FFN-down (14).  mb_gen_set_alo (diagnostic) narrows within what the handle was created with.
   int alo_mask = 0, alo_mask_built = 0;
-  const int64_t* cfg_labels_ready = nullptr;            // gen_forward_cfg: lab_cfg / drop_cfg already hold [labels | labels] / [0 | 1] for this many pairs
-  int cfg_ready_B = 0;
   int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
   uint8_t* drop_cfg = nullptr;
   float* logits = nullptr;
@@ -340,7 +345,7 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
     // (the fused pair embedding reads the conditional tokens only: the twins' copy is needed by the two-kernel path and the plain fallback)
     if (!(pair && !g->c.embed_tables && g->c.bits <= 24))
       HIP_TRY(hipMemcpyAsync(g->tok_cfg + nc * P, tokens + (size_t)b0 * P, nc * P * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (!(nc == B && g->cfg_labels_ready == labels && g->cfg_ready_B == B)) {   // (mb_sample marks them ready for the steps of one call)
+    if (!(nc == B && g->run.cfg_labels == labels && g->run.cfg_B == B)) {       // (the sampling loop marks them ready for the steps of one call)
       HIP_TRY(hipMemcpyAsync(g->lab_cfg, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemcpyAsync(g->lab_cfg + nc, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemsetAsync(g->drop_cfg, 0, nc, s));
@@ -593,35 +598,39 @@ int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels,
   return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
 }
 
-// (who: the entry point's name in the messages; num_regen != null: the edit step, which reads mask_ratio instead of k_mask_len; seeds != null: the seeded
-// step, which generates its noise from (seeds, step, rand_temp, conf_w) instead of reading exp_noise / conf_noise)
-static int sample_step_checked(const char* who, const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise,
-                               const float* conf_noise, int k_mask_len, float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in,
-                               int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream, const int64_t* seeds = nullptr,
-                               int step = 0, float rand_temp = 0.f, float conf_w = 0.f) {
-  if (!logits_c || (!seeds && (!exp_noise || !conf_noise)) || !tokens_in || !tokens_out) return fail(-1, "%s: null argument", who);
-  if (tokens_in == tokens_out) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
-  if (B <= 0 || n <= 0 || m <= 0 || C <= 0) return fail(-1, "%s: bad sizes", who);
-  mb::StepArgs a{logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, tokens_out, pred_out, B, n * m, C};
-  a.seeds = seeds; a.step = step; a.rand_temp = rand_temp; a.conf_w = conf_w;
-  ProfScope p(seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", (hipStream_t)stream);
-  if (mb::sample_step((hipStream_t)stream, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, C, n * m);
+// One step, from the three step entries and from the loop.  who: the entry's name in the messages; num_regen != null: the edit step, which reads
+// mask_ratio instead of a.k_mask_len; a.seeds != null: the seeded step, which generates its noise from (seeds, step, rand_temp, conf_w) instead of
+// reading a.exp_noise / a.conf_noise.  a.tokens is tokens_out, a.pred pred_out, a.P = n m (0: n or m was not positive).
+static int sample_step_checked(const char* who, const mb::StepArgs& a, const int64_t* tokens_in, const int32_t* num_regen, float mask_ratio, hipStream_t s) {
+  if (!a.logits_c || (!a.seeds && (!a.exp_noise || !a.conf_noise)) || !tokens_in || !a.tokens) return fail(-1, "%s: null argument", who);
+  if (tokens_in == a.tokens) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
+  if (a.B <= 0 || a.P <= 0 || a.C <= 0) return fail(-1, "%s: bad sizes", who);
+  ProfScope p(a.seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", s);
+  if (mb::sample_step(s, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, a.C, a.P);
   return launched();
 }
+
+static int step_slots(int n, int m) { return n > 0 && m > 0 ? n * m : 0; }
 
 int mb_sample_step(const float* logits_c, const float* logits_u, float scale, float temperature,
                    const float* exp_noise, const float* conf_noise, int k_mask_len, const int64_t* tokens_in,
                    int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  return sample_step_checked("mb_sample_step", logits_c, logits_u, scale, temperature, exp_noise, conf_noise, k_mask_len, 0.f, nullptr, tokens_in, tokens_out,
-                             pred_out, B, n, m, C, stream);
+  mb::StepArgs a{};
+  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
+  a.exp_noise = exp_noise; a.conf_noise = conf_noise; a.k_mask_len = k_mask_len;
+  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
+  return sample_step_checked("mb_sample_step", a, tokens_in, nullptr, 0.f, (hipStream_t)stream);
 }
 
 int mb_sample_step_edit(const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise, const float* conf_noise,
                         float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m,
                         int C, mb_stream stream) {
   if (!num_regen) return fail(-1, "mb_sample_step_edit: null argument");
-  return sample_step_checked("mb_sample_step_edit", logits_c, logits_u, scale, temperature, exp_noise, conf_noise, 0, mask_ratio, num_regen, tokens_in,
-                             tokens_out, pred_out, B, n, m, C, stream);
+  mb::StepArgs a{};
+  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
+  a.exp_noise = exp_noise; a.conf_noise = conf_noise;
+  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
+  return sample_step_checked("mb_sample_step_edit", a, tokens_in, num_regen, mask_ratio, (hipStream_t)stream);
 }
 
 int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float scale, float temperature, const int64_t* seeds, int step,
@@ -630,131 +639,171 @@ int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float sc
   if (!seeds || !num_regen) return fail(-1, "mb_sample_step_seeded: null argument");
   if (step < 0) return fail(-1, "mb_sample_step_seeded: step = %d is negative", step);
   if (pred_out && (pred_out == tokens_out || pred_out == tokens_in)) return fail(-1, "mb_sample_step_seeded: pred_out must not alias tokens_in or tokens_out");
-  return sample_step_checked("mb_sample_step_seeded", logits_c, logits_u, scale, temperature, nullptr, nullptr, 0, mask_ratio, num_regen, tokens_in,
-                             tokens_out, pred_out, B, n, m, C, stream, seeds, step, randomize_temperature, conf_weight);
+  mb::StepArgs a{};
+  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
+  a.seeds = seeds; a.step = step; a.rand_temp = randomize_temperature; a.conf_w = conf_weight;
+  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
+  return sample_step_checked("mb_sample_step_seeded", a, tokens_in, num_regen, mask_ratio, (hipStream_t)stream);
 }
+
+}  // extern "C"
 
 // ================================================================================================
 // whole loop (sampling.py:55-136)
 // ================================================================================================
+namespace {
+
 // Where a run's noise comes from: the caller's tensors of this chunk's steps (mb_sample, mb_sample_edit), or the samples' seeds (mb_sample_seeded: the
 // step kernel generates it; conf_weight = host [num_steps], indexed by the absolute step like the plan's arrays)
 struct RunNoise {
   const float* exp_noise = nullptr; const float* conf_noise = nullptr;
   const int64_t* seeds = nullptr; float rand_temp = 0.f; const float* conf_weight = nullptr;
 };
-static const char* const kRunKind[3] = {"plain", "edit", "seeded"};
+// What the three run entries differ in.  mask_len (mb_sample: the run starts all-masked) or mask_ratio (an edit run: the step reads the ratio and the
+// per-sample counts the first chunk left in g->num_regen); init_tokens: the tokens an edit run starts from (mb_sample_seeded: may be null = all-masked,
+// num_regen[b] = n m); noise.seeds != null: a seeded run.
+struct RunSpec {
+  const char* who = nullptr;                           // the entry's name in the messages
+  int num_steps = 0, use_guidance = 0, step_begin = 0, step_end = 0;
+  const float* scale = nullptr; const float* temperature = nullptr;
+  const int* mask_len = nullptr; const float* mask_ratio = nullptr;
+  const int64_t* init_tokens = nullptr;
+  RunNoise noise;
+};
+struct RunOut { int64_t* step_tokens; int64_t* codes; float* img_nchw; uint8_t* img_nhwc_u8; };   // each may be null
 
-// mb_sample (init_tokens = null: the run starts all-masked, the step reads mask_len), mb_sample_edit (the run starts from init_tokens, the step reads
-// mask_ratio and the per-sample counts the first chunk left in g->num_regen) and mb_sample_seeded (an edit run whose steps generate their noise; null
-// init_tokens: all-masked, num_regen[b] = n m)
-static int sample_run(const char* who, mb_gen* g, mb_dec* d, int num_steps, int use_guidance, const float* scale, const float* temperature, const int* mask_len,
-                      const float* mask_ratio, int step_begin, int step_end, const int64_t* labels, int B, const int64_t* init_tokens, const RunNoise& nz,
-                      int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
-  const bool edit = mask_ratio != nullptr, seeded = nz.seeds != nullptr;
-  const int kind = seeded ? 2 : edit ? 1 : 0;
-  if (!g || !labels || (seeded ? !nz.conf_weight : (!nz.exp_noise || !nz.conf_noise || (edit && !init_tokens)))) return fail(-1, "%s: null argument", who);
-  if (seeded && !edit) return fail(-1, "%s: incomplete plan", who);
-  if (!scale || !temperature || !(edit ? (const void*)mask_ratio : (const void*)mask_len) || num_steps <= 0) return fail(-1, "%s: incomplete plan", who);
-  const int nbf = use_guidance ? 2 * B : B;
+const char* const kRunKind[3] = {"plain", "edit", "seeded"};
+const char* const kStepEntry[3] = {"mb_sample_step", "mb_sample_step_edit", "mb_sample_step_seeded"};
+
+// (mb_sample_plan and mb_edit_plan differ in their third array alone)
+template <class Plan>
+RunSpec run_spec(const char* who, const Plan& p) {
+  RunSpec r;
+  r.who = who; r.num_steps = p.num_steps; r.use_guidance = p.use_guidance; r.step_begin = p.step_begin; r.step_end = p.step_end;
+  r.scale = p.scale; r.temperature = p.temperature;
+  return r;
+}
+
+// The null checks of the caller's own pointers are the entries'; g and labels are theirs too.
+int sample_run(mb_gen* g, mb_dec* d, const RunSpec& r, const int64_t* labels, int B, const RunOut& out, hipStream_t s) {
+  const char* who = r.who;
+  const RunNoise& nz = r.noise;
+  const bool edit = r.mask_ratio != nullptr, seeded = nz.seeds != nullptr;
+  const int num_steps = r.num_steps;
+  if (!r.scale || !r.temperature || !(edit ? (const void*)r.mask_ratio : (const void*)r.mask_len) || num_steps <= 0) return fail(-1, "%s: incomplete plan", who);
+  const mb_gen::Run::Id id{B, num_steps, r.use_guidance != 0, seeded ? 2 : edit ? 1 : 0};
+  const int nbf = id.guided ? 2 * B : B;
   if (B <= 0 || nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
-  if (!d && (img_nchw || img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
-  hipStream_t s = (hipStream_t)stream;
+  if (!d && (out.img_nchw || out.img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
   const mb_gen_cfg& c = g->c;
   const int n = c.seq, m = c.splits, C = g->C;
   const size_t P = (size_t)n * m;
   // state init (sampling.py:65-71): every position masked; CFG batch = [cond | label-dropped]
   // A run may be fed in step chunks (plan->step_begin / step_end: the noise of a whole 256-step run at batch 100 is 6.7 GB): chunk [0, e) starts from
   // the all-masked state, later chunks continue from the token state the engine kept; exp_noise / conf_noise / step_tokens hold THIS chunk's steps.
-  const int s0 = step_end > 0 ? step_begin : 0, s1 = step_end > 0 ? step_end : num_steps;
+  const int s0 = r.step_end > 0 ? r.step_begin : 0, s1 = r.step_end > 0 ? r.step_end : num_steps;
   if (s0 < 0 || s1 > num_steps || s0 >= s1) return fail(-1, "%s: step chunk [%d, %d) outside [0, %d)", who, s0, s1, num_steps);
   // A run fed in chunks keeps its token state in the engine: a chunk is accepted only as the exact continuation of the run in progress (same batch,
   // plan length, guidance flag and kind -- plain, edit or seeded --, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
+  mb_gen::Run& run = g->run;
   if (s0 == 0) {
-    if (init_tokens) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
+    if (r.init_tokens) mb::edit_load_tokens(s, r.init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
     else {
       mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
       if (seeded) mb::edit_load_tokens(s, g->tok_a, nullptr, g->num_regen, B, (int)P, C);          // the per-sample rule from the all-masked state: num_regen[b] = n m
     }
-    g->loop_B = B; g->loop_steps = num_steps; g->loop_guided = use_guidance != 0; g->loop_edit = kind;
+    run.id = id;
   }
-  else if (g->loop_next != s0 || g->loop_B != B || g->loop_steps != num_steps || g->loop_guided != (use_guidance != 0) || g->loop_edit != kind)
+  else if (!(run.id == id && run.next == s0))
     return fail(-1, "%s: step chunk [%d, %d) of a %d-step %s run with B = %d does not continue the run in progress (next step %d of %d, B = %d, %s %s run)",
-                who, s0, s1, num_steps, kRunKind[kind], B, g->loop_next, g->loop_steps, g->loop_B, g->loop_edit == 1 ? "an" : "a", kRunKind[g->loop_edit]);
-  g->loop_next = -1;                                   // (set again below when this chunk has been enqueued and more follow)
+                who, s0, s1, num_steps, kRunKind[id.kind], B, run.next, run.id.steps, run.id.B, run.id.kind == 1 ? "an" : "a", kRunKind[run.id.kind]);
+  run.next = -1;                                       // (set again below when this chunk has been enqueued and more follow)
   int64_t* cur = (s0 & 1) ? g->tok_b : g->tok_a;
   int64_t* nxt = (s0 & 1) ? g->tok_a : g->tok_b;
   int64_t* last_pred = g->pred;
-  g->cfg_labels_ready = nullptr;
+  // lab_cfg / drop_cfg are marked ready for the steps of this call only: whichever way it returns
+  struct CfgReady { mb_gen::Run& run; ~CfgReady() { run.cfg_labels = nullptr; } } cfg_ready{run};
+  run.cfg_labels = nullptr;
+  mb::StepArgs a{};
+  a.logits_c = g->logits; a.B = B; a.P = (int)P; a.C = C;
+  a.seeds = nz.seeds; a.rand_temp = nz.rand_temp;
   for (int i = s0; i < s1; ++i) {
-    const float* lc = g->logits;
-    const float* lu = nullptr;
     int rc;
     // sampling.py:98-99 combines c + s_i (c - u).  Where the annealed scale s_i is exactly 0 -- the first steps of the cosine schedule: (i / N)^p pi
     // is below float32's cos() resolution -- the unconditional logits do not enter the result (c + 0 (c - u) == c for finite logits), so that
     // forward is not run: the step is the plain conditional forward, bit for bit what the guided expression evaluates to.
     // (precision 4: the guided forward is also the MORE PRECISE conditional forward -- its pair tiles carry the activation-lo sets, the plain tiles do not --
     // and the first, almost fully masked steps are where near-ties flip: the zero-scale steps run it too; its unconditional half is then multiplied by 0)
-    if (use_guidance && (scale[i] != 0.0f || (g->pair_ok && c.precision >= 4))) {
+    if (id.guided && (r.scale[i] != 0.0f || (g->pair_ok && c.precision >= 4))) {
       rc = gen_forward_cfg(g, cur, labels, g->logits, B, s);
-      lu = g->logits + (size_t)B * P * C;
-      if (B <= g->chunk_seqs / 2) { g->cfg_labels_ready = labels; g->cfg_ready_B = B; }   // lab_cfg / drop_cfg stay valid for the rest of this call
+      a.logits_u = g->logits + (size_t)B * P * C;
+      if (B <= g->chunk_seqs / 2) { run.cfg_labels = labels; run.cfg_B = B; }   // lab_cfg / drop_cfg stay valid for the rest of this call
     } else {
       rc = gen_forward(g, cur, labels, nullptr, g->logits, B, s);
+      a.logits_u = nullptr;
     }
-    if (rc) { g->cfg_labels_ready = nullptr; return rc; }
+    if (rc) return rc;
     const size_t k = (size_t)(i - s0);                 // the noise / step_tokens buffers hold this chunk's steps
-    int64_t* pred = step_tokens ? step_tokens + k * B * P : g->pred;
-    if (seeded) rc = mb_sample_step_seeded(lc, lu, scale[i], temperature[i], nz.seeds, i, nz.rand_temp, nz.conf_weight[i], mask_ratio[i], g->num_regen,
-                                           cur, nxt, pred, B, n, m, C, stream);
-    else rc = edit ? mb_sample_step_edit(lc, lu, scale[i], temperature[i], nz.exp_noise + k * B * P * C, nz.conf_noise + k * B * P, mask_ratio[i], g->num_regen,
-                                         cur, nxt, pred, B, n, m, C, stream)
-                   : mb_sample_step(lc, lu, scale[i], temperature[i], nz.exp_noise + k * B * P * C, nz.conf_noise + k * B * P, mask_len[i], cur, nxt, pred, B, n, m,
-                                    C, stream);
-    if (rc) { g->cfg_labels_ready = nullptr; return rc; }
-    last_pred = pred;
+    a.scale = r.scale[i]; a.temperature = r.temperature[i];
+    a.tokens = nxt; a.pred = out.step_tokens ? out.step_tokens + k * B * P : g->pred;
+    if (seeded) { a.step = i; a.conf_w = nz.conf_weight[i]; }
+    else { a.exp_noise = nz.exp_noise + k * B * P * C; a.conf_noise = nz.conf_noise + k * B * P; }
+    if (!edit) a.k_mask_len = r.mask_len[i];
+    rc = sample_step_checked(kStepEntry[id.kind], a, cur, edit ? g->num_regen : nullptr, edit ? r.mask_ratio[i] : 0.f, s);
+    if (rc) return rc;
+    last_pred = a.pred;
     int64_t* t = cur; cur = nxt; nxt = t;
   }
-  g->cfg_labels_ready = nullptr;
   if (s1 < num_steps) {                                // more chunks follow: keep the last predictions only if they are the engine's own buffer
     if (int rc = launched()) return rc;
-    g->loop_next = s1;
+    run.next = s1;
     return 0;
   }
   // combine_factorized_tokens (factorization.py:7-24) on the LAST step's predictions, kept as integers
-  int64_t* codes = tokens_out ? tokens_out : g->codes;
+  int64_t* codes = out.codes ? out.codes : g->codes;
   mb::combine_groups(s, last_pred, codes, (size_t)B * n, m, g->gbits);
   if (d) {
-    int rc = mb_dec_decode(d, codes, img_nchw, img_nhwc_u8, B, stream);
+    int rc = mb_dec_decode(d, codes, out.img_nchw, out.img_nhwc_u8, B, (mb_stream)s);
     if (rc) return rc;
   }
   return launched();
 }
 
+}  // namespace
+
+extern "C" {
+
 int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B, const float* exp_noise,
               const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
               uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!plan) return fail(-1, "mb_sample: null argument");
-  return sample_run("mb_sample", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, plan->mask_len, nullptr, plan->step_begin,
-                    plan->step_end, labels, B, nullptr, RunNoise{exp_noise, conf_noise}, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+  if (!plan || !g || !labels || !exp_noise || !conf_noise) return fail(-1, "mb_sample: null argument");
+  RunSpec r = run_spec("mb_sample", *plan);
+  r.mask_len = plan->mask_len;
+  r.noise.exp_noise = exp_noise; r.noise.conf_noise = conf_noise;
+  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
 }
 
 int mb_sample_edit(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
                    const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
   if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_edit: %s", plan ? "incomplete plan" : "null argument");
-  return sample_run("mb_sample_edit", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, nullptr, plan->mask_ratio, plan->step_begin,
-                    plan->step_end, labels, B, init_tokens, RunNoise{exp_noise, conf_noise}, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+  if (!g || !labels || !exp_noise || !conf_noise || !init_tokens) return fail(-1, "mb_sample_edit: null argument");
+  RunSpec r = run_spec("mb_sample_edit", *plan);
+  r.mask_ratio = plan->mask_ratio;
+  r.init_tokens = init_tokens;
+  r.noise.exp_noise = exp_noise; r.noise.conf_noise = conf_noise;
+  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
 }
 
 int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
                      float randomize_temperature, const float* conf_weight, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
                      uint8_t* img_nhwc_u8, mb_stream stream) {
   if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_seeded: %s", plan ? "incomplete plan" : "null argument");
-  if (!seeds || !conf_weight) return fail(-1, "mb_sample_seeded: null argument");
-  RunNoise nz;
-  nz.seeds = seeds; nz.rand_temp = randomize_temperature; nz.conf_weight = conf_weight;
-  return sample_run("mb_sample_seeded", g, d, plan->num_steps, plan->use_guidance, plan->scale, plan->temperature, nullptr, plan->mask_ratio, plan->step_begin,
-                    plan->step_end, labels, B, init_tokens, nz, step_tokens, tokens_out, img_nchw, img_nhwc_u8, stream);
+  if (!seeds || !conf_weight || !g || !labels) return fail(-1, "mb_sample_seeded: null argument");
+  RunSpec r = run_spec("mb_sample_seeded", *plan);
+  r.mask_ratio = plan->mask_ratio;
+  r.init_tokens = init_tokens;
+  r.noise.seeds = seeds; r.noise.rand_temp = randomize_temperature; r.noise.conf_weight = conf_weight;
+  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
 }
 
 }  // extern "C"

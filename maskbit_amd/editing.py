@@ -17,19 +17,9 @@ from typing import List, Text, Tuple
 import torch
 
 from . import _lib
-from .bert import LFQBert
-from .conv_vqgan import ConvVQModel
-from .sampling import EditPlan, build_edit_plan, check_seeds, check_tokenizer, run_chunked, run_seeded
+from .sampling import build_edit_plan, check_models, check_seeds, run_chunked, seeded_plan
 
 __all__ = ["sample_from_tokens", "inpaint", "build_edit_plan"]
-
-
-def _check_models(model, vqgan_model, what: str) -> None:
-    if not isinstance(model, LFQBert):
-        raise TypeError(f"{what}() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
-    if not isinstance(vqgan_model, ConvVQModel):
-        raise TypeError(f"{what}() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
-    check_tokenizer(model, vqgan_model)
 
 
 def _check_edit_labels(model, labels, B: int) -> None:
@@ -38,14 +28,6 @@ def _check_edit_labels(model, labels, B: int) -> None:
     if labels.numel() != B:
         raise ValueError(f"{labels.numel()} labels for {B} samples")
     model._check_labels(labels)
-
-
-def _edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy):
-    plan = build_edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing,
-                           mask_schedule_strategy)
-    if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
-        plan = EditPlan(plan, force_guidance=True)     # CFG forward still runs when every a_i happens to be 0 (as in sample())
-    return plan
 
 
 @torch.no_grad()
@@ -72,7 +54,7 @@ def sample_from_tokens(
     Host-resident tokens are range-checked; device-resident ones are clamped to [0, mask_token] on the device, with no host synchronisation.
     ``seeds`` (one per sample, as for ``sample_seeded``): the steps generate their noise from the seeds instead -- nothing is drawn, no generator is
     consumed, and with every slot masked the call equals ``sample_seeded``."""
-    _check_models(model, vqgan_model, "sample_from_tokens")
+    check_models(model, vqgan_model, "sample_from_tokens")
     n, m = model.seq_len, model.splits
     if not isinstance(init_tokens, torch.Tensor) or init_tokens.dtype != torch.int64:
         raise TypeError("init_tokens must be an int64 tensor")
@@ -84,15 +66,12 @@ def sample_from_tokens(
     _check_edit_labels(model, labels, B)
     if seeds is not None:
         seeds = check_seeds(seeds, B)
-    plan = _edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     dev = model._require_cuda("sample_from_tokens")
     model.eval()
     vqgan_model.eval()
     tokens = init_tokens.to(dev).contiguous()
-    if seeds is not None:
-        img, _, step_tokens, _ = run_seeded(model, vqgan_model, labels.to(dev), plan, seeds, randomize_temperature, init_tokens=tokens)
-        return img, list(step_tokens.unbind(0))
-    img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, init_tokens=tokens)
+    img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, seeds=seeds, init_tokens=tokens)
     return img, list(step_tokens.unbind(0))
 
 
@@ -133,7 +112,7 @@ def inpaint(
     returns it), or uint8 NHWC = trunc(clamp(x, 0, 1) * 255) with ``return_uint8``.  ``keep_known_pixels`` puts the input's own pixels back outside
     the mask (bit for bit); without it the image is the decoder's output for ``codes`` everywhere -- kept tokens reconstruct their region, they do not
     copy it.  ``seeds`` (one per sample, as for ``sample_seeded``): the steps generate their noise from the seeds instead of torch's generators."""
-    _check_models(model, vqgan_model, "inpaint")
+    check_models(model, vqgan_model, "inpaint")
     if vqgan_model.quantizer_type == "lookup" and vqgan_model.codebook_size != 2 ** model.bits:
         raise ValueError(f"the tokenizer's codebook holds {vqgan_model.codebook_size} entries, the generator reads codes of 2**{model.bits}: "
                          "an encoded image could hold codes the generator has no tokens for")
@@ -150,7 +129,7 @@ def inpaint(
     _check_edit_labels(model, labels, B)
     if seeds is not None:
         seeds = check_seeds(seeds, B)
-    plan = _edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     dev = model._require_cuda("inpaint")
     model.eval()
     vqgan_model.eval()
@@ -172,12 +151,8 @@ def inpaint(
         slot_mask = token_mask.reshape(B, n, 1).expand(B, n, m).contiguous()         # every group of a regenerated cell
         _lib.check(lib.mb_edit_init(idx.data_ptr(), slot_mask.data_ptr(), tokens.data_ptr(), num_regen.data_ptr(), B, n, m, C_, stream), "mb_edit_init")
     direct_u8 = return_uint8 and not keep_known_pixels                                # the decoder's own uint8 epilogue
-    if seeds is not None:
-        gen, u8, _, codes = run_seeded(model, vqgan_model, labels.to(dev), plan, seeds, randomize_temperature, want_steps=False,
-                                       want_image=not direct_u8, want_u8=direct_u8, init_tokens=tokens)
-    else:
-        gen, u8, _, codes = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, init_tokens=tokens, want_steps=False,
-                                        want_image=not direct_u8, want_u8=direct_u8)
+    gen, u8, _, codes = run_chunked(model, vqgan_model, labels.to(dev), plan, randomize_temperature, seeds=seeds, init_tokens=tokens, want_steps=False,
+                                    want_image=not direct_u8, want_u8=direct_u8)
     if keep_known_pixels:
         out = None if return_uint8 else torch.empty_like(gen)
         u8 = torch.empty((B, H, W, ch), dtype=torch.uint8, device=dev) if return_uint8 else None

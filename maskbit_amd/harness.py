@@ -20,7 +20,7 @@ import torch
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
 from .factorization import split_factorized_tokens
-from .sampling import build_plan, check_seeds, check_tokenizer, run_chunked, run_seeded, seeded_plan, _ForcedPlan
+from .sampling import build_plan, check_models, check_seeds, check_tokenizer, forced_guidance, run_chunked, seeded_plan
 from .validation import MaskedTokenEvaluator, get_mask_tokens
 
 
@@ -47,26 +47,26 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
     ``seed`` (an int in [0, 2**64)): seeded sampling (``sample_seeded``) -- image ``j`` of the run (global index) is generated from the seed
     ``(seed + j) mod 2**64``, so the images do not depend on ``batchsize`` and any one of them can be regenerated alone; torch's generators are not
     consumed."""
-    if not isinstance(model, LFQBert) or not isinstance(vqgan_model, ConvVQModel):
-        raise TypeError("generate_uint8() needs a maskbit_amd generator and tokenizer")
-    check_tokenizer(model, vqgan_model)
-    dev = model._require_cuda("generate_uint8")
-    model.eval()
-    vqgan_model.eval()
+    check_models(model, vqgan_model, "generate_uint8")
     total = int(labels.numel()) if total_samples is None else int(total_samples)
     nbatch = total // batchsize
     if nbatch * batchsize > labels.numel():
         raise ValueError(f"{labels.numel()} labels do not cover {nbatch} batches of {batchsize}")
     model._check_labels(labels)
     n, m = model.seq_len, model.splits
-    plan = build_plan(num_steps, n * m, guidance_scale, guidance_annealing, scale_pow, softmax_temperature,
-                      use_sampling_annealing, mask_schedule_strategy)
-    if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
-        plan = _ForcedPlan(plan)
-    if seed is not None:
+    run_seeds = None
+    if seed is None:
+        plan = forced_guidance(build_plan(num_steps, n * m, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing,
+                                          mask_schedule_strategy), guidance_scale)
+    else:
         check_seeds([seed], 1)
-        run_seeds = check_seeds([(seed + j) % (1 << 64) for j in range(nbatch * batchsize)], nbatch * batchsize).to(dev)      # one copy for the whole run
+        run_seeds = check_seeds([(seed + j) % (1 << 64) for j in range(nbatch * batchsize)], nbatch * batchsize)
         plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    dev = model._require_cuda("generate_uint8")
+    model.eval()
+    vqgan_model.eval()
+    if run_seeds is not None:
+        run_seeds = run_seeds.to(dev)                   # one copy for the whole run
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     pinned = [None, None]
@@ -80,10 +80,8 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
 
     for i in range(nbatch):
         y = labels[batchsize * i: batchsize * (i + 1)].long()
-        if seed is not None:
-            _, u8, _, codes = run_seeded(model, vqgan_model, y, plan, run_seeds[batchsize * i: batchsize * (i + 1)], randomize_temperature, want_steps=False, want_image=False, want_u8=True)
-        else:
-            _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, want_steps=False, want_image=False, want_u8=True)
+        seeds = run_seeds[batchsize * i: batchsize * (i + 1)] if run_seeds is not None else None
+        _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, seeds=seeds, want_steps=False, want_image=False, want_u8=True)
         slot = i & 1
         if pinned[slot] is None or pinned[slot].shape != u8.shape:
             pinned[slot] = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)

@@ -90,7 +90,7 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
     ``noise="seeded"`` with ``seeds`` (one per global sample, as for ``sample_seeded``): sample ``j`` is generated from ``seeds[j]`` on whichever
     rank owns it -- the same images for any world size, and torch's generators are not consumed."""
     import torch.distributed as dist
-    from .sampling import _ForcedPlan, build_plan, check_seeds, check_tokenizer, draw_noise, plan_arrays, run_loop, run_seeded, seeded_plan, step_chunks
+    from .sampling import build_plan, check_seeds, check_tokenizer, forced_guidance, run_chunked, seeded_plan
     check_tokenizer(model, vqgan_model)
     if (noise == "seeded") != (seeds is not None):
         raise ValueError("noise='seeded' and seeds= go together")
@@ -100,20 +100,13 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     B = int(global_labels.numel())
     lo, hi = shard_range(rank, world, B)
-    n, m, C_ = model.seq_len, model.splits, model.effective_codebook_size
-    plan = build_plan(num_steps, n * m, guidance_scale, guidance_annealing, scale_pow, softmax_temperature,
-                      use_sampling_annealing, mask_schedule_strategy)
-    if guidance_scale != 0.0 and not any(a != 0.0 for a in plan[0]):
-        plan = _ForcedPlan(plan)                      # as sample(): the CFG forward runs even when every annealed scale is 0
+    n, m = model.seq_len, model.splits
+    sched = (guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+    if noise == "seeded":                             # (the per-sample re-masking rule; an empty shard has no generator to keep in step)
+        plan, seeds = seeded_plan(num_steps, *sched), seeds[lo:hi].contiguous()
+    else:
+        plan = forced_guidance(build_plan(num_steps, n * m, *sched), guidance_scale)
     dev = model.device
-    if noise == "seeded":
-        if hi == lo:                                  # more ranks than samples: an empty block, and no generator to keep in step
-            side = int(round(n ** 0.5)) << (vqgan_model.num_resolutions - 1)
-            return gather_images(torch.empty((0, side, side, vqgan_model.num_channels), dtype=torch.uint8, device=dev), group)
-        splan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
-        _, u8, _, _ = run_seeded(model, vqgan_model, global_labels[lo:hi].to(dev), splan, seeds[lo:hi].contiguous(), randomize_temperature,
-                                 want_steps=False, want_image=False, want_u8=True)
-        return gather_images(u8, group, equal=(B % world == 0) or None)
     if noise is None:
         noise = "rank"
         global _WARNED_DEFAULT_NOISE
@@ -122,23 +115,14 @@ def sample_sharded(model, vqgan_model, global_labels: torch.Tensor, *, noise: Op
             warnings.warn("sample_sharded: noise left at its default ('rank'): every rank draws its own shard's noise from its own generators -- "
                           "seed the ranks differently (torch.manual_seed(seed + rank)), or pass noise='batch' for the single-device-identical mode",
                           stacklevel=2)
-    if noise not in ("batch", "rank"):
+    if noise not in ("batch", "rank", "seeded"):
         raise ValueError("noise must be 'batch', 'rank' or 'seeded'")
-    nb = B if noise == "batch" else hi - lo           # the batch the noise is drawn for; chunked by steps to bound its memory (sampling.step_chunks)
+    # "batch": the noise is drawn for the whole batch and this rank is fed its rows -- an empty shard still draws, to keep the generators in step with
+    # the other ranks; chunked by steps to bound its memory (sampling.step_chunks)
+    kw = dict(seeds=seeds, noise_rows=(B, lo, hi) if noise == "batch" else None, want_steps=False, want_image=False, want_u8=True)
+    if hi > lo or noise == "batch":
+        _, u8, _, _ = run_chunked(model, vqgan_model, global_labels[lo:hi].to(dev), plan, randomize_temperature, **kw)
     if hi == lo:                                      # more ranks than samples: this rank contributes an empty block to the gather
-        if noise == "batch":
-            for (b0, b1) in step_chunks(nb, n, m, C_, num_steps):               # keep the generators in step with the other ranks
-                draw_noise(nb, n, m, C_, num_steps, randomize_temperature, dev, b0, b1)
         side = int(round(n ** 0.5)) << (vqgan_model.num_resolutions - 1)
-        return gather_images(torch.empty((0, side, side, vqgan_model.num_channels), dtype=torch.uint8, device=dev), group)
-    chunks = step_chunks(nb, n, m, C_, num_steps)
-    labels = global_labels[lo:hi].to(dev)
-    cplan = plan_arrays(plan)
-    u8 = None
-    for (b0, b1) in chunks:
-        e, c = draw_noise(nb, n, m, C_, num_steps, randomize_temperature, dev, b0, b1)
-        if noise == "batch":
-            e, c = slice_noise(e, c, lo, hi, n * m)
-        _, u8, _, _ = run_loop(model, vqgan_model, labels, plan, e, c, want_steps=False, want_image=False, want_u8=True,
-                               step_range=(b0, b1) if len(chunks) > 1 else None, _cplan=cplan)
-    return gather_images(u8, group, equal=(B % world == 0) or None)
+        u8 = torch.empty((0, side, side, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
+    return gather_images(u8, group, equal=(hi > lo and B % world == 0) or None)

@@ -21,6 +21,7 @@ from . import _lib
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
 from .masking import get_masking_ratio
+from .parallel import slice_noise
 
 
 def _scale_temperature(i: int, num_steps: int, guidance_scale: float, guidance_annealing: str, scale_pow: float, softmax_temperature: float,
@@ -39,42 +40,60 @@ def _scale_temperature(i: int, num_steps: int, guidance_scale: float, guidance_a
     return float(torch.tensor(a, dtype=torch.float32)), (0.5 + 0.8 * (1 - progress) if use_sampling_annealing else softmax_temperature)
 
 
-def build_plan(num_steps: int, num_maskable: int, guidance_scale: float, guidance_annealing: str, scale_pow: float,
-               softmax_temperature: float, use_sampling_annealing: bool, mask_schedule_strategy: str):
-    """Host-side per-step constants (sampling.py:82, 90-98, 103-104, 120-123)."""
-    get_masking_ratio(1.0, mask_schedule_strategy)          # raises ValueError on a bad strategy before any GPU work
-    scale, temp, mask_len = [], [], []
-    for i in range(num_steps):
-        a, t = _scale_temperature(i, num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing)
-        scale.append(a)
-        temp.append(t)
-        mask_len.append(int(torch.floor(get_masking_ratio((i + 1) / num_steps, mask_schedule_strategy) * num_maskable)))
-    return scale, temp, mask_len
+class Plan(tuple):
+    """The per-step constants of a run: unpacks and indexes as ``(scale, temperature, third)``, three sequences of ``num_steps``.  ``third`` holds the
+    integer mask lengths ``mb_sample`` reads, or with ``edit`` the float32 masking ratios of a run that re-masks by the per-sample rule
+    (``mb_sample_edit``, ``mb_sample_seeded``).  ``force_guidance``: the CFG forward runs although every annealed scale is 0 (``forced_guidance``).
+    ``use_cfg`` and ``arrays`` -- the ctypes arrays the C entries read (+ ``use_cfg``) -- are computed once, here."""
 
-
-class EditPlan(tuple):
-    """(scale, temperature, mask_ratio) per step: the plan of a run that starts from a partly known token map (``mb_sample_edit``)."""
-    edit = True
-    force_guidance = False
-
-    def __new__(cls, plan, force_guidance: bool = False):
-        self = super().__new__(cls, plan)
-        self.force_guidance = force_guidance
+    def __new__(cls, scale, temperature, third, edit: bool = False, force_guidance: bool = False):
+        self = super().__new__(cls, (scale, temperature, third))
+        self.edit, self.force_guidance = edit, force_guidance
+        self.use_cfg = force_guidance or any(s != 0.0 for s in scale)
+        nsteps = len(scale)
+        self.arrays = ((C.c_float * nsteps)(*scale), (C.c_float * nsteps)(*temperature), ((C.c_float if edit else C.c_int) * nsteps)(*third), self.use_cfg)
         return self
 
 
-def build_edit_plan(num_steps: int, guidance_scale: float, guidance_annealing: str, scale_pow: float, softmax_temperature: float,
-                    use_sampling_annealing: bool, mask_schedule_strategy: str) -> EditPlan:
-    """``build_plan`` for an edit run: the same scales and temperatures, and in the place of the mask lengths the float32 masking ratios themselves
-    -- the device multiplies each by the sample's own initial masked count (``floor(ratio * M_b)`` in fp32, as ``torch.floor(ratio * num_maskable)``)."""
-    get_masking_ratio(1.0, mask_schedule_strategy)
-    scale, temp, ratio = [], [], []
+def build_plan(num_steps: int, num_maskable: Optional[int], guidance_scale: float, guidance_annealing: str, scale_pow: float,
+               softmax_temperature: float, use_sampling_annealing: bool, mask_schedule_strategy: str) -> Plan:
+    """Host-side per-step constants (sampling.py:82, 90-98, 103-104, 120-123): (scale, temperature, mask_len).  ``num_maskable`` None: the edit plan
+    (``build_edit_plan``), with the masking ratios themselves in the third column."""
+    get_masking_ratio(1.0, mask_schedule_strategy)          # raises ValueError on a bad strategy before any GPU work
+    scale, temp, third = [], [], []
     for i in range(num_steps):
         a, t = _scale_temperature(i, num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing)
         scale.append(a)
         temp.append(t)
-        ratio.append(float(get_masking_ratio((i + 1) / num_steps, mask_schedule_strategy)))
-    return EditPlan((scale, temp, ratio))
+        ratio = get_masking_ratio((i + 1) / num_steps, mask_schedule_strategy)
+        third.append(float(ratio) if num_maskable is None else int(torch.floor(ratio * num_maskable)))
+    return Plan(scale, temp, third, edit=num_maskable is None)
+
+
+def build_edit_plan(num_steps: int, guidance_scale: float, guidance_annealing: str, scale_pow: float, softmax_temperature: float,
+                    use_sampling_annealing: bool, mask_schedule_strategy: str) -> Plan:
+    """``build_plan`` for an edit run: the same scales and temperatures, and in the place of the mask lengths the float32 masking ratios themselves
+    -- the device multiplies each by the sample's own initial masked count (``floor(ratio * M_b)`` in fp32, as ``torch.floor(ratio * num_maskable)``)."""
+    return build_plan(num_steps, None, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
+
+
+def forced_guidance(plan: Plan, guidance_scale: float) -> Plan:
+    """The plan the public entries run: as in the reference's ``sample()``, the CFG forward still runs when ``guidance_scale != 0`` but every annealed
+    scale happens to be 0.  (Not applied by ``build_plan`` / ``build_edit_plan``: a plan built directly runs what its scales say.)"""
+    if guidance_scale != 0.0 and not plan.use_cfg:
+        return Plan(*plan, edit=plan.edit, force_guidance=True)
+    return plan
+
+
+def seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy) -> Plan:
+    """The plan of a seeded or an edit run as the public entries build it: ``build_edit_plan`` (per-sample masking ratios) under ``forced_guidance``."""
+    return forced_guidance(build_edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing,
+                                           mask_schedule_strategy), guidance_scale)
+
+
+def plan_arrays(plan: Plan):
+    """The plan as the ctypes arrays ``mb_sample`` reads (+ whether any step is guided); of an edit plan, those ``mb_sample_edit`` reads."""
+    return plan.arrays
 
 
 def check_tokenizer(model, vqgan_model) -> None:
@@ -82,6 +101,15 @@ def check_tokenizer(model, vqgan_model) -> None:
     codebook's nn.Embedding, quantizer.py:115).  Raised before any device work.  LFQ tokenizers are not checked (unchanged path)."""
     if getattr(vqgan_model, "quantizer_type", None) == "lookup" and vqgan_model.codebook_size < 2 ** model.bits:
         raise ValueError(f"the tokenizer's codebook holds {vqgan_model.codebook_size} entries, the generator emits codes up to 2**{model.bits}")
+
+
+def check_models(model, vqgan_model, what: str) -> None:
+    """``what()`` runs on this package's own models (there is no fall-back for others), and the tokenizer holds the generator's codes."""
+    if not isinstance(model, LFQBert):
+        raise TypeError(f"{what}() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
+    if not isinstance(vqgan_model, ConvVQModel):
+        raise TypeError(f"{what}() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
+    check_tokenizer(model, vqgan_model)
 
 
 NOISE_CHUNK_BYTES = 1 << 30       # sample() / generate_uint8() draw and feed the Exp(1) noise in step chunks of at most this size
@@ -173,68 +201,75 @@ def step_chunks(num_samples: int, n: int, m: int, C_: int, num_steps: int):
     return [(b, min(b + k, num_steps)) for b in range(0, num_steps, k)]
 
 
-def run_chunked(model: "LFQBert", vqgan_model, labels: torch.Tensor, plan, randomize_temperature: float, **kw):
-    """run_loop over the whole run with the noise drawn chunk by chunk (same random streams as one whole-run draw).  An ``EditPlan`` with
-    ``init_tokens=`` runs the edit loop: same draws, same chunks."""
-    scale = plan[0]
-    steps = len(scale)
-    B = labels.shape[0]
-    n, m = model.seq_len, model.splits
-    chunks = step_chunks(B, n, m, model.effective_codebook_size, steps)
-    if len(chunks) == 1:
-        e, c = draw_noise(B, n, m, model.effective_codebook_size, steps, randomize_temperature, model.device)
-        return run_loop(model, vqgan_model, labels, plan, e, c, **kw)
-    want_steps = kw.get("want_steps", True)
-    parts, out = [], None
-    kw = dict(kw, _cplan=plan_arrays(plan))              # the ctypes arrays of the plan are built once per run, not once per chunk
+def run_chunked(model: "LFQBert", vqgan_model, labels: torch.Tensor, plan: Plan, randomize_temperature: float, *, seeds: Optional[torch.Tensor] = None,
+                noise_rows: Optional[Tuple[int, int, int]] = None, **kw):
+    """A whole run -> what ``run_loop`` returns.  The noise is drawn chunk by chunk (same random streams as one whole-run draw), each chunk one ``run_loop``
+    call; an edit plan with ``init_tokens=`` runs the edit loop: same draws, same chunks.
+    ``seeds`` (what ``check_seeds`` returns): one ``run_seeded`` call instead -- no chunks, nothing drawn.
+    ``noise_rows`` = (nb, lo, hi): the noise is drawn for ``nb`` samples and the run is fed the rows of samples [lo, hi) (``parallel.slice_noise``) --
+    ``labels`` are those samples'; lo == hi: the draws alone (-> four Nones), which keep the generators in step with the callers that have samples."""
+    if seeds is not None:
+        return run_seeded(model, vqgan_model, labels, plan, seeds, randomize_temperature, **kw)
+    steps = len(plan[0])
+    n, m, C_ = model.seq_len, model.splits, model.effective_codebook_size
+    nb, lo, hi = noise_rows if noise_rows is not None else (labels.shape[0], 0, labels.shape[0])
+    chunks = step_chunks(nb, n, m, C_, steps)
+    parts, out = [], (None, None, None, None)
     for (b0, b1) in chunks:
-        e, c = draw_noise(B, n, m, model.effective_codebook_size, steps, randomize_temperature, model.device, b0, b1)
-        out = run_loop(model, vqgan_model, labels, plan, e, c, step_range=(b0, b1), **kw)
-        if want_steps:
-            parts.append(out[2])
-    img, u8, _, codes = out
-    return img, u8, (torch.cat(parts) if want_steps else None), codes
+        e, c = draw_noise(nb, n, m, C_, steps, randomize_temperature, model.device, b0, b1)
+        if noise_rows is not None:
+            if lo == hi:
+                continue
+            e, c = slice_noise(e, c, lo, hi, n * m)
+        out = run_loop(model, vqgan_model, labels, plan, e, c, step_range=(b0, b1) if len(chunks) > 1 else None, **kw)
+        parts.append(out[2])
+    if len(parts) > 1 and parts[0] is not None:
+        out = out[0], out[1], torch.cat(parts), out[3]
+    return out
 
 
-def plan_arrays(plan):
-    """The plan as the ctypes arrays ``mb_sample`` reads (+ whether any step is guided); of an ``EditPlan``, those ``mb_sample_edit`` reads."""
-    scale, temp, mask_len = plan
-    nsteps = len(scale)
-    use_cfg = any(s != 0.0 for s in scale) or getattr(plan, "force_guidance", False)
-    third = C.c_float if getattr(plan, "edit", False) else C.c_int            # (an edit plan holds the float32 masking ratios there)
-    return (C.c_float * nsteps)(*scale), (C.c_float * nsteps)(*temp), (third * nsteps)(*mask_len), use_cfg
-
-
-def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan, exp_noise: torch.Tensor,
-             conf_noise: torch.Tensor, want_steps: bool = True, want_image: bool = True, want_u8: bool = False,
-             step_range: Optional[Tuple[int, int]] = None, _cplan=None, init_tokens: Optional[torch.Tensor] = None):
-    """One ``mb_sample`` call.  -> (image or None, uint8 NHWC or None, step tokens [steps,B,n,m] or None, codes [B,n]).
-    ``init_tokens`` (int64 [B,n,m] on the model's device, ``model.mask_token`` at the slots to regenerate) with an ``EditPlan``: one ``mb_sample_edit``
-    call -- the run starts from those tokens instead of the all-masked state (read by the chunk that starts the run).
-    ``step_range`` = (begin, end): only those steps of the plan, with ``exp_noise`` / ``conf_noise`` holding that chunk's noise; chunk (0, e)
-    starts the run, later chunks continue from the engine's token state, the chunk ending at the last step combines and decodes (image / codes
-    are meaningful only then)."""
-    dev = model._require_cuda("sample")
-    scale, temp, mask_len = plan
-    nsteps = len(scale)
+def _run(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan: Plan, want_steps: bool, want_image: bool, want_u8: bool,
+         step_range: Optional[Tuple[int, int]], init_tokens: Optional[torch.Tensor], noise=None, seeded=None):
+    """One call of a run entry, for ``run_loop`` (``noise`` = (exp_noise, conf_noise) of the step range: ``mb_sample``, or ``mb_sample_edit`` with an edit
+    plan) and ``run_seeded`` (``seeded`` = (seeds, randomize_temperature): ``mb_sample_seeded``)."""
+    dev = model._require_cuda("sample" if seeded is None else "sample_seeded")
+    nsteps = len(plan[0])
     sb, se = step_range if step_range is not None else (0, nsteps)
     steps = se - sb
-    if exp_noise.shape[0] != steps or conf_noise.shape[0] != steps:
-        raise ValueError(f"noise holds {exp_noise.shape[0]} steps, the step range {steps}")
     B = labels.shape[0]
     n, m = model.seq_len, model.splits
-    edit = getattr(plan, "edit", False)
-    if edit != (init_tokens is not None):
-        raise ValueError("an edit plan (build_edit_plan) and init_tokens go together")
-    if edit and (init_tokens.shape != (B, n, m) or init_tokens.dtype != torch.int64 or init_tokens.device.type != dev.type or not init_tokens.is_contiguous()):
+    if seeded is None:
+        exp_noise, conf_noise = noise
+        if exp_noise.shape[0] != steps or conf_noise.shape[0] != steps:
+            raise ValueError(f"noise holds {exp_noise.shape[0]} steps, the step range {steps}")
+        if plan.edit != (init_tokens is not None):
+            raise ValueError("an edit plan (build_edit_plan) and init_tokens go together")
+    else:
+        seeds, randomize_temperature = seeded
+        if not plan.edit:
+            raise ValueError("a seeded run takes an edit plan (build_edit_plan): it re-masks by the per-sample rule")
+        if seeds.shape != (B,) or seeds.dtype != torch.int64:
+            raise ValueError(f"seeds must be int64 [{B}]")
+    if init_tokens is not None and (init_tokens.shape != (B, n, m) or init_tokens.dtype != torch.int64 or init_tokens.device.type != dev.type
+                                    or not init_tokens.is_contiguous()):
         raise ValueError(f"init_tokens must be a contiguous int64 [{B}, {n}, {m}] tensor on {dev}")
-    c_scale, c_temp, c_len, use_cfg = _cplan if _cplan is not None else plan_arrays(plan)
+    c_scale, c_temp, c_third, use_cfg = plan.arrays
     labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if seeded is None:
+        entry = "mb_sample_edit" if plan.edit else "mb_sample"
+        source = ((init_tokens.data_ptr(),) if plan.edit else ()) + (exp_noise.data_ptr(), conf_noise.data_ptr())
+    else:
+        # (host-resident seeds: a pageable-memory copy would hold the host until the device has run everything enqueued before it -- the previous batch --
+        # and the device then idles while this run is enqueued; pinned and asynchronous, as _to_device_early's)
+        seeds = seeds.to(dev) if seeds.device.type != "cpu" else seeds.pin_memory().to(dev, non_blocking=True)
+        conf_w = (C.c_float * nsteps)(*[1 - (i + 1) / nsteps for i in range(nsteps)])   # float32(1 - progress), sampling.py:117
+        entry = "mb_sample_seeded"
+        source = (ptr(init_tokens), seeds.data_ptr(), float(randomize_temperature), conf_w)
     step_tokens = torch.empty((steps, B, n, m), dtype=torch.int64, device=dev) if want_steps else None
     last = se == nsteps                                  # only the chunk that ends the run combines and decodes: earlier chunks need no outputs
     codes = torch.empty((B, n), dtype=torch.int64, device=dev) if last else None
-    img = u8 = None
-    hdec = None
+    img = u8 = hdec = None
     if last and vqgan_model is not None and (want_image or want_u8):
         side = int(round(n ** 0.5))
         res = side << (vqgan_model.num_resolutions - 1)
@@ -244,19 +279,24 @@ def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.T
             u8 = torch.empty((B, res, res, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
         hdec = vqgan_model.engine(B, side)
     hgen = model.engine(2 * B if use_cfg else B)
-    cplan = (_lib.EditPlan if edit else _lib.SamplePlan)(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_len, sb if step_range is not None else 0,
-                                                         se if step_range is not None else 0)
-    ptr = lambda t: t.data_ptr() if t is not None else None
+    cplan = (_lib.EditPlan if plan.edit else _lib.SamplePlan)(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_third, sb if step_range is not None else 0,
+                                                              se if step_range is not None else 0)
     with torch.cuda.device(dev):
-        if edit:
-            _lib.check(_lib.load().mb_sample_edit(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, init_tokens.data_ptr(), exp_noise.data_ptr(),
-                                                  conf_noise.data_ptr(), ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
-                                                  torch.cuda.current_stream().cuda_stream), "mb_sample_edit")
-            return img, u8, step_tokens, codes
-        _lib.check(_lib.load().mb_sample(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, exp_noise.data_ptr(),
-                                         conf_noise.data_ptr(), ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
-                                         torch.cuda.current_stream().cuda_stream), "mb_sample")
+        _lib.check(getattr(_lib.load(), entry)(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, *source, ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
+                                               torch.cuda.current_stream().cuda_stream), entry)
     return img, u8, step_tokens, codes
+
+
+def run_loop(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan: Plan, exp_noise: torch.Tensor,
+             conf_noise: torch.Tensor, want_steps: bool = True, want_image: bool = True, want_u8: bool = False,
+             step_range: Optional[Tuple[int, int]] = None, init_tokens: Optional[torch.Tensor] = None):
+    """One ``mb_sample`` call.  -> (image or None, uint8 NHWC or None, step tokens [steps,B,n,m] or None, codes [B,n]).
+    ``init_tokens`` (int64 [B,n,m] on the model's device, ``model.mask_token`` at the slots to regenerate) with an edit plan: one ``mb_sample_edit``
+    call -- the run starts from those tokens instead of the all-masked state (read by the chunk that starts the run).
+    ``step_range`` = (begin, end): only those steps of the plan, with ``exp_noise`` / ``conf_noise`` holding that chunk's noise; chunk (0, e)
+    starts the run, later chunks continue from the engine's token state, the chunk ending at the last step combines and decodes (image / codes
+    are meaningful only then)."""
+    return _run(model, vqgan_model, labels, plan, want_steps, want_image, want_u8, step_range, init_tokens, noise=(exp_noise, conf_noise))
 
 
 def check_seeds(seeds, num_samples: int) -> torch.Tensor:
@@ -285,59 +325,13 @@ def check_seeds(seeds, num_samples: int) -> torch.Tensor:
     return torch.tensor(out, dtype=torch.int64)
 
 
-def run_seeded(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan, seeds: torch.Tensor, randomize_temperature: float,
+def run_seeded(model: LFQBert, vqgan_model: Optional[ConvVQModel], labels: torch.Tensor, plan: Plan, seeds: torch.Tensor, randomize_temperature: float,
                want_steps: bool = True, want_image: bool = True, want_u8: bool = False, step_range: Optional[Tuple[int, int]] = None,
                init_tokens: Optional[torch.Tensor] = None):
-    """One ``mb_sample_seeded`` call: ``run_loop`` for an ``EditPlan`` whose steps generate their own noise from ``seeds`` (int64 [B], what
+    """One ``mb_sample_seeded`` call: ``run_loop`` for an edit plan whose steps generate their own noise from ``seeds`` (int64 [B], what
     ``check_seeds`` returns).  No noise tensor exists, no generator is consumed, nothing is drawn on the host.  ``init_tokens`` None: the run starts
     all-masked.  -> (image or None, uint8 NHWC or None, step tokens or None, codes [B,n] or None), as ``run_loop``."""
-    dev = model._require_cuda("sample_seeded")
-    if not getattr(plan, "edit", False):
-        raise ValueError("a seeded run takes an edit plan (build_edit_plan): it re-masks by the per-sample rule")
-    scale, temp, ratio = plan
-    nsteps = len(scale)
-    sb, se = step_range if step_range is not None else (0, nsteps)
-    B = labels.shape[0]
-    n, m = model.seq_len, model.splits
-    if seeds.shape != (B,) or seeds.dtype != torch.int64:
-        raise ValueError(f"seeds must be int64 [{B}]")
-    if init_tokens is not None and (init_tokens.shape != (B, n, m) or init_tokens.dtype != torch.int64 or init_tokens.device.type != dev.type
-                                    or not init_tokens.is_contiguous()):
-        raise ValueError(f"init_tokens must be a contiguous int64 [{B}, {n}, {m}] tensor on {dev}")
-    c_scale, c_temp, c_ratio, use_cfg = plan_arrays(plan)
-    conf_w = (C.c_float * nsteps)(*[1 - (i + 1) / nsteps for i in range(nsteps)])       # float32(1 - progress), sampling.py:117
-    labels = labels.to(device=dev, dtype=torch.int64).contiguous()
-    # (host-resident seeds: a pageable-memory copy would hold the host until the device has run everything enqueued before it -- the previous batch --
-    # and the device then idles while this run is enqueued; pinned and asynchronous, as _to_device_early's)
-    seeds = seeds.to(dev) if seeds.device.type != "cpu" else seeds.pin_memory().to(dev, non_blocking=True)
-    step_tokens = torch.empty((se - sb, B, n, m), dtype=torch.int64, device=dev) if want_steps else None
-    last = se == nsteps
-    codes = torch.empty((B, n), dtype=torch.int64, device=dev) if last else None
-    img = u8 = hdec = None
-    if last and vqgan_model is not None and (want_image or want_u8):
-        side = int(round(n ** 0.5))
-        res = side << (vqgan_model.num_resolutions - 1)
-        if want_image:
-            img = torch.empty((B, vqgan_model.num_channels, res, res), dtype=torch.float32, device=dev)
-        if want_u8:
-            u8 = torch.empty((B, res, res, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
-        hdec = vqgan_model.engine(B, side)
-    hgen = model.engine(2 * B if use_cfg else B)
-    cplan = _lib.EditPlan(nsteps, 1 if use_cfg else 0, c_scale, c_temp, c_ratio, sb if step_range is not None else 0, se if step_range is not None else 0)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().mb_sample_seeded(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, ptr(init_tokens), seeds.data_ptr(),
-                                                float(randomize_temperature), conf_w, ptr(step_tokens), ptr(codes), ptr(img), ptr(u8),
-                                                torch.cuda.current_stream().cuda_stream), "mb_sample_seeded")
-    return img, u8, step_tokens, codes
-
-
-def seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy) -> EditPlan:
-    """The plan of a seeded run: ``build_edit_plan`` (per-sample masking ratios), with the CFG forward forced when every annealed scale is 0, as in ``sample()``."""
-    plan = build_edit_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
-    if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
-        plan = EditPlan(plan, force_guidance=True)
-    return plan
+    return _run(model, vqgan_model, labels, plan, want_steps, want_image, want_u8, step_range, init_tokens, seeded=(seeds, randomize_temperature))
 
 
 @torch.no_grad()
@@ -362,11 +356,7 @@ def sample_seeded(
     (include/maskbit_hip.h): no noise tensor is created, neither the CPU nor the device torch generator is consumed, and the whole run is one
     ``mb_sample_seeded`` call.  The samples are re-masked by the per-sample rule of the edit step.  Same return value as ``sample()``; the noise is
     NOT the reference's, so a seeded run does not reproduce a ``sample()`` run."""
-    if not isinstance(model, LFQBert):
-        raise TypeError(f"sample_seeded() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
-    if not isinstance(vqgan_model, ConvVQModel):
-        raise TypeError(f"sample_seeded() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
-    check_tokenizer(model, vqgan_model)
+    check_models(model, vqgan_model, "sample_seeded")
     if not isinstance(labels, torch.Tensor):
         raise TypeError(f"labels must be a tensor of class ids, got {type(labels).__name__}")
     seeds = check_seeds(seeds, int(labels.numel()))
@@ -374,7 +364,7 @@ def sample_seeded(
     plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
     model.eval()
     vqgan_model.eval()
-    img, _, step_tokens, _ = run_seeded(model, vqgan_model, labels.reshape(-1), plan, seeds, randomize_temperature)
+    img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels.reshape(-1), plan, randomize_temperature, seeds=seeds)
     return img, list(step_tokens.unbind(0))
 
 
@@ -400,11 +390,7 @@ def sample(
 ) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """Generate ``num_samples`` class-conditional images.  See the module docstring; arguments as in the
     reference (sampling.py:32-54).  ``use_tqdm`` is accepted and ignored (the loop runs on the device)."""
-    if not isinstance(model, LFQBert):
-        raise TypeError(f"sample() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
-    if not isinstance(vqgan_model, ConvVQModel):
-        raise TypeError(f"sample() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
-    check_tokenizer(model, vqgan_model)
+    check_models(model, vqgan_model, "sample")
     device = model.device
     model.eval()
     vqgan_model.eval()
@@ -422,16 +408,7 @@ def sample(
     labels = labels.to(device)
     if labels.numel() != num_samples:
         raise ValueError(f"{labels.numel()} labels for num_samples={num_samples}")
-    plan = build_plan(num_steps, n * m, guidance_scale, guidance_annealing, scale_pow, softmax_temperature,
-                      use_sampling_annealing, mask_schedule_strategy)
-    if guidance_scale != 0.0 and not any(s != 0.0 for s in plan[0]):
-        plan = _ForcedPlan(plan)                      # CFG forward still runs when every a_i happens to be 0
+    plan = forced_guidance(build_plan(num_steps, n * m, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing,
+                                      mask_schedule_strategy), guidance_scale)
     img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels, plan, randomize_temperature)
     return img, list(step_tokens.unbind(0))
-
-
-class _ForcedPlan(tuple):
-    force_guidance = True
-
-    def __new__(cls, plan):
-        return super().__new__(cls, plan)

@@ -86,6 +86,34 @@ def test_edit_plan_matches_the_float32_formulas_and_build_plan(N, ann, sp, strat
         build_edit_plan(4, 3.0, "bogus", 1.0, 1.0, False, "linear")
 
 
+DEGENERATE = dict(num_steps=1, guidance_annealing="linear", guidance_scale=3.0)               # the only annealed scale is 3.0 * 0 / 1 = 0.0
+
+
+def test_one_plan_type_and_one_forced_guidance_rule():
+    from maskbit_amd.sampling import build_edit_plan, build_plan, forced_guidance, plan_arrays, seeded_plan
+    plain = build_plan(1, 512, 3.0, "linear", 1.0, 1.0, False, "arccos")
+    edit = build_edit_plan(1, 3.0, "linear", 1.0, 1.0, False, "arccos")
+    assert type(plain) is type(edit) and plain[0] == edit[0] == [0.0]
+    for plan in (plain, edit):
+        assert plan_arrays(plan)[3] is False and not plan.force_guidance                       # the builders do not apply the rule ...
+        forced = forced_guidance(plan, 3.0)                                                    # ... the helper does
+        assert type(forced) is type(plan) and forced.edit == plan.edit and forced.force_guidance and tuple(forced) == tuple(plan)
+        assert plan_arrays(forced)[3] is True and plan_arrays(plan)[3] is False                # (a new plan: the argument is unchanged)
+        assert plan_arrays(forced_guidance(plan, 0.0))[3] is False                             # no guidance asked for: nothing to force
+        assert plan_arrays(plan) is plan_arrays(plan)                                          # the arrays are built once per plan
+    assert plan_arrays(seeded_plan(1, 3.0, "linear", 1.0, 1.0, False, "arccos"))[3] is True
+    assert plan_arrays(seeded_plan(1, 0.0, "linear", 1.0, 1.0, False, "arccos"))[3] is False
+    cos = build_plan(8, 512, 3.0, "cosine", 4.0, 1.0, False, "arccos")                         # step 1's scale is 4.47e-7: tiny, not zero
+    assert cos[0][0] == 0.0 and 4.4e-7 < cos[0][1] < 4.5e-7
+    assert plan_arrays(cos)[3] is True and forced_guidance(cos, 3.0) is cos and not cos.force_guidance
+    for plan, third in ((cos, ctypes.c_int), (build_edit_plan(8, 3.0, "cosine", 4.0, 1.0, False, "arccos"), ctypes.c_float)):
+        scale, temp, col = plan                                                                # still three sequences of num_steps
+        assert len(scale) == len(temp) == len(col) == 8 and plan[0] is scale and plan[2] is col
+        arrays = plan_arrays(plan)
+        assert [a._type_ for a in arrays[:3]] == [ctypes.c_float, ctypes.c_float, third] and [len(a) for a in arrays[:3]] == [8, 8, 8]
+        assert list(arrays[2]) == col
+
+
 def test_edit_plan_struct_matches_the_header():
     from maskbit_amd import _lib
     header = open(os.path.join(ROOT, "include", "maskbit_hip.h")).read()
@@ -223,6 +251,47 @@ def test_inpaint_refuses_before_any_device_work():
     for ok_mask in (mask, mask.unsqueeze(1), mask.to(torch.uint8)):
         with pytest.raises(RuntimeError, match="no CPU path"):
             inpaint(gm, tm, img, ok_mask, y)
+
+
+def test_every_public_entry_builds_its_plan_through_the_one_helper(monkeypatch):
+    """CPU-resident models, the degenerate schedule: each entry passes its argument checks, builds its plan through ``sampling.forced_guidance`` (a
+    spy in its place) with ``force_guidance`` set, and stops at the missing device.  No caller keeps a copy of the rule."""
+    from maskbit_amd import editing, generate_uint8, harness, inpaint, sample, sample_from_tokens, sample_seeded, sampling
+    from maskbit_amd.parallel import sample_sharded
+    gm, tm = cpu_models()
+    seen = []
+    real = sampling.forced_guidance
+
+    def spy(plan, guidance_scale):
+        out = real(plan, guidance_scale)
+        seen.append((plan.edit, guidance_scale, out.force_guidance, out))
+        return out
+    for mod in (sampling, editing, harness):                                                   # (parallel imports it from sampling at call time)
+        if hasattr(mod, "forced_guidance"):
+            monkeypatch.setattr(mod, "forced_guidance", spy)
+    ran = []
+    real_run = sampling._run
+    monkeypatch.setattr(sampling, "_run", lambda model, vq, labels, plan, *a, **kw: (ran.append(plan), real_run(model, vq, labels, plan, *a, **kw))[1])
+    y = torch.tensor([1, 2])
+    tok = torch.full((2, 256, 2), 64, dtype=torch.int64)
+    img, mask = torch.rand(2, 3, 64, 64), torch.ones(2, 64, 64, dtype=torch.bool)
+    entries = [
+        ("sample", False, lambda: sample(gm, tm, num_samples=2, labels=y, mask_token=64, codebook_size=4096, codebook_splits=2, **DEGENERATE)),
+        ("sample_seeded", True, lambda: sample_seeded(gm, tm, [5, 6], y, **DEGENERATE)),
+        ("sample_from_tokens", True, lambda: sample_from_tokens(gm, tm, tok, y, **DEGENERATE)),
+        ("sample_from_tokens seeded", True, lambda: sample_from_tokens(gm, tm, tok, y, seeds=[5, 6], **DEGENERATE)),
+        ("inpaint", True, lambda: inpaint(gm, tm, img, mask, y, **DEGENERATE)),
+        ("generate_uint8", False, lambda: next(generate_uint8(gm, tm, y, 2, **DEGENERATE))),
+        ("generate_uint8 seeded", True, lambda: next(generate_uint8(gm, tm, y, 2, seed=5, **DEGENERATE))),
+        ("sample_sharded", False, lambda: sample_sharded(gm, tm, y, noise="rank", scale_pow=1.0, **DEGENERATE)),
+        ("sample_sharded seeded", True, lambda: sample_sharded(gm, tm, y, noise="seeded", seeds=[5, 6], scale_pow=1.0, **DEGENERATE)),
+    ]
+    for name, edit, call in entries:
+        del seen[:], ran[:]
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            call()
+        assert len(seen) == 1 and seen[0][:3] == (edit, 3.0, True), (name, seen)
+        assert all(p is seen[0][3] for p in ran), name                                         # what reached the runner is the helper's plan
 
 
 # ---- the restatements themselves ---------------------------------------------------------------------------------------------------------

@@ -177,6 +177,50 @@ def test_seeded_run_equals_the_edit_run_on_the_dumped_noise_and_step_chunks():
         run_seeded(gm, tm, y, splan, sd, 8.2, want_image=False, step_range=(3, 4))
 
 
+def test_a_chunk_continues_a_run_of_its_own_kind_only():
+    """Tiny generator, B = 2, 4 guided steps, the three kinds of run -- plain (mb_sample), edit (mb_sample_edit, mixed masks), seeded (mb_sample_seeded)
+    -- with the same batch, plan length and guidance flag, so that the kind alone tells them apart.  After steps [0, 3) of one kind, step [3, 4) of
+    each other kind is refused (an argument refusal: nothing is launched); after the refusal a fresh [0, 3) + [3, 4) of the first kind equals its
+    unchunked run, bit for bit."""
+    from maskbit_amd import _lib
+    from maskbit_amd.sampling import build_edit_plan, build_plan, check_seeds, run_loop, run_seeded, seeded_plan
+    from test_hip_edit import dev_noise
+    gm, tm = tiny_models()
+    B, N, rt = 2, 4, 8.2
+    y = torch.tensor([3, 7], device=DEV)
+    sched = (7.1, "cosine", 3.0, 1.0, False, "arccos")
+    plans = {"plain": build_plan(N, 512, *sched), "edit": build_edit_plan(N, *sched), "seeded": seeded_plan(N, *sched)}
+    assert all(p[0] == plans["plain"][0] and p.use_cfg for p in plans.values())
+    q, c = dev_noise(23, B, N, rt)
+    init = tokens_with_masks([512, 100], seed=13)[0].to(DEV)
+    sd = check_seeds([11, 2 ** 64 - 3], B)
+
+    def run(kind, step_range):
+        b0, b1 = step_range or (0, N)
+        if kind == "seeded":
+            return run_seeded(gm, tm, y, plans[kind], sd, rt, want_u8=True, step_range=step_range)
+        return run_loop(gm, tm, y, plans[kind], q[b0:b1], c[b0:b1], want_u8=True, step_range=step_range, init_tokens=init if kind == "edit" else None)
+    whole = {kind: run(kind, None) for kind in plans}
+    assert not torch.equal(whole["plain"][2], whole["edit"][2]) and not torch.equal(whole["edit"][2], whole["seeded"][2])   # three different runs
+    for first in plans:
+        for other in plans:
+            if other == first:
+                continue
+            run(first, (0, 3))
+            _lib.prof_enable(True)
+            try:
+                with pytest.raises(RuntimeError, match=f"of a 4-step {other} run with B = 2 does not continue the run in progress .*{first} run"):
+                    run(other, (3, 4))
+                assert _lib.prof_read() == {}, (first, other)                                      # refused in front of every launch
+            finally:
+                _lib.prof_enable(False)
+            _, _, st03, _ = run(first, (0, 3))                                                     # (a rejected chunk ends the run: start again)
+            img, u8, st34, codes = run(first, (3, 4))
+            ref = whole[first]
+            assert torch.equal(torch.cat([st03, st34]), ref[2]), (first, other)
+            assert torch.equal(img, ref[0]) and torch.equal(u8, ref[1]) and torch.equal(codes, ref[3]), (first, other)
+
+
 # ---- 4. a sample does not depend on its batch -------------------------------------------------------------------------------------------------
 def seeded_steps(gm, seeds, y, plan, rt=8.2):
     from maskbit_amd.sampling import check_seeds, run_seeded
