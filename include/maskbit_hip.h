@@ -320,6 +320,22 @@ int mb_lpips_forward(mb_lpips* h, const float* real, const float* fake, int B, i
 /* 4-channel activation groups of this handle's convolutions clamped at +-65504 since the last reset.  Synchronises `stream`. */
 int mb_lpips_saturation_count(mb_lpips* h, unsigned* count, int reset, mb_stream stream);
 
+/* ---- FID / Inception Score statistics: GeneratorEvaluator.update, evaluator/evaluator.py:549-569 (rFID: :336-364) --------------------------- *
+ * Stateless like the tokenizer evaluation above: caller-owned buffers (zeroed once by the caller), no allocation, no synchronisation.  dtype of the
+ * input rows: 0 = fp32 (widened exactly), 1 = fp64; row_stride in elements, >= the row length.  A shape outside B, D (C) in [1, 2^20] is refused.
+ * total double [D] += sum_n f_n and sigma double [D,D] += F^T F for feats [B, D]: the per-image `total += f; sigma += torch.outer(f, f)` loop of
+ * evaluator.py:567-569 as one fp64 MFMA rank-B update.  Every element chains the batch's rows in increasing order onto its loaded value and is
+ * written by one wave (no floating-point atomics): bitwise reproducible, and consecutive calls on the parts of a batch split at a multiple of 4 rows
+ * leave the bits of one call on the whole.  ONLY the 64 x 64 blocks of sigma on and above the diagonal are updated (elements [i][j] with
+ * i / 64 <= j / 64); the blocks below it are never read or written -- mirror the upper triangle before reading the matrix. */
+int mb_fid_accumulate(const void* feats, int dtype, int B, int D, int64_t row_stride, double* total, double* sigma, mb_stream stream);
+/* Bytes of workspace mb_is_accumulate needs (two doubles per row); 0 for a shape it does not take. */
+size_t mb_is_workspace_bytes(int B, int C);
+/* p = softmax(logits [B, C]) in fp64 with the row maximum subtracted; prob_total double [C] += sum_n p and kl_total double [C] += sum_n p log(p + 1e-16)
+ * (evaluator.py:553-564), each column summed over the batch in a fixed order: deterministic. */
+int mb_is_accumulate(const void* logits, int dtype, int B, int C, int64_t row_stride, double* prob_total, double* kl_total, void* workspace,
+                     mb_stream stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */
 int mb_prof_read(char* buf, int buflen); /* host buffer; writes "name calls total_ms\n" lines */

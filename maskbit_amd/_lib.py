@@ -117,7 +117,10 @@ SIGNATURES = {
     "mb_lpips_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_lpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mb_lpips_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
-    "mb_set_cu_count": (C.c_int, [C.c_int]),
+    "mb_fid_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_is_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mb_is_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_set_cu_count":(C.c_int, [C.c_int]),
     "mb_gemm_ht_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mb_prof_enable": (C.c_int, [C.c_int]),
     "mb_prof_read": (C.c_int, [C.c_char_p, C.c_int]),

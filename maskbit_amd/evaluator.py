@@ -8,10 +8,12 @@ metrics, then a small deterministic finalize) and one for the indices (``mb_eval
 calls and a ``.tolist()`` into a Python set); it enqueues on the current stream and never synchronises.  The running state -- four float64
 sums, an int64 histogram, an out-of-range counter -- stays on the device; ``result()`` makes one device-to-host copy.
 
-rFID and the Inception score are not built: they raise at construction, and so does ``enable_lpips_score`` -- that flag means "build LPIPS
-with downloaded weights", which cannot be honoured here.  LPIPS itself is built (``maskbit_amd.LPIPS``, csrc/lpips.hip): attach a model that
+``enable_rfid``, ``enable_inception_score`` and ``enable_lpips_score`` raise at construction: those flags mean "fetch the network and its
+weights", which cannot be honoured here.  LPIPS itself is built (``maskbit_amd.LPIPS``, csrc/lpips.hip): attach a model that
 holds the user's weights with ``use_lpips(model)`` and ``update()`` also enqueues ``mb_lpips_forward`` on the same images into a float64 device
-sum; ``result()`` reports ``"LPIPS"`` where the reference does.  There is no CPU path.
+sum; ``result()`` reports ``"LPIPS"`` where the reference does.  rFID and the Inception score work the same way: ``use_inception(extractor)``
+attaches the caller's Inception network, and everything after it -- the statistics of real and fake features (csrc/fid.hip) and the two closed
+forms -- runs here (``generator_evaluator.py``, which also holds ``GeneratorEvaluator``).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -20,6 +22,8 @@ from typing import Mapping, Optional, Text
 import torch
 
 from . import _lib
+from .generator_evaluator import (FeatureStatistics, GeneratorEvaluator, ScoreStatistics, extract, frechet_distance,  # noqa: F401
+                                  get_covariance, inception_score, to_uint8)
 
 _ABS, _SQ, _SSIM = 1, 2, 4          # metrics bits of mb_eval_images
 
@@ -71,6 +75,9 @@ class TokenizerEvaluator:
         self.last_lpips: Optional[torch.Tensor] = None
         self._lpips = None
         self._lpips_sum: Optional[torch.Tensor] = None
+        self._inception = None                                                                # use_inception(): the extractor and its three states
+        self._rfid = self._inception_score = False
+        self._is_stats = self._rfid_real = self._rfid_fake = None
         if self._device.index is None:
             self._device = torch.device("cuda", torch.cuda.current_device())
         self.reset_metrics()
@@ -92,6 +99,28 @@ class TokenizerEvaluator:
         self.last_lpips = None
         if self._lpips_sum is not None:
             self._lpips_sum.zero_()
+        for stats in (self._is_stats, self._rfid_real, self._rfid_fake):
+            if stats is not None:
+                stats.reset()
+
+    def use_inception(self, extractor, rfid: bool = True, inception_score: bool = True) -> None:
+        """Attaches a feature extractor with the contract of the reference's ``get_inception_model()`` -- uint8 [B, 3, H, W] in,
+        ``{"2048": [B, D], "logits_unbiased": [B, C]}`` out -- (``None`` detaches): ``update()`` then runs it on ``(images * 255).to(uint8)`` of the
+        fake images, and for rFID of the real ones, and accumulates the statistics with ``mb_is_accumulate`` / ``mb_fid_accumulate``
+        (evaluator.py:336-364); ``result()`` reports ``"InceptionScore"`` and ``"rFID"`` where the reference does (evaluator.py:406-451).  Takes
+        the place of ``enable_rfid`` / ``enable_inception_score``, whose network cannot be fetched here.  Attach before the first ``update()`` of a
+        pass, or call ``reset_metrics()``."""
+        if extractor is None:
+            self._inception, self._rfid, self._inception_score = None, False, False
+            return
+        if not callable(extractor):
+            raise TypeError(f"use_inception() takes a callable, got {type(extractor).__name__}")
+        if not (rfid or inception_score):
+            raise ValueError("use_inception(): rfid or inception_score must be asked for")
+        self._inception, self._rfid, self._inception_score = extractor, bool(rfid), bool(inception_score)
+        if self._is_stats is None:
+            self._is_stats, self._rfid_real, self._rfid_fake = (ScoreStatistics(self._device), FeatureStatistics(self._device),
+                                                                FeatureStatistics(self._device))
 
     def use_lpips(self, model) -> None:
         """Attaches a loaded ``maskbit_amd.LPIPS`` on the evaluator's device (``None`` detaches): ``update()`` then also adds the batch's LPIPS
@@ -151,7 +180,20 @@ class TokenizerEvaluator:
                 _lib.check(lib.mb_eval_images(real.data_ptr(), fake.data_ptr(), B, C, H, W, self._metrics, 1 if clamp else 0,
                                               self._workspace.data_ptr(), per_image.data_ptr(), self._sums.data_ptr(), stream), "mb_eval_images")
                 self.last_per_image = per_image
-            if self._lpips is not None:                                                          # evaluator.py:366-368
+            if self._inception is not None:                                                      # evaluator.py:336-364
+                images = (fake_images, real_images.reshape(fake_images.shape))
+                if clamp:
+                    images = tuple(v.clamp(0.0, 1.0) for v in images)
+                pool_fake, logits_fake = extract(self._inception, to_uint8(images[0]), self._rfid, self._inception_score)
+                if self._inception_score:
+                    self._is_stats.add(logits_fake)
+                if self._rfid:
+                    pool_real, _ = extract(self._inception, to_uint8(images[1]), True, False)
+                    if tuple(pool_real.shape) != tuple(pool_fake.shape):
+                        raise ValueError(f"features of the real images {tuple(pool_real.shape)} and of the fake ones {tuple(pool_fake.shape)} differ")
+                    self._rfid_real.add(pool_real)
+                    self._rfid_fake.add(pool_fake)
+            if self._lpips is not None:                                                         # evaluator.py:366-368
                 self.last_lpips = self._lpips._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._lpips_sum)
             if self._codebook:
                 idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
@@ -175,6 +217,14 @@ class TokenizerEvaluator:
             probs = counts / counts.sum()
             entropy = (-torch.log2(probs + 1e-8) * probs).sum()                                # evaluator.py:462-463
             parts += [(self._hist != 0).sum().double().reshape(1), (self._out_of_range.long() & 0xFFFFFFFF).double()]
+        if (self._inception_score and self._is_stats.width is None) or (self._rfid and self._rfid_real.width is None):
+            raise ValueError("use_inception() was called after the updates of this pass: attach the extractor first, or reset_metrics()")
+        at = sum(int(p.numel()) for p in parts)                                                # where the Inception statistics begin
+        if self._inception_score:
+            parts.append(self._is_stats.sums.reshape(-1))
+        if self._rfid:
+            for stats in (self._rfid_real, self._rfid_fake):
+                parts += [stats.total, stats.full_sigma().reshape(-1)]
         host = torch.cat(parts).cpu()                                                           # the one copy
         if self._codebook and host[cb + 1] != 0:
             raise IndexError(f"{int(host[cb + 1])} codebook indices outside [0, {self._num_codebook_entries})")
@@ -188,6 +238,14 @@ class TokenizerEvaluator:
             eval_score["PSNR"] = host[2].item() / n
         if self._enable_ssim_score:
             eval_score["SSIM"] = host[3].item() / n
+        if self._inception_score:                                                               # evaluator.py:406-415
+            C = self._is_stats.width
+            eval_score["InceptionScore"] = inception_score(host[at:at + C], host[at + C:at + 2 * C], n)
+            at += 2 * C
+        if self._rfid:                                                                          # evaluator.py:417-451
+            D = self._rfid_real.width
+            (t_real, s_real), (t_fake, s_fake) = ((host[o:o + D], host[o + D:o + D + D * D].reshape(D, D)) for o in (at, at + D + D * D))
+            eval_score["rFID"] = frechet_distance(t_real / n, get_covariance(s_real, t_real, n), t_fake / n, get_covariance(s_fake, t_fake, n))
         if lp:
             eval_score["LPIPS"] = host[4].item() / n                                            # evaluator.py:453-455
         if self._enable_codebook_usage_measure:

@@ -34,20 +34,12 @@ def mask_token_for(num_codebook_entries: int, codebook_splits: int) -> int:
     return int(2 ** (math.log2(num_codebook_entries) // codebook_splits))
 
 
-@torch.no_grad()
-def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tensor, batchsize: int, *,
-                   softmax_temperature: float = 1.0, randomize_temperature: float = 4.5, mask_schedule_strategy: Text = "linear",
-                   num_steps: int = 12, guidance_scale: float = 3.0, guidance_annealing: Text = "none",
-                   use_sampling_annealing: bool = False, scale_pow: float = 4.0,
-                   total_samples: Optional[int] = None, return_codes: bool = False, seed: Optional[int] = None) -> Iterator[np.ndarray]:
-    """Yield ``total_samples // batchsize`` arrays ``uint8 [batchsize, H, W, 3]`` (host memory), batch *i* generated for
-    ``labels[batchsize * i : batchsize * (i + 1)]`` exactly as eval_maskbit.py:111-135 does.  Each yielded array is a fresh copy
-    (the reference appends them to a list).  ``return_codes=True`` yields ``(images, codes int64 [batchsize, n])`` -- the combined
-    tokens each image was decoded from (what the reference's evaluator takes as ``codebook_indices``, evaluator.py:536).
-    ``seed`` (an int in [0, 2**64)): seeded sampling (``sample_seeded``) -- image ``j`` of the run (global index) is generated from the seed
-    ``(seed + j) mod 2**64``, so the images do not depend on ``batchsize`` and any one of them can be regenerated alone; torch's generators are not
-    consumed."""
-    check_models(model, vqgan_model, "generate_uint8")
+def _device_batches(who: Text, model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tensor, batchsize: int, total_samples: Optional[int],
+                    seed: Optional[int], softmax_temperature, randomize_temperature, mask_schedule_strategy, num_steps, guidance_scale,
+                    guidance_annealing, use_sampling_annealing, scale_pow):
+    """The checks and the plan of a generation run, then an iterator over its batches as DEVICE tensors ``(uint8 [batchsize, H, W, 3], codes int64
+    [batchsize, n])``: the sampling loop of eval_maskbit.py:111-135 up to the decoder's uint8 output.  Nothing in it synchronises."""
+    check_models(model, vqgan_model, who)
     total = int(labels.numel()) if total_samples is None else int(total_samples)
     nbatch = total // batchsize
     if nbatch * batchsize > labels.numel():
@@ -62,11 +54,39 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
         check_seeds([seed], 1)
         run_seeds = check_seeds([(seed + j) % (1 << 64) for j in range(nbatch * batchsize)], nbatch * batchsize)
         plan = seeded_plan(num_steps, guidance_scale, guidance_annealing, scale_pow, softmax_temperature, use_sampling_annealing, mask_schedule_strategy)
-    dev = model._require_cuda("generate_uint8")
+    dev = model._require_cuda(who)
     model.eval()
     vqgan_model.eval()
     if run_seeds is not None:
         run_seeds = run_seeds.to(dev)                   # one copy for the whole run
+
+    def batches():
+        for i in range(nbatch):
+            y = labels[batchsize * i: batchsize * (i + 1)].long()
+            seeds = run_seeds[batchsize * i: batchsize * (i + 1)] if run_seeds is not None else None
+            _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, seeds=seeds, want_steps=False, want_image=False,
+                                          want_u8=True)
+            yield u8, codes
+
+    return batches()
+
+
+@torch.no_grad()
+def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tensor, batchsize: int, *,
+                   softmax_temperature: float = 1.0, randomize_temperature: float = 4.5, mask_schedule_strategy: Text = "linear",
+                   num_steps: int = 12, guidance_scale: float = 3.0, guidance_annealing: Text = "none",
+                   use_sampling_annealing: bool = False, scale_pow: float = 4.0,
+                   total_samples: Optional[int] = None, return_codes: bool = False, seed: Optional[int] = None) -> Iterator[np.ndarray]:
+    """Yield ``total_samples // batchsize`` arrays ``uint8 [batchsize, H, W, 3]`` (host memory), batch *i* generated for
+    ``labels[batchsize * i : batchsize * (i + 1)]`` exactly as eval_maskbit.py:111-135 does.  Each yielded array is a fresh copy
+    (the reference appends them to a list).  ``return_codes=True`` yields ``(images, codes int64 [batchsize, n])`` -- the combined
+    tokens each image was decoded from (what the reference's evaluator takes as ``codebook_indices``, evaluator.py:536).
+    ``seed`` (an int in [0, 2**64)): seeded sampling (``sample_seeded``) -- image ``j`` of the run (global index) is generated from the seed
+    ``(seed + j) mod 2**64``, so the images do not depend on ``batchsize`` and any one of them can be regenerated alone; torch's generators are not
+    consumed."""
+    batches = _device_batches("generate_uint8", model, vqgan_model, labels, batchsize, total_samples, seed, softmax_temperature, randomize_temperature,
+                              mask_schedule_strategy, num_steps, guidance_scale, guidance_annealing, use_sampling_annealing, scale_pow)
+    dev = model._require_cuda("generate_uint8")
     main = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     pinned = [None, None]
@@ -78,10 +98,7 @@ def generate_uint8(model: LFQBert, vqgan_model: ConvVQModel, labels: torch.Tenso
         out = pinned[slot].numpy().copy()
         return (out, codes.cpu().numpy()) if return_codes else out
 
-    for i in range(nbatch):
-        y = labels[batchsize * i: batchsize * (i + 1)].long()
-        seeds = run_seeds[batchsize * i: batchsize * (i + 1)] if run_seeds is not None else None
-        _, u8, _, codes = run_chunked(model, vqgan_model, y, plan, randomize_temperature, seeds=seeds, want_steps=False, want_image=False, want_u8=True)
+    for i, (u8, codes) in enumerate(batches):
         slot = i & 1
         if pinned[slot] is None or pinned[slot].shape != u8.shape:
             pinned[slot] = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
@@ -105,6 +122,27 @@ def to_evaluator_uint8(u8_nhwc: torch.Tensor) -> torch.Tensor:
     network, ``(generated_images * 255).to(torch.uint8)`` on the clamped float image (evaluator/evaluator.py:549-551): the same
     bytes without materialising the float image.  A view, no copy."""
     return u8_nhwc.permute(0, 3, 1, 2)
+
+
+@torch.no_grad()
+def eval_generation(model: LFQBert, vqgan_model: ConvVQModel, evaluator, num_samples: int, batchsize: int, labels: Optional[torch.Tensor] = None, *,
+                    softmax_temperature: float = 1.0, randomize_temperature: float = 4.5, mask_schedule_strategy: Text = "linear",
+                    num_steps: int = 12, guidance_scale: float = 3.0, guidance_annealing: Text = "none",
+                    use_sampling_annealing: bool = False, scale_pow: float = 4.0, seed: Optional[int] = None):
+    """The generation loop of eval_maskbit.py:107-135 with a ``maskbit_amd.GeneratorEvaluator`` as the consumer: ``num_samples // batchsize``
+    batches are sampled and decoded to device uint8 as in ``generate_uint8`` (same arguments, same images for the same ``seed``), and each goes
+    straight into ``evaluator.update_uint8(to_evaluator_uint8(u8), codes)`` -- no float image, no copy to the host, nothing in the loop
+    synchronises.  ``labels`` default to ``eval_labels`` over the model's classes, repeated to cover ``num_samples``.  The evaluator is reset
+    first; returns ``evaluator.result()``."""
+    if labels is None:
+        dev = model._require_cuda("eval_generation")
+        labels = eval_labels(dev, model.nclass, max(1, -(-int(num_samples) // model.nclass)))
+    batches = _device_batches("eval_generation", model, vqgan_model, labels, batchsize, num_samples, seed, softmax_temperature, randomize_temperature,
+                              mask_schedule_strategy, num_steps, guidance_scale, guidance_annealing, use_sampling_annealing, scale_pow)
+    evaluator.reset_metrics()
+    for u8, codes in batches:
+        evaluator.update_uint8(to_evaluator_uint8(u8), codes)
+    return evaluator.result()
 
 
 @torch.no_grad()

@@ -310,6 +310,37 @@ def make_eval_indices(kind: str, K: int, shape, seed: int) -> Tensor:
     raise ValueError(f"unknown index kind {kind!r}")
 
 
+EVAL_FEATURE_KINDS = ("real", "fake")
+
+
+def make_eval_features(D: int, C: int, N: int, seed: int, kind: str = "fake") -> Tuple[Tensor, Tensor]:
+    """Seeded float64 inputs of the FID / Inception-score fixtures: features [N, D], non-negative and correlated like pooled ReLU activations
+    (a per-sample common factor and a neighbour term under the ReLU), and logits [N, C] = 3 * randn with one boosted class per sample, so that
+    the score is neither 1 nor C.  ``kind``: ``real`` or ``fake`` -- the fake features are shifted and widened, for a Frechet distance well
+    above its rounding.  Element-wise operations only: the same bits on every machine."""
+    if kind not in EVAL_FEATURE_KINDS:
+        raise ValueError(f"unknown feature kind {kind!r}")
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(N, D, generator=g, dtype=torch.float64)
+    common = torch.randn(N, 1, generator=g, dtype=torch.float64)
+    bias = torch.rand(1, D, generator=g, dtype=torch.float64)
+    gain, shift = (1.0, 0.0) if kind == "real" else (1.15, 0.1)
+    feats = torch.relu(gain * (z + 0.7 * torch.roll(z, 1, dims=1) + 0.5 * common) + 0.4 * bias + shift)
+    logits = 3.0 * torch.randn(N, C, generator=g, dtype=torch.float64)
+    hot = torch.randint(0, C, (N, 1), generator=g)
+    logits.scatter_add_(1, hot, torch.full((N, 1), 4.0, dtype=torch.float64))
+    return feats.contiguous(), logits.contiguous()
+
+
+def make_eval_statistics(D: int, N: int, seed: int) -> Tuple[Tensor, Tensor]:
+    """Seeded "real" statistics for the FID fixtures, in the format of the reference's ImageNet statistics file: ``mu`` [D] and the sample
+    covariance ``sigma`` [D, D] (float64) of N ``real`` features (N > D: full rank)."""
+    x, _ = make_eval_features(D, 1, N, seed, "real")
+    mu = x.mean(0)
+    xc = x - mu
+    return mu, (xc.T @ xc) / (N - 1)
+
+
 def make_mlm_case(b: int, n: int, m: int, C: int, seed: int) -> Tuple[Tensor, Tensor]:
     """Seeded inputs of the masked-token validation fixtures: logits fp32 [b, n, m, C] = 4 * randn, and targets int64 [b, n, m] = the row's
     argmax on a seeded half of the rows, a uniform draw elsewhere -- accuracies near 0.5, so that ``accuracy ** m`` is not degenerate."""
