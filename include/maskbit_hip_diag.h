@@ -1,5 +1,6 @@
 /* libmaskbit_hip.so -- DIAGNOSTIC entry points: single kernels of the engine on caller buffers, for the unit tests (tests/test_hip_gemm.py,
- * test_hip_pair.py, test_hip_conv.py) and the tools under tools/.  Nothing here is part of the reference's surface and no host binding of the product needs it:
+ * test_hip_pair.py, test_hip_conv.py; the row kernels -- mb_layernorm, mb_layernorm_f4_seq, mb_layernorm_pair, mb_pairify, mb_embed_ln, mb_embed_pair --
+ * in test_hip_rows.py) and the tools under tools/.  Nothing here is part of the reference's surface and no host binding of the product needs it:
  * include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered, 0 / negative return, mb_last_error()).
  */
 #ifndef MASKBIT_HIP_DIAG_H
@@ -52,6 +53,36 @@ int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* 
                        int rows, int N, int kw, const void* const* lo, mb_stream stream);
 int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
                     void* xl4_scale, int M, int d, mb_stream stream);
+/* ... for sequences of seq_rows rows incl. the class token: M % seq_rows == 0, (seq_rows - 1) % 64 == 0; the scale arrays hold
+ * (d / 64) * (M / seq_rows) * (seq_rows - 1) bytes in lane order with (seq_rows - 1) / 64 token groups per sequence.  mb_layernorm_f4 = seq_rows 257. */
+int mb_layernorm_f4_seq(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+                        void* xl4_scale, int M, int d, int seq_rows, mb_stream stream);
+
+/* ---- the other row kernels of norm_embed.hip, each through the product's own launcher (tests/test_hip_rows.py).  Common refusals (-1): a NULL
+ * required pointer, d > 2048, an e2m1 copy (x4 / xl4) without its scale array or the reverse, e2m1 copies at d other than 768 / 1024 or for sequences
+ * whose token count is no multiple of 64.  e2m1 rows have a stride of 2 d bytes (first d / 2 written); class-token rows receive none.
+ * mb_layernorm_pair (mb::layernorm_pair): y fp32 [2 P, d], rows r < P conditional, r + P their unconditional twins -> x_h16 [2 P, d] =
+ * fp16(LN(y_r)) | fp16(LN(y_{r+P}) - LN(y_r)), stats (optional) {mean, rstd} [2 P], the e2m1 set (optional) of the CONDITIONAL rows' values / lo halves
+ * (P % seq_rows == 0 then; seq_rows is not read otherwise).  d = 768 / 1024, anything else returns -3 and writes nothing.
+ * mb_pairify (mb::pairify_rows): the same operands from fp32 rows x_f32 [2 P, d] that already exist. */
+int mb_layernorm_pair(const float* y, const float* gamma, const float* beta, float eps, void* x_h16, float* stats, void* x4, void* x4_scale, void* xl4,
+                      void* xl4_scale, int P, int d, int seq_rows, mb_stream stream);
+int mb_pairify(const float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4, void* xl4_scale, int P, int d, int seq_rows, mb_stream stream);
+/* mb_embed_ln (mb::embed_ln): tokens int64 [nb, seq, m], labels int64 [nb], drop uint8 [nb] or NULL, w_in = input_proj.weight as the checkpoint holds
+ * it, fp32 [d, m * gbits] (transposed inside by the product's kernel, as mb_gen_load does), b_in [d], class_emb [nclass + 1, d], pos [seq + 1, d], gamma /
+ * beta [d] of the first LayerNorm (eps 1e-12), tables (optional; then w_in / b_in may be NULL) = the embedding tables [m][2^gbits + 1][d], row 2^gbits the
+ * mask token's -> x_f32 and x_h16 [nb (seq + 1), d] (both required), x_lo (optional) the fp16 lo halves, the e2m1 set (optional) of the token rows.
+ * Further refusals (-1): m * gbits > 24, more than 8 tables.  The entry trusts the device CONTENTS: the caller passes tokens in [0, 2^gbits] and
+ * labels in [0, nclass], nothing else.  Synchronises the stream (the transposed weight is scratch).
+ * mb_embed_pair (mb::embed_pair): the guided forward's fused form over nb CONDITIONAL sequences: x_f32 / x_h16 [2 nb (seq + 1), d], what mb_embed_ln
+ * over [conditional | label-dropped twins] followed by mb_pairify writes, bit for bit.  Returns -3 and launches nothing where the fused kernel does
+ * not serve (tables, m * gbits > 24, d other than 768 / 1024): the engine then runs those two. */
+int mb_embed_ln(const int64_t* tokens, const int64_t* labels, const uint8_t* drop, const float* w_in, const float* b_in, const float* class_emb,
+                const float* pos, const float* gamma, const float* beta, const float* tables, float* x_f32, void* x_h16, void* x_lo, void* x4,
+                void* x4_scale, void* xl4, void* xl4_scale, int nb, int seq, int m, int gbits, int d, int nclass, mb_stream stream);
+int mb_embed_pair(const int64_t* tokens, const int64_t* labels, const float* w_in, const float* b_in, const float* class_emb, const float* pos,
+                  const float* gamma, const float* beta, const float* tables, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+                  void* xl4_scale, int nb, int seq, int m, int gbits, int d, int nclass, mb_stream stream);
 /* Attention of a CFG pair batch (the generator's guided forward, bert.py:84,137 on both streams): qkv [2 pairs N, 3d] fp16 packed in_proj rows, the
  * conditional sequences first, their unconditional twins `pairs` sequences later.  out rows of conditional sequences = softmax(QK^T/sqrt(dh))V in
  * fp16; rows of unconditional sequences = fp16(o_u - o_c), the difference operand of the out-proj pair GEMM (the conditional output tiles stay in

@@ -81,6 +81,11 @@ SIGNATURES = {
     "mb_w4lo_from_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_layernorm_f4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_void_p]),
+    "mb_layernorm_f4_seq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
+    "mb_layernorm_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
+    "mb_pairify": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
+    "mb_embed_ln": (C.c_int, [C.c_void_p] * 17 + [C.c_int] * 6 + [C.c_void_p]),
+    "mb_embed_pair": (C.c_int, [C.c_void_p] * 15 + [C.c_int] * 6 + [C.c_void_p]),
     "mb_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_attention_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_attention_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -37,6 +37,46 @@ int pool_entry(const char* what, decltype(mb::launch_s2d)* launch, const void* x
   return launched();
 }
 
+// The optional e2m1 outputs of a row kernel (values x4 / x4_scale, fp16 lo halves xl4 / xl4_scale) over `rows` rows of `seq_rows` each, the class
+// token last: the vector kernels alone write them (d = 768 / 1024), and the lane-ordered scale arrays hold whole 64-token groups.
+int f4_rows(const char* who, mb::Fp4Rows& f4, void* x4, void* x4_scale, void* xl4, void* xl4_scale, int rows, int d, int seq_rows) {
+  f4 = mb::Fp4Rows{};
+  if ((x4 != nullptr) != (x4_scale != nullptr) || (xl4 != nullptr) != (xl4_scale != nullptr)) return fail(-1, "%s: an e2m1 copy and its scale array go together", who);
+  if (!x4 && !xl4) return 0;
+  if (d != 768 && d != 1024) return fail(-1, "%s: e2m1 copies are written at d = 768 / 1024 only, not %d", who, d);
+  if (seq_rows < 65 || (seq_rows - 1) % 64 || rows % seq_rows)
+    return fail(-1, "%s: e2m1 copies: sequences of 64 k tokens + the class token, whole sequences (%d rows of %d)", who, rows, seq_rows);
+  f4 = mb::Fp4Rows{(uint8_t*)x4, (uint8_t*)x4_scale, (uint8_t*)xl4, (uint8_t*)xl4_scale, rows / seq_rows, seq_rows};
+  return 0;
+}
+
+// The argument checks of the two embedding entries (the kernels check nothing).  Device CONTENTS are trusted: tokens in [0, 2^gbits], labels in [0, nclass].
+int embed_args(const char* who, mb::EmbedArgs& e, const int64_t* tokens, const int64_t* labels, const float* w_in, const float* b_in, const float* class_emb,
+               const float* pos, const float* gamma, const float* beta, const float* tables, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+               void* xl4_scale, int nb, int seq, int m, int gbits, int d, int nclass) {
+  if (!tokens || !labels || !class_emb || !pos || !gamma || !beta || !x_f32 || !x_h16 || (!tables && (!w_in || !b_in))) return fail(-1, "%s: null argument", who);
+  if (nb <= 0 || seq <= 0 || m <= 0 || gbits <= 0 || d <= 0 || nclass < 0) return fail(-1, "%s: bad sizes", who);
+  if (d > 2048) return fail(-1, "%s: d = %d is beyond the row kernels (2048)", who, d);
+  if ((int64_t)m * gbits > 24) return fail(-1, "%s: %d groups of %d bits are beyond the embed kernels (24 bits)", who, m, gbits);
+  if (tables && m > 8) return fail(-1, "%s: %d embedding tables are beyond the embed kernel (8)", who, m);
+  mb::Fp4Rows f4;
+  if (int rc = f4_rows(who, f4, x4, x4_scale, xl4, xl4_scale, nb * (seq + 1), d, seq + 1)) return rc;
+  e = mb::EmbedArgs{tokens, labels, nullptr, nullptr, b_in, class_emb, pos, gamma, beta, x_f32, (h16*)x_h16, nb, seq, m, gbits, d, nclass, tables};
+  e.f4 = f4;
+  return 0;
+}
+// input_proj.weight as the checkpoint holds it, [d, K] -> e.w_in = [K, d] in the arena, by the product's transpose as mb_gen_load runs it
+int embed_weight(const char* who, mb::DevArena& arena, mb::EmbedArgs& e, const float* w_in, hipStream_t s) {
+  if (e.tables) return 0;
+  const int K = e.m * e.gbits;
+  float* wt = nullptr;
+  arena.get(&wt, (size_t)K * e.d);
+  if (int rc = arena.failed(who)) return rc;
+  mb::transpose_f32(s, w_in, wt, e.d, K);
+  e.w_in = wt;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -114,12 +154,66 @@ int mb_layernorm(const float* y, const float* gamma, const float* beta, float ep
   mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, stats, M, d, (h16*)x_lo);
   return launched();
 }
+int mb_layernorm_f4_seq(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+                        void* xl4_scale, int M, int d, int seq_rows, mb_stream stream) {
+  if (!y || !gamma || !beta || (!x4 && !xl4) || M <= 0) return fail(-1, "mb_layernorm_f4: bad arguments (an e2m1 output is required)");
+  mb::Fp4Rows f4;
+  if (int rc = f4_rows("mb_layernorm_f4", f4, x4, x4_scale, xl4, xl4_scale, M, d, seq_rows)) return rc;
+  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4);
+  return launched();
+}
 int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
                     void* xl4_scale, int M, int d, mb_stream stream) {
-  if (!y || !gamma || !beta || (!x4 && !xl4) || (x4 && !x4_scale) || (xl4 && !xl4_scale) || M <= 0 || M % 257 || (d != 768 && d != 1024))
-    return fail(-1, "mb_layernorm_f4: bad arguments (d must be 768 or 1024, M a multiple of 257)");
-  mb::Fp4Rows f4{(uint8_t*)x4, (uint8_t*)x4_scale, (uint8_t*)xl4, (uint8_t*)xl4_scale, M / 257};
-  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4);
+  return mb_layernorm_f4_seq(y, gamma, beta, eps, x_f32, x_h16, x4, x4_scale, xl4, xl4_scale, M, d, 257, stream);
+}
+
+// ---- the pair forms and the embedding kernels of norm_embed.hip on caller buffers ----
+int mb_layernorm_pair(const float* y, const float* gamma, const float* beta, float eps, void* x_h16, float* stats, void* x4, void* x4_scale, void* xl4,
+                      void* xl4_scale, int P, int d, int seq_rows, mb_stream stream) {
+  if (!y || !gamma || !beta || !x_h16 || P <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_layernorm_pair: bad arguments");
+  mb::Fp4Rows f4;
+  if (int rc = f4_rows("mb_layernorm_pair", f4, x4, x4_scale, xl4, xl4_scale, P, d, seq_rows)) return rc;
+  if (mb::layernorm_pair((hipStream_t)stream, y, gamma, beta, eps, (h16*)x_h16, stats, P, d, f4))
+    return fail(-3, "mb_layernorm_pair: width %d is outside the pair kernels (768 or 1024)", d);
+  return launched();
+}
+int mb_pairify(const float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4, void* xl4_scale, int P, int d, int seq_rows, mb_stream stream) {
+  if (!x_f32 || !x_h16 || P <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_pairify: bad arguments");
+  mb::Fp4Rows f4;
+  if (int rc = f4_rows("mb_pairify", f4, x4, x4_scale, xl4, xl4_scale, P, d, seq_rows)) return rc;
+  if (mb::pairify_rows((hipStream_t)stream, x_f32, (h16*)x_h16, P, d, f4))
+    return fail(-3, "mb_pairify: width %d is outside the pair kernels (768 or 1024)", d);
+  return launched();
+}
+int mb_embed_ln(const int64_t* tokens, const int64_t* labels, const uint8_t* drop, const float* w_in, const float* b_in, const float* class_emb,
+                const float* pos, const float* gamma, const float* beta, const float* tables, float* x_f32, void* x_h16, void* x_lo, void* x4,
+                void* x4_scale, void* xl4, void* xl4_scale, int nb, int seq, int m, int gbits, int d, int nclass, mb_stream stream) {
+  mb::EmbedArgs e;
+  if (int rc = embed_args("mb_embed_ln", e, tokens, labels, w_in, b_in, class_emb, pos, gamma, beta, tables, x_f32, x_h16, x4, x4_scale, xl4, xl4_scale,
+                          nb, seq, m, gbits, d, nclass)) return rc;
+  e.drop = drop; e.x_lo = (h16*)x_lo;
+  mb::DevArena arena;
+  if (int rc = embed_weight("mb_embed_ln", arena, e, w_in, (hipStream_t)stream)) return rc;
+  mb::embed_ln((hipStream_t)stream, e);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(-10, "mb_embed_ln: the launch failed");   // the arena goes on return
+  return launched();
+}
+int mb_embed_pair(const int64_t* tokens, const int64_t* labels, const float* w_in, const float* b_in, const float* class_emb, const float* pos,
+                  const float* gamma, const float* beta, const float* tables, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
+                  void* xl4_scale, int nb, int seq, int m, int gbits, int d, int nclass, mb_stream stream) {
+  // what mb::embed_pair itself refuses (-1 there) is refused here in front of the weight transpose, so that nothing at all is launched
+  // (an e2m1 request at a scalar-path width, or a width beyond 2048, is a bad argument: -1 from embed_args)
+  const bool f4 = x4 || x4_scale || xl4 || xl4_scale;
+  if (tables || (m > 0 && gbits > 0 && (int64_t)m * gbits > 24) || (!f4 && d > 0 && d <= 2048 && d != 768 && d != 1024))
+    return fail(-3, "mb_embed_pair: not served by the fused kernel (embedding tables, more than 24 bits, widths other than 768 / 1024): embed_ln + pairify");
+  mb::EmbedArgs e;
+  if (int rc = embed_args("mb_embed_pair", e, tokens, labels, w_in, b_in, class_emb, pos, gamma, beta, tables, x_f32, x_h16, x4, x4_scale, xl4, xl4_scale,
+                          nb, seq, m, gbits, d, nclass)) return rc;
+  mb::DevArena arena;
+  if (int rc = embed_weight("mb_embed_pair", arena, e, w_in, (hipStream_t)stream)) return rc;
+  const int refused = mb::embed_pair((hipStream_t)stream, e);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(-10, "mb_embed_pair: the launch failed");
+  if (refused) return fail(-3, "mb_embed_pair: not served by the fused kernel");
   return launched();
 }
 
