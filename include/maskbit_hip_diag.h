@@ -45,6 +45,22 @@ int mb_gemm_mini_seq(int epi, const void* A, const void* W, const float* bias, c
  * K-elements) -- in the kernel's lane order (w4_scale_index: byte ((((n >> 6) * (K / 128) + j) * 16 + (n & 15)) * 4 + ((n >> 4) & 3)); N % 64 == 0, K % 128 == 0. */
 int mb_w4_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream);
 int mb_w4lo_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream);
+/* ---- the head path of gemm.hip (tests/test_hip_head.py): the two head GEMMs as the engine's head_gemms fills them, and the two weight-preparation
+ * launchers of mb_gen_load.
+ * mb_gemm_head: out = ((A_hi + A_lo) . W_hi^T + A_hi . W_lo^T) * *scale + bias -- sweeps (A_hi, W_hi), (A_lo, W_hi), (A_hi, W_lo) of kw columns each in one
+ * fp32 accumulator, no lo x lo term; A_* fp16 [M, kw], W_* fp16 [N, kw], scale one device float.  W_lo and scale both NULL: the two-sweep form
+ * (A_hi + A_lo) . W_hi^T + bias (Bert's prediction layer).  epi 3: gelu -> out_f32 [M, N], bias [N].  epi 4: row m with m % period == period - 1 is dropped,
+ * the others land in row (m / period) * (period - 1) + m % period; bias [N], or with bias_per_pos [period - 1][N], row m % period.
+ * Refusals (-1, nothing launched): a NULL required pointer, kw <= 0 or kw % 64, N % 4, an epilogue other than 3 / 4, epilogue 4 with period < 2 or
+ * M % period, bias_per_pos outside epilogue 4, W_lo without scale or the reverse.  -3: the launcher refused. */
+int mb_gemm_head(int epi, const void* A_hi, const void* A_lo, const void* W_hi, const void* W_lo, const float* scale, const float* bias, int bias_per_pos,
+                 float* out_f32, int M, int N, int kw, int period, mb_stream stream);
+/* dst fp16 [n] = IEEE round-to-nearest-even of src fp32 [n], what torch's .half() gives: beyond 65520 -> inf, NaN stays NaN (mb::cast_f32_to_h16: the
+ * trunk weights at load); src and dst 16- / 8-byte aligned, n >= 0. */
+int mb_cast_f32_to_h16(const float* src, void* dst, int64_t n, mb_stream stream);
+/* src fp32 [N, K] -> hi = fp16(src * 2^S), lo = fp16(src * 2^S - hi), *scale_out = 2^-S with S = 15 - e for max |src| = f * 2^e, f in [0.5, 1) (0 for an
+ * all-zero weight): mb::split_f32_to_h16_planes, the head weights at load.  tmp = one device uint32 of the caller's (scratch).  -1: a NULL pointer, N K <= 0. */
+int mb_split_f32_planes(const float* src, void* hi, void* lo, int N, int K, float* scale_out, unsigned* tmp, mb_stream stream);
 /* LayerNorm that also writes the e2m1 copies of its output rows: values (x4 / x4_scale) and / or fp16 lo halves (xl4 / xl4_scale); M % 257 == 0,
  * d = 768 / 1024; class-token rows (row % 257 == 256) are skipped. */
 /* ... the plain forward's default for QKV / FFN-up (precision >= 2): plain sequence tiles over hi + lo activation halves

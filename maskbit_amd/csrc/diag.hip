@@ -141,6 +141,31 @@ int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* 
   return run_gemm(stream, epi, a, 257, "mb_gemm_mini_split");
 }
 
+// ---- the head GEMMs as head_gemms (engine.hip) fills them, and the two weight-preparation launchers of mb_gen_load that had no entry ----
+int mb_gemm_head(int epi, const void* A_hi, const void* A_lo, const void* W_hi, const void* W_lo, const float* scale, const float* bias, int bias_per_pos,
+                 float* out_f32, int M, int N, int kw, int period, mb_stream stream) {
+  if (!A_hi || !A_lo || !W_hi || !bias || !out_f32) return fail(-1, "mb_gemm_head: null argument");
+  if ((W_lo != nullptr) != (scale != nullptr)) return fail(-1, "mb_gemm_head: the weights' lo plane and the scale go together");
+  if (epi != mb::EPI_GELU_F32 && epi != mb::EPI_LOGITS_F32) return fail(-1, "mb_gemm_head: epilogue 3 or 4");
+  if (M <= 0 || N <= 0 || N % 4 || kw <= 0 || kw % 64) return fail(-1, "mb_gemm_head: M > 0, N a multiple of 4, kw a multiple of 64");
+  if (epi == mb::EPI_LOGITS_F32 && (period < 2 || M % period)) return fail(-1, "mb_gemm_head: epilogue 4: whole sequences of period >= 2 rows");
+  if (bias_per_pos && epi != mb::EPI_LOGITS_F32) return fail(-1, "mb_gemm_head: a per-position bias goes with epilogue 4");
+  mb::GemmArgs a{(const h16*)A_hi, (const h16*)W_hi, bias, nullptr, out_f32, nullptr, M, N, (W_lo ? 3 : 2) * kw, period, scale};
+  a.A2 = (const h16*)A_lo; a.kw = kw; a.W2 = (const h16*)W_lo;
+  a.bias_per_pos = bias_per_pos;
+  return run_gemm(stream, epi, a, 0, "mb_gemm_head");
+}
+int mb_cast_f32_to_h16(const float* src, void* dst, int64_t n, mb_stream stream) {
+  if (!src || !dst || n < 0) return fail(-1, "mb_cast_f32_to_h16: bad arguments");
+  mb::cast_f32_to_h16((hipStream_t)stream, src, (h16*)dst, (size_t)n);
+  return launched();
+}
+int mb_split_f32_planes(const float* src, void* hi, void* lo, int N, int K, float* scale_out, unsigned* tmp, mb_stream stream) {
+  if (!src || !hi || !lo || !scale_out || !tmp || N <= 0 || K <= 0) return fail(-1, "mb_split_f32_planes: bad arguments");
+  mb::split_f32_to_h16_planes((hipStream_t)stream, src, (h16*)hi, (h16*)lo, N, K, scale_out, tmp);
+  return launched();
+}
+
 int mb_w4_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, mb_stream stream) {
   return w4_entry("mb_w4_from_f32", mb::w4_from_f32, W, N, K, dst4, scale_out, stream);
 }

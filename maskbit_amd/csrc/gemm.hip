@@ -171,15 +171,17 @@ int gemm_tn(hipStream_t s, GemmEpi epi, const GemmArgs& a, int variant) {
   return 0;
 }
 
+// A WEIGHT's fp16 value is the plain IEEE conversion -- what w4_kernel / w4lo_kernel below take fp16(W) to be and what torch's .half() gives: a weight
+// beyond fp16's range becomes inf and a NaN stays one (loud in every output), where the activations' to_h would store a silent +-65504.
 __global__ void cast_kernel(const float* __restrict__ src, h16* __restrict__ dst, size_t n) {
   size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
   for (; i + 3 < n; i += stride) {
     const float4 v = *(const float4*)(src + i);
-    *(h16x4*)(dst + i) = h16x4{to_h(v.x), to_h(v.y), to_h(v.z), to_h(v.w)};
+    *(h16x4*)(dst + i) = h16x4{(h16)v.x, (h16)v.y, (h16)v.z, (h16)v.w};
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (size_t j = n & ~(size_t)3; j < n; ++j) dst[j] = to_h(src[j]);
+    for (size_t j = n & ~(size_t)3; j < n; ++j) dst[j] = (h16)src[j];
 }
 void cast_f32_to_h16(hipStream_t s, const float* src, h16* dst, size_t n) {
   const int blocks = (int)min((size_t)2048, (n / 4 + 255) / 256 + 1);

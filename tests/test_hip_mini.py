@@ -20,6 +20,9 @@ def _weights(N, K, lib, lo: bool):
     fn = lib.mb_w4lo_from_f32 if lo else lib.mb_w4_from_f32
     _lib.check(fn(W32.data_ptr(), N, K, w4.data_ptr(), wsb.data_ptr(), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+    if lo and N * K <= 2 ** 20:                     # what is decoded below is also what the contract asks for, byte for byte (tests/head_reference.py)
+        import head_reference
+        head_reference.w4lo_check(W32.cpu(), w4.reshape(-1), wsb, label=f"w4lo {N} x {K}")
     return W32, w4, wsb, w4_decode(w4, wsb, N, K)
 
 
