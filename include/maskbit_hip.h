@@ -336,6 +336,23 @@ size_t mb_is_workspace_bytes(int B, int C);
 int mb_is_accumulate(const void* logits, int dtype, int B, int C, int64_t row_stride, double* prob_total, double* kl_total, void* workspace,
                      mb_stream stream);
 
+/* ---- FID Inception-v3 (the network behind the reference's metrics.inception.get_inception_model(): pytorch-fid's pt_inception-2015-12-05) ------ *
+ * fp16 NHWC activations, one general implicit-GEMM convolution on MFMA with a BatchNorm (eval) + ReLU epilogue (csrc/inception.hip); the graph
+ * is the one written out in DESIGN.md "Inception-v3".  The handle holds the packed weights and the activation buffers for max_images images. */
+typedef struct mb_inception mb_inception;
+int mb_inception_create(int max_images, mb_inception** out);
+void mb_inception_destroy(mb_inception* h);
+/* One state-dict entry (device fp32): `<layer>.conv.weight` [Cout, Cin, kh, kw], `<layer>.bn.{weight,bias,running_mean,running_var}` [Cout] for the
+ * 94 BasicConv2d layers, `fc.weight` [1008, 2048], `fc.bias` [1008]; `<layer>.bn.num_batches_tracked` is accepted and ignored.  -2: unknown name,
+ * -4: wrong size. */
+int mb_inception_load(mb_inception* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
+/* u8 uint8 [B, 3, H, W] (H, W >= 2, B <= max_images) -> pool fp32 [B, 2048], logits_unbiased fp32 [B, 1008] = pool @ fc.weight^T, logits = that +
+ * fc.bias; a NULL output is skipped.  A row does not depend on B or on the other images (no floating-point atomics).  No synchronisation.
+ * Fails (-1) before any launch when the checkpoint is incomplete or the geometry is not taken. */
+int mb_inception_forward(mb_inception* h, const uint8_t* u8, int B, int H, int W, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
+/* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
+int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */
 int mb_prof_read(char* buf, int buflen); /* host buffer; writes "name calls total_ms\n" lines */

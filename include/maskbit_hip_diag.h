@@ -183,6 +183,30 @@ int mb_lpips_distance(const void* feat_a, const void* feat_b, const float* w, in
 int mb_lpips_features(mb_lpips* h, const float* real, const float* fake, int B, int H, int W, int clamp01, void* tap0, void* tap1, void* tap2, void* tap3,
                       void* tap4, mb_stream stream);
 
+/* ---- the pieces of the Inception-v3 forward (inception.hip) on caller buffers.
+ * mb_convbn_layer: one BasicConv2d as the network launches it -- convolution (kh x kw in 1 .. 7, stride 1 or 2, zero padding ph < kh, pw < kw, no
+ * bias), fp32 epilogue scale[c] * acc + shift[c], ReLU, saturating fp16 store.  in_h16 fp16 [B, H, W, in_cs] of which channels
+ * [in_off, in_off + Cin) are read (in_off % 8 == 0, in_cs % 8 == 0, in_off + Cin rounded up to 8 <= in_cs); out_h16 [B, Ho, Wo, out_cs] of which
+ * channels [out_off, out_off + Cout) are written and nothing else (Cout, out_off, out_cs % 4 == 0); w_oihw fp32 [Cout, Cin, kh, kw], scale / shift
+ * fp32 [Cout].  variant: 0 = the launcher's choice, 1 = the 64-pixel x 64-channel wave tile, 2 = the 32 x 32 one (the same bits).
+ * *saturated (host) = 4-channel groups clamped at 65504.  Synchronises the stream. */
+int mb_convbn_layer(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
+                    int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
+                    mb_stream stream);
+/* 3 x 3 pools of x fp16 [B, H, W, in_cs] channels [in_off, in_off + C) -> y [B, Ho, Wo, out_cs] channels [out_off, ..): mode 0 = max, stride 2,
+ * no padding (Ho = (H - 3) / 2 + 1); 1 = max, stride 1, padding 1 over the in-image taps only; 2 = average, stride 1, padding 1, fp32 sum of the
+ * in-image taps in row-major order divided by their number, one fp16 rounding.  C, offsets and strides % 8 == 0. */
+int mb_pool3(const void* x_h16, void* y_h16, int B, int H, int W, int C, int mode, int in_off, int in_cs, int out_off, int out_cs, mb_stream stream);
+/* uint8 [B, 3, H, W] -> fp16 [B, 299, 299, 8]: channels 0 .. 2 = (bilinear(x) - 128) / 128 with source coordinate dst * in / 299 (no half-pixel
+ * offset), i0 = (dst * in) / 299 and t = ((dst * in) % 299) / 299 from the integers, v = a0 + (a1 - a0) * t along x, then along y, in fp32;
+ * channels 3 .. 7 = 0. */
+int mb_inception_input(const uint8_t* u8, void* out_h16, int B, int H, int W, mb_stream stream);
+/* One forward with every tap; each output may be NULL.  map0 .. map3: the fp16 NHWC maps after MaxPool_2 [B, 35, 35, 192], Mixed_5d [B, 35, 35, 288],
+ * Mixed_6e [B, 17, 17, 768], Mixed_7c [B, 8, 8, 2048]; tap64 / tap192 / tap768 fp32 [B, C]: the spatial means after the first pool, the second pool
+ * and Mixed_6e; pool, logits_unbiased, logits as in mb_inception_forward. */
+int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, void* map0, void* map1, void* map2, void* map3, float* tap64,
+                      float* tap192, float* tap768, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ from .sampling import sample, sample_seeded
 from .evaluator import TokenizerEvaluator
 from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covariance, inception_score
 from .lpips import LPIPS
+from .inception import InceptionV3, get_inception_model
 from .editing import inpaint, sample_from_tokens
 from .validation import MLMLoss, MaskedTokenEvaluator, get_mask_tokens
 from .harness import (eval_generation, eval_labels, eval_masked_prediction, eval_reconstruction, generate_uint8, mask_token_for,
@@ -18,4 +19,5 @@ __all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "sample", "sample_seed
            "combine_factorized_tokens", "split_factorized_tokens", "eval_labels", "generate_uint8", "mask_token_for", "to_evaluator_uint8",
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",
-           "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance"]
+           "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance",
+           "InceptionV3", "get_inception_model"]

@@ -386,3 +386,111 @@ def make_vgg16_weights(seed: int, style: str = "he") -> StateDict:
             w, b = w * VGG16_GROWN_GAIN, b * gain
         sd[f"{idx}.weight"], sd[f"{idx}.bias"] = w.contiguous(), b.contiguous()
     return sd
+
+
+InceptionConv = Tuple[str, int, int, Tuple[int, int], int, Tuple[int, int]]     # (name, Cin, Cout, (kh, kw), stride, (ph, pw))
+INCEPTION_CONCAT = {"Mixed_5b": 256, "Mixed_5c": 288, "Mixed_5d": 288, "Mixed_6a": 768, "Mixed_6b": 768, "Mixed_6c": 768, "Mixed_6d": 768,
+                    "Mixed_6e": 768, "Mixed_7a": 1280, "Mixed_7b": 2048, "Mixed_7c": 2048}
+INCEPTION_FC = (1008, 2048)
+
+
+def inception_convs() -> List[InceptionConv]:
+    """The 94 ``BasicConv2d`` layers of the FID Inception-v3 (pytorch-fid's ``pt_inception-2015-12-05``) in forward order: the table of shapes
+    behind the state dict.  (The wiring -- which layer reads what -- is DESIGN.md "Inception-v3"; it is not here.)"""
+    L: List[InceptionConv] = []
+
+    def add(name, cin, cout, k=(1, 1), stride=1, pad=(0, 0)):
+        L.append((name, cin, cout, k, stride, pad))
+
+    add("Conv2d_1a_3x3", 3, 32, (3, 3), 2)
+    add("Conv2d_2a_3x3", 32, 32, (3, 3))
+    add("Conv2d_2b_3x3", 32, 64, (3, 3), 1, (1, 1))
+    add("Conv2d_3b_1x1", 64, 80)
+    add("Conv2d_4a_3x3", 80, 192, (3, 3))
+    for n, cin, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        add(n + ".branch1x1", cin, 64)
+        add(n + ".branch5x5_1", cin, 48)
+        add(n + ".branch5x5_2", 48, 64, (5, 5), 1, (2, 2))
+        add(n + ".branch3x3dbl_1", cin, 64)
+        add(n + ".branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+        add(n + ".branch3x3dbl_3", 96, 96, (3, 3), 1, (1, 1))
+        add(n + ".branch_pool", cin, pf)
+    add("Mixed_6a.branch3x3", 288, 384, (3, 3), 2)
+    add("Mixed_6a.branch3x3dbl_1", 288, 64)
+    add("Mixed_6a.branch3x3dbl_2", 64, 96, (3, 3), 1, (1, 1))
+    add("Mixed_6a.branch3x3dbl_3", 96, 96, (3, 3), 2)
+    for n, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):
+        add(n + ".branch1x1", 768, 192)
+        add(n + ".branch7x7_1", 768, c7)
+        add(n + ".branch7x7_2", c7, c7, (1, 7), 1, (0, 3))
+        add(n + ".branch7x7_3", c7, 192, (7, 1), 1, (3, 0))
+        add(n + ".branch7x7dbl_1", 768, c7)
+        add(n + ".branch7x7dbl_2", c7, c7, (7, 1), 1, (3, 0))
+        add(n + ".branch7x7dbl_3", c7, c7, (1, 7), 1, (0, 3))
+        add(n + ".branch7x7dbl_4", c7, c7, (7, 1), 1, (3, 0))
+        add(n + ".branch7x7dbl_5", c7, 192, (1, 7), 1, (0, 3))
+        add(n + ".branch_pool", 768, 192)
+    add("Mixed_7a.branch3x3_1", 768, 192)
+    add("Mixed_7a.branch3x3_2", 192, 320, (3, 3), 2)
+    add("Mixed_7a.branch7x7x3_1", 768, 192)
+    add("Mixed_7a.branch7x7x3_2", 192, 192, (1, 7), 1, (0, 3))
+    add("Mixed_7a.branch7x7x3_3", 192, 192, (7, 1), 1, (3, 0))
+    add("Mixed_7a.branch7x7x3_4", 192, 192, (3, 3), 2)
+    for n, cin in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        add(n + ".branch1x1", cin, 320)
+        add(n + ".branch3x3_1", cin, 384)
+        add(n + ".branch3x3_2a", 384, 384, (1, 3), 1, (0, 1))
+        add(n + ".branch3x3_2b", 384, 384, (3, 1), 1, (1, 0))
+        add(n + ".branch3x3dbl_1", cin, 448)
+        add(n + ".branch3x3dbl_2", 448, 384, (3, 3), 1, (1, 1))
+        add(n + ".branch3x3dbl_3a", 384, 384, (1, 3), 1, (0, 1))
+        add(n + ".branch3x3dbl_3b", 384, 384, (3, 1), 1, (1, 0))
+        add(n + ".branch_pool", cin, 192)
+    return L
+
+
+def make_inception_weights(seed: int, style: str = "he") -> StateDict:
+    """Seeded weights of the FID Inception-v3 under the keys of pytorch-fid's ``pt_inception-2015-12-05-6726825d.pth``: per ``BasicConv2d``
+    ``<name>.conv.weight`` (OIHW, no bias) and ``<name>.bn.{weight,bias,running_mean,running_var}``, then ``fc.weight`` [1008, 2048] and
+    ``fc.bias`` [1008]: 94 x 5 + 2 = 472 entries.  The real checkpoint is not available here; these stand in for it.
+
+    ``"he"``: He-normal convolutions (std = sqrt(2 / fan_in)); BatchNorm gamma in [0.8, 1.2), beta N(0, 0.1), running mean N(0, 0.1) and
+    running variance in [0.8, 1.25): the epilogue scale is near 1 and every layer hands on what a He-initialised ReLU layer does.
+
+    ``"tf"``: gamma exactly 1, as the TF checkpoint has it, and running variances 10^U(-3, 1) per channel -- four decades.  The convolution
+    weights of a channel are the He draw times sqrt(var + 1e-3) and its running mean N(0, 0.1) times the same factor, so that the epilogue
+    scale 1 / sqrt(var + 1e-3) in [0.3, 31] brings every channel back to O(1): an engine that folded the scale into fp16 weights, or dropped
+    it, is far off on these.
+
+    Measured on the real half of ``make_eval_images("noise", 0.05, 2, 64, 64, 5)`` as uint8 (seed 4400; rms / maximum / share of exact zeros of
+    the ReLU outputs behind the taps -- the two pooled taps '64' and '192' read Conv2d_2b and Conv2d_4a through a 3 x 3 maximum, which has next to
+    no zeros itself):
+      he: Conv2d_2b 0.30 / 2.9 / 0.53, Conv2d_4a 0.42 / 3.8 / 0.54, Mixed_5d 0.52 / 3.5 / 0.47, Mixed_6e 0.50 / 3.3 / 0.49, Mixed_7c 0.58 / 3.5 / 0.50
+      tf: Conv2d_2b 0.36 / 3.3 / 0.44, Conv2d_4a 0.52 / 4.1 / 0.59, Mixed_5d 0.61 / 4.1 / 0.51, Mixed_6e 0.72 / 4.4 / 0.48, Mixed_7c 0.83 / 4.6 / 0.48
+    The fp32 taps '64' / '192' / '768' / '2048' have rms 0.45 / 0.60 / 0.46 / 0.53 (he) and 0.53 / 0.69 / 0.66 / 0.77 (tf).
+    No tap is dead or saturated and the zeros stay between 20 % and 80 % (tests/test_inception_cpu.py holds both styles to that).
+    ``fc``: N(0, 1 / sqrt(2048)) weights and N(0, 0.1) bias: logits of order 1."""
+    if style not in ("he", "tf"):
+        raise ValueError(f"unknown Inception weight style {style!r}")
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+    for name, cin, cout, (kh, kw), _stride, _pad in inception_convs():
+        w = torch.randn(cout, cin, kh, kw, generator=g) * math.sqrt(2.0 / (cin * kh * kw))
+        beta = torch.randn(cout, generator=g) * 0.1
+        mean = torch.randn(cout, generator=g) * 0.1
+        u = torch.rand(cout, generator=g)
+        if style == "he":
+            gamma = 0.8 + 0.4 * torch.rand(cout, generator=g)
+            var = 0.8 + 0.45 * u
+        else:
+            gamma = torch.ones(cout)
+            var = torch.pow(10.0, 4.0 * u - 3.0)
+            s = torch.sqrt(var + 1e-3)
+            w, mean = w * s.view(-1, 1, 1, 1), mean * s
+        sd[name + ".conv.weight"] = w.contiguous()
+        sd[name + ".bn.weight"], sd[name + ".bn.bias"] = gamma, beta
+        sd[name + ".bn.running_mean"], sd[name + ".bn.running_var"] = mean, var
+    n, d = INCEPTION_FC
+    sd["fc.weight"] = torch.randn(n, d, generator=g) / math.sqrt(d)
+    sd["fc.bias"] = torch.randn(n, generator=g) * 0.1
+    return sd
