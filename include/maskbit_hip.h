@@ -353,6 +353,31 @@ int mb_inception_forward(mb_inception* h, const uint8_t* u8, int B, int H, int W
 /* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
 int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream);
 
+/* ---- Taming VQGAN tokenizer: OriginalVQModel, modeling/taming_vqgan.py:19-69 (Encoder / Decoder of modeling/taming/taming_autoencoder.py) ---- *
+ * The fixed network of that class: ch 128, ch_mult (1,1,2,2,4), 2 (decoder: 3) res blocks per level, seven single-head AttnBlocks of 512 channels at
+ * the 16-pixel level, quant_conv / post_quant_conv, SimpleVectorizer(1024, 256) without normalisation.  fp16 NHWC activations on the convolution
+ * launchers of the other tokenizers (every conv with bias; GroupNorm without SiLU in front of q / k / v), the attention in csrc/spatial_attention.hip,
+ * the nearest-codeword search of the lookup tokenizer.  latent_size 16 or 32 = 256 x 256 or 512 x 512 images; additions, MB_ABI_VERSION unchanged. */
+typedef struct mb_taming mb_taming;
+int mb_taming_create(int max_batch, int latent_size, mb_taming** out);
+void mb_taming_destroy(mb_taming* h);
+/* One state-dict entry of the reference model (device fp32), by its own key: the 343 entries `encoder.*`, `decoder.*`, `quant_conv.*`,
+ * `post_quant_conv.*`, `quantize.embedding.weight`.  q / k / v of an AttnBlock are stacked into one projection; decoder.conv_out takes decode's
+ * (y + 1) / 2 (weight x 0.5, bias (b + 1) / 2).  -2: unknown name, -4: wrong size. */
+int mb_taming_load(mb_taming* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
+/* OriginalVQModel.encode: img fp32 [B,3,H,W] in [0,1] (scaled x * 2 - 1 on the way in) -> indices int64 [B, h*w] (nearest entry, ties to the lowest
+ * index) and optionally zq fp32 [B,256,h,w] (the selected rows), zraw fp32 [B,256,h,w] (the output of quant_conv) and row_dist fp32 [B*h*w] =
+ * sum_k (z_k - e_idx,k)^2. */
+int mb_taming_encode(mb_taming* h, const float* img_nchw, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, mb_stream stream);
+/* OriginalVQModel.decode_tokens: tokens int64 [B, h*w] (clamped to [0, 1024) on the device) -> img_nchw fp32 [B,3,H,W] unclamped and / or
+ * img_nhwc_u8 uint8 [B,H,W,3] = trunc(clamp(x,0,1)*255); at least one of the two. */
+int mb_taming_decode(mb_taming* h, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream);
+/* OriginalVQModel.decode of any float latent z_nchw fp32 [B,256,h,w]. */
+int mb_taming_decode_latent(mb_taming* h, const float* z_nchw, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream);
+/* 4-channel activation groups (conv outputs incl. q / k / v, attention outputs, latent packs) clamped at the fp16 range since the last reset.
+ * Synchronises `stream`; nothing else of this handle does. */
+int mb_taming_saturation_count(mb_taming* h, unsigned* count, int reset, mb_stream stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */
 int mb_prof_read(char* buf, int buflen); /* host buffer; writes "name calls total_ms\n" lines */

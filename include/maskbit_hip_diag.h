@@ -207,6 +207,18 @@ int mb_inception_input(const uint8_t* u8, void* out_h16, int B, int H, int W, mb
 int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, void* map0, void* map1, void* map2, void* map3, float* tap64,
                       float* tap192, float* tap768, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
 
+/* ---- the Taming tokenizer (spatial_attention.hip, taming.hip).
+ * mb_spatial_attention: the AttnBlock's attention as the handle launches it: one head of 512 channels over the N pixels of each of B images,
+ * out[b, i] = sum_j softmax_j(q[b, i] . k[b, j] * 512^-0.5) v[b, j].  q, k, v fp16, pixel (b, i) at element (b N + i) * ld of each (ld >= 512,
+ * ld % 8 == 0; slices of one [B N, 1536] projection have ld = 1536), out_h16 fp16 rows at stride ldo (>= 512, % 4 == 0); N % 16 == 0,
+ * 16 <= N <= 1024.  Scores and P V on MFMA with fp32 accumulation, fp32 streaming softmax over 32-key blocks, probabilities rounded to fp16 for P V.
+ * No atomics on data, tiles per image: bitwise deterministic and independent of B.  *sat (device, may be NULL) += output groups of 4 clamped at
+ * the fp16 range.  Refused (-1, nothing launched): a NULL pointer, a shape outside the above.
+ * mb_taming_set_tap: the next forwards of the handle also copy the output of AttnBlock `block` (0, 1 = encoder.down.4.attn.{0,1}, 2 =
+ * encoder.mid.attn_1, 3 = decoder.mid.attn_1, 4 .. 6 = decoder.up.4.attn.{0,1,2}) to out_h16 fp16 [B, N, 512]; NULL removes the tap. */
+int mb_spatial_attention(const void* q, const void* k, const void* v, void* out_h16, unsigned* sat, int B, int N, int ld, int ldo, mb_stream stream);
+int mb_taming_set_tap(mb_taming* h, int block, void* out_h16);
+
 #ifdef __cplusplus
 }
 #endif

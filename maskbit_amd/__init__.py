@@ -3,6 +3,7 @@ reference's LFQBert / ConvVQModel / sample() call surface)."""
 from .base_model import BaseModel
 from .bert import Bert, LFQBert
 from .conv_vqgan import ConvVQModel
+from .taming_vqgan import OriginalVQModel
 from .factorization import combine_factorized_tokens, split_factorized_tokens
 from .masking import get_masking_ratio
 from .sampling import sample, sample_seeded
@@ -15,7 +16,7 @@ from .validation import MLMLoss, MaskedTokenEvaluator, get_mask_tokens
 from .harness import (eval_generation, eval_labels, eval_masked_prediction, eval_reconstruction, generate_uint8, mask_token_for,
                       to_evaluator_uint8)
 
-__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "sample", "sample_seeded", "get_masking_ratio",
+__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sample", "sample_seeded", "get_masking_ratio",
            "combine_factorized_tokens", "split_factorized_tokens", "eval_labels", "generate_uint8", "mask_token_for", "to_evaluator_uint8",
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",

@@ -138,6 +138,15 @@ SIGNATURES = {
     "mb_pool3": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
     "mb_inception_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_inception_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "mb_taming_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mb_taming_destroy": (None, [C.c_void_p]),
+    "mb_taming_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "mb_taming_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_taming_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_taming_decode_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_taming_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
+    "mb_taming_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_spatial_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "mb_set_cu_count":(C.c_int, [C.c_int]),
     "mb_gemm_ht_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mb_prof_enable": (C.c_int, [C.c_int]),

@@ -15,6 +15,7 @@
 // (one (sum, sumsq) pair per 8x16-pixel tile and group, written next to the tile), level two in gn_finalize_kernel before the consuming conv;
 // only tensors that no conv of this file produced (the encoder's average-pooled ones) still take the separate sweep (gn_partial_kernel).
 #include <algorithm>
+#include <cassert>
 #include <type_traits>
 
 #include "mb_conv.h"
@@ -43,7 +44,8 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // workgroups per CU (74 KiB each) but FOUR waves per SIMD at the same 125 VGPRs, stages each weight tile for twice the pixels and shrinks the
 // halo overhead from 1.41 to 1.27 pixels read per pixel written.
 // RELU (the VGG16 stack of lpips.hip): max(v, 0) after bias, before the fp16 store.  Off by default: every instantiation without it compiles to the code it had.
-template <int NI, int WN, int KS, bool UP, bool FINAL, int TH = 8, bool RELU = false>
+// SILU = false (the q / k / v projection of the Taming AttnBlock, whose `norm` has no nonlinearity behind it): the prologue applies (scale, shift) only.
+template <int NI, int WN, int KS, bool UP, bool FINAL, int TH = 8, bool RELU = false, bool SILU = true>
 __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
   constexpr int NTHR = 32 * TH, NWAVE = NTHR / 64;
   constexpr int WM = NWAVE / WN, MJ = TH / WM, BN = WN * NI * 16;
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(32 * TH, TH / 4) void conv_kernel(ConvArgs a) {
           if (a.gn) {
             h16x8 v = *slot;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = to_h(silu(fmaf((float)v[e], sc[e], sh[e])));
+            for (int e = 0; e < 8; ++e) { const float f = fmaf((float)v[e], sc[e], sh[e]); v[e] = to_h(SILU ? silu(f) : f); }
             *slot = v;
           }
         } else {
@@ -524,7 +526,8 @@ void launch_lfq(hipStream_t s, const h16* z, int64_t* idx, float* zq, float* zra
 }
 
 void launch_conv(hipStream_t s, GnCtx* gc, const Conv& c, const h16* in, const float2* gn, const h16* residual, h16* out,
-                 float* img, uint8_t* u8, int B, int H, int W, bool final_, bool stats) {
+                 float* img, uint8_t* u8, int B, int H, int W, bool final_, bool stats, bool gn_silu) {
+  assert((gn_silu || !gn || (c.ks == 1 && !final_)) && "the GroupNorm prologue without SiLU is built for 1x1 convolutions only");
   // GroupNorm partials of the output ride in the epilogue when a GroupNorm will read it (stats) and its groups are whole lane groups of a tile
   const int cpg = c.cout / 32;
   const bool part = !final_ && stats && c.cout % 128 == 0 && (cpg == 4 || cpg == 8 || cpg == 16);
@@ -536,6 +539,7 @@ void launch_conv(hipStream_t s, GnCtx* gc, const Conv& c, const h16* in, const f
   gc->ntile = (H / th) * (W / TW);
   dim3 grid((unsigned)((size_t)B * (H / th) * (W / TW) * (c.cout_pad / bn))), block(32 * th);
   if (final_) hipLaunchKernelGGL((conv_kernel<1, 1, 3, false, true>), grid, block, 0, s, a);
+  else if (c.ks == 1 && gn && !gn_silu) hipLaunchKernelGGL((conv_kernel<4, 2, 1, false, false, 8, false, false>), grid, block, 0, s, a);
   else if (c.ks == 1) hipLaunchKernelGGL((conv_kernel<4, 2, 1, false, false>), grid, block, 0, s, a);
   else if (c.ks == 2) hipLaunchKernelGGL((conv_kernel<4, 2, 2, false, false>), grid, block, 0, s, a);
   else if (c.up && th16) hipLaunchKernelGGL((conv_kernel<4, 2, 3, true, false, 16>), grid, block, 0, s, a);

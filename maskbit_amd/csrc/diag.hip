@@ -8,6 +8,7 @@
 #include "mb_abi.h"
 #include "mb_conv.h"
 #include "mb_kernels.h"
+#include "mb_spattn.h"
 #include "mb_vq.h"
 
 using mb::fail;
@@ -404,6 +405,14 @@ int mb_conv_relu_layer(const void* in_h16, const float* w_oihw, const float* bia
   ok = hipMemcpyAsync(&nsat, c.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
   if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_conv_relu_layer: copy failed");
   if (saturated) *saturated = nsat;
+  return launched();
+}
+// the spatial self-attention launch of the Taming tokenizer's AttnBlock (spatial_attention.hip), as the handle issues it
+int mb_spatial_attention(const void* q, const void* k, const void* v, void* out_h16, unsigned* sat, int B, int N, int ld, int ldo, mb_stream stream) {
+  using namespace mb;
+  if (!q || !k || !v || !out_h16) return fail(-1, "mb_spatial_attention: null argument");
+  if (!launch_spatial_attention((hipStream_t)stream, SpAttn{(const h16*)q, (const h16*)k, (const h16*)v, (h16*)out_h16, sat, B, N, ld, ldo}))
+    return fail(-1, "mb_spatial_attention: B >= 1, N a multiple of 16 in [16, 1024], ld >= 512 a multiple of 8, ldo >= 512 a multiple of 4");
   return launched();
 }
 int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_maxpool2", mb::launch_maxpool2, x_h16, y_h16, B, H, W, C, stream); }

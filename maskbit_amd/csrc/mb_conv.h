@@ -48,8 +48,9 @@ inline void launch_repack_conv(hipStream_t s, const Conv& c, const float* w_oihw
 // One convolution of the tokenizer on fp16 NHWC (H % 8 == 0, W % 16 == 0): `gn` (or null) = the (scale, shift) of a GroupNorm + SiLU prologue,
 // `residual` (or null) added in the epilogue; final_: fp32 NCHW `img` and / or uint8 NHWC `u8` instead of `out`.  With `stats` the epilogue leaves the
 // GroupNorm partials of `out` in gc where the channel count allows it (gc->of == out then), for the launch_gn that follows.
+// gn_silu = false (1x1 convolutions only): the prologue is the GroupNorm alone, without SiLU.
 void launch_conv(hipStream_t s, GnCtx* gc, const Conv& c, const h16* in, const float2* gn, const h16* residual, h16* out, float* img, uint8_t* u8,
-                 int B, int H, int W, bool final_, bool stats = true);
+                 int B, int H, int W, bool final_, bool stats = true, bool gn_silu = true);
 // GroupNorm(32 groups, eps 1e-6) statistics of x [B, HW, n.c] -> gc->ss: from the partials the last conv left when x is that conv's output, else a sweep
 void launch_gn(hipStream_t s, GnCtx* gc, const Norm& n, const h16* x, int B, int HW);
 

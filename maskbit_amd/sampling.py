@@ -21,6 +21,7 @@ from . import _lib
 from .bert import LFQBert
 from .conv_vqgan import ConvVQModel
 from .masking import get_masking_ratio
+from .taming_vqgan import OriginalVQModel
 from .parallel import slice_noise
 
 
@@ -107,6 +108,9 @@ def check_models(model, vqgan_model, what: str) -> None:
     """``what()`` runs on this package's own models (there is no fall-back for others), and the tokenizer holds the generator's codes."""
     if not isinstance(model, LFQBert):
         raise TypeError(f"{what}() needs a maskbit_amd LFQBert generator, got {type(model).__name__}")
+    if isinstance(vqgan_model, OriginalVQModel):
+        raise TypeError(f"{what}() does not take the Taming VQGAN tokenizer (OriginalVQModel): the sampling loop decodes through a ConvVQModel engine, "
+                        "and the reference pairs no generator with this tokenizer")
     if not isinstance(vqgan_model, ConvVQModel):
         raise TypeError(f"{what}() needs a maskbit_amd ConvVQModel tokenizer, got {type(vqgan_model).__name__}")
     check_tokenizer(model, vqgan_model)

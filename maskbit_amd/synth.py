@@ -262,6 +262,32 @@ def make_tokenizer_weights(cfg: TokCfg, seed: int = 0, with_encoder: bool = Fals
     return sd
 
 
+def make_taming_weights(seed: int = 0, qk_gain: float = 1.0) -> StateDict:
+    """Seeded weights of the Taming VQGAN tokenizer (``OriginalVQModel``) with the reference's 343 key names and shapes, in the state dict's own
+    order: conv weights randn / sqrt(fan_in), conv biases ~ 0.05, GroupNorm gamma ~ 1 -- O(1) activations through the depth, as
+    make_tokenizer_weights.  ``qk_gain`` multiplies the q and k weights and biases of the seven AttnBlocks: with the plain draw the scores have
+    unit variance and the softmax over 256 keys is nearly uniform, which would leave the attention untested end to end; the scores' spread grows
+    with the square of the gain.  ``quantize.embedding.weight`` is a placeholder of zeros: the codebook comes from make_vq_codebook on the
+    latent statistics, as for the other lookup tokenizers."""
+    from .taming_vqgan import CODEBOOK_SIZE, TOKEN_SIZE, taming_specs, _conv
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+    specs = taming_specs() + [("quantize.embedding.weight", (CODEBOOK_SIZE, TOKEN_SIZE), "codebook")] + \
+        _conv("quant_conv", TOKEN_SIZE, TOKEN_SIZE, 1) + _conv("post_quant_conv", TOKEN_SIZE, TOKEN_SIZE, 1)
+    for key, shape, kind in specs:
+        if kind == "codebook":
+            sd[key] = torch.zeros(shape)
+        elif len(shape) == 4:
+            sd[key] = torch.randn(*shape, generator=g) / math.sqrt(shape[1] * shape[2] * shape[3])
+        elif kind == "ones":
+            sd[key] = 1.0 + torch.randn(*shape, generator=g) * 0.05
+        else:
+            sd[key] = torch.randn(*shape, generator=g) * 0.05
+        if key.rsplit(".", 2)[-2] in ("q", "k"):
+            sd[key] = sd[key] * qk_gain
+    return sd
+
+
 def make_vq_codebook(codebook_size: int, token_size: int, seed: int, mean, std) -> Tensor:
     """Seeded lookup-quantizer codebook [C, K] = randn * std + mean (per channel): entries at the scale of the encoder's latents, so that the
     nearest-entry search is not trivial (the reference's uniform(+-1/C) init puts every entry next to the origin)."""
