@@ -67,6 +67,11 @@ int mb_split_f32_planes(const float* src, void* hi, void* lo, int N, int K, floa
  * (A_hi, A_lo [rows, kw]; the fp16 sweep runs twice over W [N, kw]) AND one mini-tile operand set over the kw columns; epi 0 / 1. */
 int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, void* out_h16, void* out4, void* out4_scale,
                        int rows, int N, int kw, const void* const* lo, mb_stream stream);
+/* ... and the residual GEMMs as the engine launches them (epilogue 2): y [rows (pair: 2 rows), N] fp32 holds the PRE-LayerNorm rows on entry; the
+ * residual that is added is LayerNorm(y) re-derived from ln_stats = {mean, rstd} per row, ln_g, ln_b, and y is updated in place.  Arguments otherwise
+ * as mb_gemm_mini_seq. */
+int mb_gemm_mini_ln(const void* A, const void* W, const float* bias, float* y, const float* ln_stats, const float* ln_g, const float* ln_b, int rows, int pair,
+                    int seq_rows, int N, int K, int nlo, const void* const* lo, mb_stream stream);
 int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
                     void* xl4_scale, int M, int d, mb_stream stream);
 /* ... for sequences of seq_rows rows incl. the class token: M % seq_rows == 0, (seq_rows - 1) % 64 == 0; the scale arrays hold
@@ -124,6 +129,20 @@ int mb_gen_set_alo(mb_gen* g, int gemm_mask);
 /* Persistent kernels launch one workgroup per CU.  On a stream created with a CU mask (hipExtStreamCreateWithCUMask) fewer CUs serve the launch:
  * n = the CUs the following launches should size their grids for, 0 = the device's count (default).  Process-wide, not thread-safe. */
 int mb_set_cu_count(int n);
+/* Walk order.  Every trunk launch takes a direction: 0 visits its tiles / workgroups / rows front to back, 1 is the exact mirror in time (the same work,
+ * bit-identical results).  The generator alternates it along the launch chain of a forward so that a kernel starts on what its producer wrote last.
+ * mb_gen_set_walk: 1 = alternating (the product's default), 0 = every launch in direction 0 -- for timing both in one process and comparing their logits.
+ * mb_diag_set_walk: the direction the per-launch entries of this header (mb_gemm*, mb_attention*, mb_layernorm*, mb_pairify) hand to their kernel from
+ * now on (process-wide, not thread-safe; default 0).  C has no default arguments, so this stands in for a trailing parameter of each of those entries.
+ * mb_walk_tile / mb_walk_seq / mb_walk_row / mb_walk_group: the order functions themselves, evaluated on the host (no GPU needed; -1 on a bad index):
+ * virtual block -> logical tile of the persistent GEMM walk; slot -> sequence (pair) of the grid kernels, `grp` sequences per GEMM super-row; slot -> row
+ * of the row kernels over whole sequences of seq_rows (pair: pair tiles); sequences per super-row. */
+int mb_gen_set_walk(mb_gen* g, int mode);
+int mb_diag_set_walk(int reverse);
+int mb_walk_tile(int vb, int ntiles, int reverse);
+int mb_walk_seq(int slot, int n, int grp, int reverse);
+int mb_walk_row(int slot, int rows, int seq_rows, int pair, int reverse);
+int mb_walk_group(int seq_rows, int pair);
 /* Host only: 1 if the half-tile kernel (gemm_ht.hip) takes a plain M x N x K GEMM with this epilogue, 0 if the launcher falls back to the 128 x 128
  * kernel -- among other rules, the kernel's 32-bit byte offsets need M * K * 2 and N * K * 2 below 2^32. */
 int mb_gemm_ht_supported(int epi, int M, int N, int K);

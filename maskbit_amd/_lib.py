@@ -100,6 +100,7 @@ SIGNATURES = {
                                    C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "mb_gemm_mini_split": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_void_p), C.c_void_p]),
+    "mb_gemm_mini_ln": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.c_void_p]),
     "mb_gemm_act_split": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p]),
     "mb_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -148,6 +149,12 @@ SIGNATURES = {
     "mb_taming_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mb_spatial_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "mb_set_cu_count":(C.c_int, [C.c_int]),
+    "mb_gen_set_walk": (C.c_int, [C.c_void_p, C.c_int]),
+    "mb_diag_set_walk": (C.c_int, [C.c_int]),
+    "mb_walk_tile": (C.c_int, [C.c_int] * 3),
+    "mb_walk_seq": (C.c_int, [C.c_int] * 4),
+    "mb_walk_row": (C.c_int, [C.c_int] * 5),
+    "mb_walk_group": (C.c_int, [C.c_int] * 2),
     "mb_gemm_ht_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mb_prof_enable": (C.c_int, [C.c_int]),
     "mb_prof_read": (C.c_int, [C.c_char_p, C.c_int]),

@@ -82,7 +82,8 @@ template <int DH, int AUX = 0>
 __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
                                                           int N, int d, int heads, float scale_log2e, int sq_off = 0,
                                                           uint8_t* __restrict__ out4 = nullptr, uint8_t* __restrict__ out4s = nullptr, int out4_nseq = 0,
-                                                          uint8_t* __restrict__ out4l = nullptr, uint8_t* __restrict__ out4ls = nullptr) {
+                                                          uint8_t* __restrict__ out4l = nullptr, uint8_t* __restrict__ out4ls = nullptr,
+                                                          int reverse = 0, int wgrp = 8) {
   // out4 / out4s (AUX 4: conditional sequences; AUX 5: the plain forward, every sequence; optional): e2m1 of the output VALUES (row stride 2d
   // bytes) with one E8M0 scale byte per (row, head) in the lane-ordered layout of the GEMM's mini-tile passes (GemmArgs.lo; out4_nseq sequences),
   // DH = 64, N = 257 -- the token operand of the out-proj GEMM's weight-correction pass
@@ -98,7 +99,10 @@ __global__ __launch_bounds__(64 * ATT_NW, 2) void attention_kernel(const h16* __
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   char* Ks = smem;
   char* Vs = Ks + ATT_NP * ROW;
-  const int sq0 = blockIdx.x / heads, h = blockIdx.x - sq0 * heads;
+  // walk order (mb_kernels.h): workgroup slot -> (sequence or pair, head), mirrored as a whole in direction 1; once per workgroup, in SGPRs
+  const int wslot = reverse ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int sslot = wslot / heads, h = wslot - sslot * heads;
+  const int sq0 = walk_seq(sslot, (int)gridDim.x / heads, wgrp, 0);
   const size_t rs = (size_t)3 * d;                                   // qkv row stride (elements)
   // AUX = 4: the workgroup handles the conditional sequence and then its unconditional twin (two passes over the same code); the conditional
   // output tiles stay in registers (oc) for the subtraction -- one launch, and still two 72 KiB workgroups per CU
@@ -335,7 +339,8 @@ template <int DH, bool PAIRM = false>
 __global__ __launch_bounds__(256, 2) void attention_long_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
                                                                int N, int d, int heads, int nchunk, float scale_log2e, int sq_off = 0,
                                                                uint8_t* __restrict__ out4 = nullptr, uint8_t* __restrict__ out4s = nullptr, int out4_nseq = 0,
-                                                               uint8_t* __restrict__ out4l = nullptr, uint8_t* __restrict__ out4ls = nullptr) {
+                                                               uint8_t* __restrict__ out4l = nullptr, uint8_t* __restrict__ out4ls = nullptr,
+                                                               int reverse = 0, int wgrp = 8) {
   constexpr int ROW = DH * 2, SL = DH / 8, KS = DH / 32, NT = DH / 16, RPI = 64 / SL;
   constexpr int BLK_BYTES = ATTL_KB * ROW;                 // one operand block
   constexpr int NINST = ATTL_KB / RPI;                     // DMA instructions per operand block (16 or 8)
@@ -343,9 +348,10 @@ __global__ __launch_bounds__(256, 2) void attention_long_kernel(const h16* __res
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BLK_BYTES];   // [buffer][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int bid = blockIdx.x;
+  int bid = reverse ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;   // walk order: see attention_kernel
   const int chunk = bid % nchunk; bid /= nchunk;
-  const int sq0 = bid / heads, h = bid - sq0 * heads;
+  const int sslot = bid / heads, h = bid - sslot * heads;
+  const int sq0 = walk_seq(sslot, (int)gridDim.x / (heads * nchunk), wgrp, 0);
   const size_t rs = (size_t)3 * d;
   auto kswz = [](int row) { return SL == 8 ? ((row >> 1) & 7) : ((0 - (row >> 2)) & 3); };
   auto vswz = [](int row) { return SL == 8 ? (((row >> 1) & 3) << 1) : (((row >> 1) & 1) << 1); };
@@ -568,26 +574,31 @@ int attention_probs(hipStream_t s, const h16* qkv, float* out, int nb, int N, in
 // Shorter sequences (a 128-pixel model has 64 + 1 tokens) go to the streaming kernels, which mask every key >= N.
 static bool att_streams(int N) { return N > ATT_NP || N < ATT_NP - 32; }
 
-void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, int heads, uint8_t* out4, uint8_t* out4s) {
+void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, int heads, uint8_t* out4, uint8_t* out4s, int reverse) {
   const int dh = d / heads;
+  const int wg = walk_group(N, false);
+  uint8_t* const nil = nullptr;
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
   if (att_streams(N)) {                                       // longer than one head's K/V fits in LDS, or shorter than the one-block kernel masks
     const int nchunk = (N + 63) / 64;
     const bool f4 = N > ATT_NP && (N - 1) % 64 == 0;          // (the e2m1 copy exists for 257 tokens and for whole 64-token groups beyond 288)
     dim3 grid(nb * heads * nchunk), block(256);
-    if (dh == 64) hipLaunchKernelGGL(attention_long_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, 0, f4 ? out4 : nullptr, f4 ? out4s : nullptr, nb);
-    else hipLaunchKernelGGL(attention_long_kernel<32>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e);
+    if (dh == 64) hipLaunchKernelGGL(attention_long_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, 0, f4 ? out4 : nil, f4 ? out4s : nil, nb, nil, nil, reverse, wg);
+    else hipLaunchKernelGGL(attention_long_kernel<32>, grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, 0, nil, nil, 0, nil, nil, reverse, wg);
     return;
   }
   dim3 grid(nb * heads), block(64 * ATT_NW);
   if (out4 && dh == 64 && N == 257)        // plain forward with the weight-correction mini-tiles: also the e2m1 copy of the outputs
-    hipLaunchKernelGGL((attention_kernel<64, 5>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, 0, out4, out4s, nb);
-  else if (dh == 64) hipLaunchKernelGGL(attention_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, scale_log2e);
-  else hipLaunchKernelGGL(attention_kernel<32>, grid, block, 0, s, qkv, out, N, d, heads, scale_log2e);
+    hipLaunchKernelGGL((attention_kernel<64, 5>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, 0, out4, out4s, nb, nil, nil, reverse, wg);
+  else if (dh == 64) hipLaunchKernelGGL(attention_kernel<64>, grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, 0, nil, nil, 0, nil, nil, reverse, wg);
+  else hipLaunchKernelGGL(attention_kernel<32>, grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, 0, nil, nil, 0, nil, nil, reverse, wg);
 }
 
-int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d, int heads, uint8_t* out4, uint8_t* out4s, uint8_t* out4l, uint8_t* out4ls) {
+int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d, int heads, uint8_t* out4, uint8_t* out4s, uint8_t* out4l, uint8_t* out4ls,
+                   int reverse) {
   const int dh = d / heads;
+  const int wg = walk_group(N, true);
+  uint8_t* const nil = nullptr;
   if (dh != 64 && dh != 32) return -1;
   if ((out4l || out4ls) && (!out4 || !out4s || !out4l || !out4ls)) return -1;   // the lo copy rides with the value copy
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
@@ -595,15 +606,15 @@ int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d,
     if ((out4 || out4s) && (dh != 64 || (N - 1) % 64 || N < ATT_NP)) return -1;
     const int nchunk = ((N + 15) / 16 + 3) / 4;
     dim3 grid(P * heads * nchunk), block(256);
-    if (dh == 64) hipLaunchKernelGGL((attention_long_kernel<64, true>), grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, P, out4, out4s, P, out4l, out4ls);
-    else hipLaunchKernelGGL((attention_long_kernel<32, true>), grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, P);
+    if (dh == 64) hipLaunchKernelGGL((attention_long_kernel<64, true>), grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, P, out4, out4s, P, out4l, out4ls, reverse, wg);
+    else hipLaunchKernelGGL((attention_long_kernel<32, true>), grid, block, 0, s, qkv, out, N, d, heads, nchunk, scale_log2e, P, nil, nil, 0, nil, nil, reverse, wg);
     return 0;
   }
   dim3 grid(P * heads), block(64 * ATT_NW);
   if ((out4 || out4s) && (dh != 64 || N != 257)) return -1;   // the fp4 output exists for head dimension 64 and 257-token sequences
   // one workgroup per (pair, head): conditional pass, then the twin; conditional outputs parked in registers
-  if (dh == 64) hipLaunchKernelGGL((attention_kernel<64, 4>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, P, out4, out4s, P, out4l, out4ls);
-  else hipLaunchKernelGGL((attention_kernel<32, 4>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, P);
+  if (dh == 64) hipLaunchKernelGGL((attention_kernel<64, 4>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, P, out4, out4s, P, out4l, out4ls, reverse, wg);
+  else hipLaunchKernelGGL((attention_kernel<32, 4>), grid, block, 0, s, qkv, out, N, d, heads, scale_log2e, P, nil, nil, 0, nil, nil, reverse, wg);
   return 0;
 }
 

@@ -17,8 +17,13 @@ using mb::ProfScope;
 
 namespace {
 
+// The walk direction (mb_kernels.h walk_tile / walk_seq) the per-launch entries below hand to their trunk kernel: mb_diag_set_walk, 0 unless a test sets it.
+int g_walk_reverse = 0;
+
 // The common tail of the GEMM entries: the timed launch, the refusal message (`mini`: the entry's name, sequence-aligned tiles), the launch check.
-int run_gemm(mb_stream stream, int epi, const mb::GemmArgs& a, int variant, const char* mini = nullptr) {
+int run_gemm(mb_stream stream, int epi, const mb::GemmArgs& args, int variant, const char* mini = nullptr) {
+  mb::GemmArgs a = args;
+  a.reverse = g_walk_reverse;
   ProfScope p("gemm_diag", (hipStream_t)stream);
   if (mb::gemm_tn((hipStream_t)stream, (mb::GemmEpi)epi, a, variant))
     return mini ? fail(-3, "%s: shape refused", mini) : fail(-3, "GEMM shape M=%d N=%d K=%d is outside the kernels' shapes", a.M, a.N, a.K);
@@ -83,6 +88,17 @@ int embed_weight(const char* who, mb::DevArena& arena, mb::EmbedArgs& e, const f
 extern "C" {
 
 int mb_set_cu_count(int n) { mb::set_cu_count(n); return 0; }
+int mb_diag_set_walk(int reverse) {
+  if (reverse != 0 && reverse != 1) return fail(-1, "mb_diag_set_walk: direction 0 or 1");
+  g_walk_reverse = reverse;
+  return 0;
+}
+int mb_walk_tile(int vb, int ntiles, int reverse) { return vb < 0 || vb >= ntiles ? -1 : mb::walk_tile(vb, ntiles, reverse ? 1 : 0); }
+int mb_walk_seq(int slot, int n, int grp, int reverse) { return slot < 0 || slot >= n || grp < 1 ? -1 : mb::walk_seq(slot, n, grp, reverse ? 1 : 0); }
+int mb_walk_row(int slot, int rows, int seq_rows, int pair, int reverse) {
+  return slot < 0 || slot >= rows ? -1 : mb::walk_row(slot, rows, mb::walk_rows(rows, seq_rows, pair != 0, reverse));
+}
+int mb_walk_group(int seq_rows, int pair) { return seq_rows < 2 ? -1 : mb::walk_group(seq_rows, pair != 0); }
 int mb_gemm_ht_supported(int epi, int M, int N, int K) {
   mb::GemmArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, K, 0};
   return mb::gemm_ht_supported((mb::GemmEpi)epi, a) ? 1 : 0;
@@ -128,6 +144,18 @@ int mb_gemm_mini_seq(int epi, const void* A, const void* W, const float* bias, c
   a.out4l = (uint8_t*)out4l; a.out4l_scale = (uint8_t*)out4l_scale;
   if ((!seq_rows && a.M % 257) || !mb::gemm_ht_supported((mb::GemmEpi)epi, a)) return fail(-3, "mb_gemm_mini: shape not supported by the sequence-aligned tiles");
   return run_gemm(stream, epi, a, 257, "mb_gemm_mini");
+}
+int mb_gemm_mini_ln(const void* A, const void* W, const float* bias, float* y, const float* ln_stats, const float* ln_g, const float* ln_b, int rows, int pair,
+                    int seq_rows, int N, int K, int nlo, const void* const* lo, mb_stream stream) {
+  if (!A || !W || !bias || !y || !ln_stats || !ln_g || !ln_b || rows <= 0 || K <= 0 || K % 64 || nlo < 0 || nlo > 2 || (nlo && !lo))
+    return fail(-1, "mb_gemm_mini_ln: bad arguments");
+  mb::GemmArgs a{(const h16*)A, (const h16*)W, bias, y, y, nullptr, pair ? 2 * rows : rows, N, K, 0, nullptr, ln_stats, ln_g, ln_b};
+  if (pair) a.pair_rows = rows;
+  a.seq_rows = seq_rows;
+  a.nlo = nlo;
+  for (int i = 0; i < nlo; ++i) a.lo[i] = {(const uint8_t*)lo[4 * i], (const uint8_t*)lo[4 * i + 1], (const uint8_t*)lo[4 * i + 2], (const uint8_t*)lo[4 * i + 3]};
+  if ((!seq_rows && a.M % 257) || !mb::gemm_ht_supported(mb::EPI_RES_F32, a)) return fail(-3, "mb_gemm_mini_ln: shape not supported by the sequence-aligned tiles");
+  return run_gemm(stream, mb::EPI_RES_F32, a, 257, "mb_gemm_mini_ln");
 }
 int mb_gemm_mini_split(int epi, const void* A_hi, const void* A_lo, const void* W, const float* bias, void* out_h16, void* out4, void* out4_scale,
                        int rows, int N, int kw, const void* const* lo /* {A4, a_scale, W4, w_scale} */, mb_stream stream) {
@@ -177,7 +205,7 @@ int mb_w4lo_from_f32(const float* W, int N, int K, void* dst4, void* scale_out, 
 int mb_layernorm(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x_lo, float* stats, int M,
                  int d, mb_stream stream) {
   if (!y || !gamma || !beta || M <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_layernorm: bad arguments");
-  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, stats, M, d, (h16*)x_lo);
+  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, stats, M, d, (h16*)x_lo, mb::Fp4Rows{}, g_walk_reverse, 0);
   return launched();
 }
 int mb_layernorm_f4_seq(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
@@ -185,7 +213,7 @@ int mb_layernorm_f4_seq(const float* y, const float* gamma, const float* beta, f
   if (!y || !gamma || !beta || (!x4 && !xl4) || M <= 0) return fail(-1, "mb_layernorm_f4: bad arguments (an e2m1 output is required)");
   mb::Fp4Rows f4;
   if (int rc = f4_rows("mb_layernorm_f4", f4, x4, x4_scale, xl4, xl4_scale, M, d, seq_rows)) return rc;
-  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4);
+  mb::layernorm_rows((hipStream_t)stream, y, gamma, beta, eps, x_f32, (h16*)x_h16, nullptr, M, d, nullptr, f4, g_walk_reverse, seq_rows);
   return launched();
 }
 int mb_layernorm_f4(const float* y, const float* gamma, const float* beta, float eps, float* x_f32, void* x_h16, void* x4, void* x4_scale, void* xl4,
@@ -199,7 +227,7 @@ int mb_layernorm_pair(const float* y, const float* gamma, const float* beta, flo
   if (!y || !gamma || !beta || !x_h16 || P <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_layernorm_pair: bad arguments");
   mb::Fp4Rows f4;
   if (int rc = f4_rows("mb_layernorm_pair", f4, x4, x4_scale, xl4, xl4_scale, P, d, seq_rows)) return rc;
-  if (mb::layernorm_pair((hipStream_t)stream, y, gamma, beta, eps, (h16*)x_h16, stats, P, d, f4))
+  if (mb::layernorm_pair((hipStream_t)stream, y, gamma, beta, eps, (h16*)x_h16, stats, P, d, f4, g_walk_reverse, seq_rows))
     return fail(-3, "mb_layernorm_pair: width %d is outside the pair kernels (768 or 1024)", d);
   return launched();
 }
@@ -207,7 +235,7 @@ int mb_pairify(const float* x_f32, void* x_h16, void* x4, void* x4_scale, void* 
   if (!x_f32 || !x_h16 || P <= 0 || d <= 0 || d > 2048) return fail(-1, "mb_pairify: bad arguments");
   mb::Fp4Rows f4;
   if (int rc = f4_rows("mb_pairify", f4, x4, x4_scale, xl4, xl4_scale, P, d, seq_rows)) return rc;
-  if (mb::pairify_rows((hipStream_t)stream, x_f32, (h16*)x_h16, P, d, f4))
+  if (mb::pairify_rows((hipStream_t)stream, x_f32, (h16*)x_h16, P, d, f4, g_walk_reverse, seq_rows))
     return fail(-3, "mb_pairify: width %d is outside the pair kernels (768 or 1024)", d);
   return launched();
 }
@@ -247,7 +275,7 @@ int mb_attention(const void* qkv, void* out_h16, void* out4, void* out4_scale, i
   if (!qkv || !out_h16 || (!out4) != (!out4_scale) || nb <= 0 || N <= 0 || d <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention: bad arguments");
   if (d / heads != 32 && d / heads != 64) return fail(-3, "mb_attention: head width %d is outside the attention kernels (32 or 64)", d / heads);
   ProfScope p("attention", (hipStream_t)stream);
-  mb::attention((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, nb, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale);
+  mb::attention((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, nb, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale, g_walk_reverse);
   return launched();
 }
 int mb_attention_probs(const void* qkv, float* out_f32, int nb, int N, int d, int heads, mb_stream stream) {
@@ -259,14 +287,14 @@ int mb_attention_probs(const void* qkv, float* out_f32, int nb, int N, int d, in
 int mb_attention_pair(const void* qkv, void* out_h16, int pairs, int N, int d, int heads, mb_stream stream) {
   if (!qkv || !out_h16 || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair: bad arguments");
   ProfScope p("attention", (hipStream_t)stream);
-  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, nullptr, nullptr))
+  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, nullptr, nullptr, nullptr, nullptr, g_walk_reverse))
     return fail(-3, "mb_attention_pair: head width %d (N = %d tokens) is outside the attention kernels", d / heads, N);
   return launched();
 }
 int mb_attention_pair_f4(const void* qkv, void* out_h16, void* out4, void* out4_scale, void* out4l, void* out4l_scale, int pairs, int N, int d, int heads, mb_stream stream) {
   if (!qkv || !out_h16 || !out4 || !out4_scale || (!out4l) != (!out4l_scale) || pairs <= 0 || N <= 0 || heads <= 0 || d % heads) return fail(-1, "mb_attention_pair_f4: bad arguments");
   ProfScope p("attention", (hipStream_t)stream);
-  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale, (uint8_t*)out4l, (uint8_t*)out4l_scale))
+  if (mb::attention_pair((hipStream_t)stream, (const h16*)qkv, (h16*)out_h16, pairs, N, d, heads, (uint8_t*)out4, (uint8_t*)out4_scale, (uint8_t*)out4l, (uint8_t*)out4l_scale, g_walk_reverse))
     return fail(-3, "mb_attention_pair_f4: head width %d / N = %d tokens: no e2m1 copy for this shape", d / heads, N);
   return launched();
 }

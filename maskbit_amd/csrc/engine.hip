@@ -83,6 +83,9 @@ struct mb_gen {
   //   out-proj + FFN-up + FFN-down 241 / 115 / 203 at 33.4;  all four 228 / 116 / 200 at 34.3 -- the QKV set buys nothing (as round 5 found for precision 3).
   // precision 3 = out-proj + FFN-up of every layer (6); precision 4 = + FFN-down (14).  mb_gen_set_alo (diagnostic) narrows within what the handle was created with.
   int alo_mask = 0, alo_mask_built = 0;
+  // Walk order of the trunk launches (mb_kernels.h walk_tile / walk_seq): 1 = every launch of a forward walks the batch opposite to the launch in front of
+  // it, so that it starts on what its producer wrote last (the product); 0 = every launch front to back (mb_gen_set_walk, diagnostic: the A/B of the two)
+  int walk = 1;
   int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
   uint8_t* drop_cfg = nullptr;
   float* logits = nullptr;
@@ -130,6 +133,9 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     return attn ? attention_probs(s, g->qkv, attn + (size_t)l * nb * N * N, nb, N, d, c.heads) : 0;
   };
   int attn_rc = 0, gemm_rc = 0;
+  // the direction bit of this forward (mb_gen::walk): the embedding starts the chain front to back, every trunk launch after it takes the bit and flips it
+  int wdir = 0;
+  auto walk_next = [&] { wdir ^= g->walk; return wdir; };
   // The plain forward (mb_gen_forward, sampling without guidance, the zero-scale steps of a guided run), by precision:
   //   >= 1: the LayerNorm output enters FFN-UP as an fp16 hi + lo pair (x_h16 + x_lo: that GEMM sweeps its weight twice, K = 2d).  Rounds 3-4 did the
   //         same in QKV; over configs[1]'s three reference runs + the trained-like one (348 160 positions) the QKV sweep buys nothing -- 153 mismatches
@@ -164,6 +170,7 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     if (wm && epi == EPI_GELU_H16) { ga.out4 = g->h4.v; ga.out4_scale = g->h4.s; }
     if (((widx & 3) == 2 || xlo_all) && xlo_layer(widx >> 2)) { ga.K = 2 * d; ga.A2 = g->x_lo; ga.kw = d; }   // FFN-up only with the correction (see above)
     ga.sat = g->sat;
+    ga.reverse = walk_next();
     gemm_rc |= gemm_tn(s, epi, ga, wm ? 257 : 0);
   };
   // out-proj / FFN-down: + residual (prev: the LayerNorm whose output is the residual, re-derived from the row statistics; null: the buffer's own rows)
@@ -172,6 +179,7 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     if (ln_g) { ga.ln_stats = g->ln_stats; ga.ln_g = ln_g; ga.ln_b = ln_b; }
     if (wm) ga.seq_rows = N;
     lo_set(ga, a4, a4s, widx);
+    ga.reverse = walk_next();
     gemm_rc |= gemm_tn(s, EPI_RES_F32, ga, wm ? 257 : 0);
   };
   {
@@ -188,23 +196,23 @@ int gen_forward_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
     // fp16 GEMM operand and {mean, rstd}, the next residual GEMM re-derives the normalised rows in its epilogue and updates y_f32 in place (layer 0's
     // first residual is the embedding LayerNorm output, stored as is by embed_ln).  use_prenorm (bert.py:49-59, 106-123): x = x + Attn(LN(x));
     // x = x + FFN(LN(x)): the buffer holds x itself, every LayerNorm only produces the GEMM operand, the residual GEMMs add the buffer's own rows.
-    if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, L.ln1g, L.ln1b, 1e-12f, nullptr, g->x_h16, nullptr, M, d, xlo_qkv, f4x); }
+    if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, L.ln1g, L.ln1b, 1e-12f, nullptr, g->x_h16, nullptr, M, d, xlo_qkv, f4x, walk_next(), N); }
     { ProfScope p("gemm_qkv", s, true); xgemm(EPI_H16, L.wqkv, L.bqkv, g->qkv, 3 * d, 4 * l); }
-    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wm ? g->att4.v : nullptr, wm ? g->att4.s : nullptr); }
+    { ProfScope p("attention", s, true); attention(s, g->qkv, g->att, nb, N, d, c.heads, wm ? g->att4.v : nullptr, wm ? g->att4.s : nullptr, walk_next()); }
     attn_rc |= attn_maps(l);
     { ProfScope p("gemm_attn_out", s, true);
       const bool re = !c.prenorm && l > 0;
       rgemm(g->att, L.wo, L.bo, d, 4 * l + 1, g->att4.v, g->att4.s, re ? g->layers[l - 1].ln2g : nullptr, re ? g->layers[l - 1].ln2b : nullptr); }
     { ProfScope p("layernorm", s, true);
-      layernorm_rows(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, nullptr, g->x_h16, c.prenorm ? nullptr : g->ln_stats, M, d, xlo_layer(l) ? xlo_ffn : nullptr, f4x); }
+      layernorm_rows(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, nullptr, g->x_h16, c.prenorm ? nullptr : g->ln_stats, M, d, xlo_layer(l) ? xlo_ffn : nullptr, f4x, walk_next(), N); }
     { ProfScope p("gemm_ffn_up", s, true); xgemm(EPI_GELU_H16, L.w1, L.b1, g->h, f, 4 * l + 2); }
     { ProfScope p("gemm_ffn_down", s, true);
       rgemm(g->h, L.w2, L.b2, f, 4 * l + 3, g->h4.v, g->h4.s, c.prenorm ? nullptr : L.ln1g, c.prenorm ? nullptr : L.ln1b); }
     if (!c.prenorm) { ProfScope p("layernorm", s, true);
       const bool last = l + 1 == c.depth;                  // the last one feeds the head: plain hi + lo rows
-      layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, last ? g->x_lo : xlo_qkv, last ? Fp4Rows{} : f4x); }
+      layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, last ? g->x_lo : xlo_qkv, last ? Fp4Rows{} : f4x, walk_next(), N); }
   }
-  if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo); }   // norm_after_transformer
+  if (c.prenorm) { ProfScope p("layernorm", s, true); layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo, Fp4Rows{}, walk_next(), N); }   // norm_after_transformer
   gemm_rc |= head_gemms(g, logits, M, s);
   if (int rc = launched()) return rc;
   if (attn_rc) return fail(-3, "attention maps: head dim %d / %d tokens not supported", d / c.heads, N);
@@ -223,6 +231,8 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
   const mb_gen_cfg& c = g->c;
   const int d = c.hidden, f = c.mlp, N = g->N, nb = 2 * B, M = nb * N, P = B * N;
   int rc = 0;
+  int wdir = 0;                                         // the direction bit of this forward: see gen_forward_impl
+  auto walk_next = [&] { wdir ^= g->walk; return wdir; };
   // measured (profiles/r03_parity.md): the correction pass in layers >= depth / 2 alone buys about 60 % of the gain on the 12-bit runs for half of
   // the cost and next to nothing on the 14-bit one (and per GEMM type no subset is a cheaper "precise": section 5 there) -- so it runs on every GEMM
   // of every layer
@@ -256,6 +266,7 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
       ga.nlo = lo; ga.lo[0] = {a4, a4s, g->w4lo[widx], g->w4los[widx]};
       if (lo == 2) ga.lo[1] = {al4, al4s, g->w4[widx], g->w4s[widx]};
     }
+    ga.reverse = walk_next();                           // (every pgemm is launched where it is built)
     return ga;
   };
   {
@@ -267,13 +278,13 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     if (embed_pair(s, e)) {         // shapes the fused kernel does not serve: the two-kernel path
       e.drop = drop; e.nb = nb; e.f4 = Fp4Rows{};
       embed_ln(s, e);
-      rc |= pairify_rows(s, g->y_f32, g->x_h16, P, d, f4_for());        // y_f32 holds the embedding LayerNorm's fp32 rows here
+      rc |= pairify_rows(s, g->y_f32, g->x_h16, P, d, f4_for(), walk_next(), N);        // y_f32 holds the embedding LayerNorm's fp32 rows here
     }
   }
   // pre-norm: the first sub-layer normalises the embedding rows again (LayerNorm 1 of layer 0); post-norm: the embedding's own pair operands feed QKV
   if (c.prenorm && c.depth > 0) {
     ProfScope p("layernorm", s, true);
-    rc |= layernorm_pair(s, g->y_f32, g->layers[0].ln1g, g->layers[0].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for());
+    rc |= layernorm_pair(s, g->y_f32, g->layers[0].ln1g, g->layers[0].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for(), walk_next(), N);
   }
   for (int l = 0; l < c.depth; ++l) {
     const mb_gen::Layer& L = g->layers[l];
@@ -283,7 +294,7 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
       rc |= gemm_tn(s, EPI_H16, ga, 257); }
     const bool lo_o = alo_on(1), lo_h = alo_on(3);      // the producers also write the lo halves' e2m1 copies for a consumer that carries the set
     { ProfScope p("attention", s, true); rc |= attention_pair(s, g->qkv, g->att, B, N, d, c.heads, wmode ? g->att4.v : nullptr, wmode ? g->att4.s : nullptr,
-                                                              lo_o ? g->attl4.v : nullptr, lo_o ? g->attl4.s : nullptr); }
+                                                              lo_o ? g->attl4.v : nullptr, lo_o ? g->attl4.s : nullptr, walk_next()); }
     { ProfScope p("gemm_attn_out", s, true);
       GemmArgs ga = pgemm(EPI_RES_F32, g->att, L.wo, L.bo, nullptr, g->y_f32, d, d, 4 * l + 1, wmode ? (alo_on(1) ? 2 : 1) : 0, g->att4.v, g->att4.s, g->attl4.v, g->attl4.s);
       if (l > 0 && !c.prenorm) { ga.ln_stats = g->ln_stats; ga.ln_g = g->layers[l - 1].ln2g; ga.ln_b = g->layers[l - 1].ln2b; }
@@ -291,7 +302,7 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
     // post-norm: LayerNorm 1 follows the attention block; pre-norm: LayerNorm 2 precedes the FFN (same place in the launch order, other parameters;
     // the stream buffer then holds the raw residual and no GEMM re-derives a LayerNorm from the statistics)
     { ProfScope p("layernorm", s, true);
-      rc |= layernorm_pair(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, g->x_h16, c.prenorm ? nullptr : g->ln_stats, P, d, f4_for(true)); }
+      rc |= layernorm_pair(s, g->y_f32, c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b, 1e-12f, g->x_h16, c.prenorm ? nullptr : g->ln_stats, P, d, f4_for(true), walk_next(), N); }
     { ProfScope p("gemm_ffn_up", s, true);
       GemmArgs ga = pgemm(EPI_GELU_H16, g->x_h16, L.w1, L.b1, g->h, nullptr, f, d, 4 * l + 2, xlo_mode, g->x4.v, g->x4.s, g->xl4.v, g->xl4.s);
       if (wmode) { ga.out4 = g->h4.v; ga.out4_scale = g->h4.s; }
@@ -303,11 +314,11 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
       rc |= gemm_tn(s, EPI_RES_F32, ga, 257); }
     { ProfScope p("layernorm", s, true);
       if (c.prenorm) {            // the next layer's LayerNorm 1 (bert.py:49-59, 106-123), or norm_after_transformer in front of the head
-        if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo);
-        else rc |= layernorm_pair(s, g->y_f32, g->layers[l + 1].ln1g, g->layers[l + 1].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for());
+        if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, g->lnag, g->lnab, 1e-12f, nullptr, g->x_h16, nullptr, M, d, g->x_lo, Fp4Rows{}, walk_next(), N);
+        else rc |= layernorm_pair(s, g->y_f32, g->layers[l + 1].ln1g, g->layers[l + 1].ln1b, 1e-12f, g->x_h16, nullptr, P, d, f4_for(), walk_next(), N);
       }
-      else if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, g->x_lo);   // feeds the head: plain hi (+ lo) rows
-      else rc |= layernorm_pair(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, g->x_h16, g->ln_stats, P, d, f4_for()); }
+      else if (l + 1 == c.depth) layernorm_rows(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, nullptr, g->x_h16, g->ln_stats, M, d, g->x_lo, Fp4Rows{}, walk_next(), N);   // feeds the head: plain hi (+ lo) rows
+      else rc |= layernorm_pair(s, g->y_f32, L.ln2g, L.ln2b, 1e-12f, g->x_h16, g->ln_stats, P, d, f4_for(), walk_next(), N); }
   }
   rc |= head_gemms(g, logits, M, s);
   if (int lrc = launched()) return lrc;
@@ -567,6 +578,12 @@ int mb_gen_set_alo(mb_gen* g, int gemm_mask) {
   if (gemm_mask & ~g->alo_mask_built)
     return fail(-1, "mb_gen_set_alo: the handle was created (precision %d) with the activation-lo operands of GEMM mask %d only", g->c.precision, g->alo_mask_built);
   g->alo_mask = gemm_mask;
+  return 0;
+}
+
+int mb_gen_set_walk(mb_gen* g, int mode) {
+  if (!g || (mode != 0 && mode != 1)) return fail(-1, "mb_gen_set_walk: mode 0 (every launch front to back) or 1 (alternating)");
+  g->walk = mode;
   return 0;
 }
 

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs a) {
   const int wm = wave >> 1, wn = wave & 1;
   const int tiles_n = (a.N + BN - 1) / BN;
   const int tiles_m = (a.M + BM - 1) / BM;
-  const int L = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+  const int L = walk_tile(blockIdx.x, tiles_m * tiles_n, a.reverse);
   const int m0 = (L / tiles_n) * BM, n0 = (L % tiles_n) * BN;
   const int K = a.K, KA = a.kw ? a.kw : a.K, nka = KA / BK;
   const int KW = a.kw ? a.kw : a.K, nkw = KW / BK;   // split activations: W has kw columns and is swept twice, A2 takes over from A

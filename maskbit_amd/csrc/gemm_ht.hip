@@ -140,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ht_kernel(GemmArgs a, int tiles_m
   auto make_plan = [&](int vb, Plan& p) {
     int lane_o = lane;                                 // opaque copy: keeps the plan's lane arithmetic from being hoisted
     asm volatile("" : "+v"(lane_o));                   // out of the tile loop and held in VGPRs across the K loop
-    const int L = xcd_remap(vb, ntiles);              // XCD-contiguous chunks; inside, 8 x tiles_n super-rows
+    const int L = walk_tile(vb, ntiles, a.reverse);   // XCD-contiguous chunks; inside, 8 x tiles_n super-rows (a.reverse: the mirrored walk, mb_kernels.h)
     const int sr = L / (8 * tiles_n);
     const int rows_sr = min(8, tiles_m - sr * 8);
     const int rem = L - sr * 8 * tiles_n;

@@ -150,7 +150,7 @@ __device__ __forceinline__ float ln_affine(float v, float mean, float rstd, floa
 
 // XCD-aware bijective remap: hardware places block b on XCD b%8; give every XCD a contiguous
 // chunk of the logical tile list so neighbouring tiles (sharing an operand panel) share an L2.
-__device__ __forceinline__ int xcd_remap(int b, int nblk) {
+__host__ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
   const int q = nblk >> 3, r = nblk & 7, x = b & 7, i = b >> 3;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }

@@ -71,6 +71,9 @@ struct GemmArgs {
   int nlo = 0;
   // fp16 epilogues (optional): lanes that stored a value outside fp16's range (or a NaN) add 1 to *sat (mb_gen_saturation_count)
   unsigned* sat = nullptr;
+  // walk order (walk_tile below): 0 = the tile list front to back, 1 = back to front.  The same tiles with the same contents either way; the engine
+  // alternates it along the launch chain so that a kernel starts on the rows its producer wrote last.
+  int reverse = 0;
 };
 // Byte offset of element (row n, K-element k) of an e2m1 WEIGHT operand of the mini-tile passes.  The operand is stored MINI-TILE-PACKED:
 // [N / 16][K / 128] chunks of 1 KiB = 16 rows x 64 B, the 16-byte pieces of a row swizzled with (row >> 1) & 3 -- the LDS image of one DMA
@@ -91,6 +94,52 @@ __host__ __device__ inline size_t w4_scale_index(int n, int j, int K) {
 __host__ __device__ inline size_t fp4_scale_index(int blk, int nseq, int seq, int r, int groups = 4) {
   return (((size_t)blk * nseq + seq) * groups + (r >> 6)) * 64 + (r & 15) * 4 + ((r >> 4) & 3);
 }
+// ---- walk order: which sequence (pair) a trunk launch visits when -------------------------------------------------------------------------------
+// A consumer that streams a hand-off larger than the 256 MiB Infinity Cache in its producer's direction asks first for the bytes written longest ago,
+// which are gone.  Each launch therefore takes a direction (`reverse`, 0 or 1) and the engine alternates it along the launch chain: a kernel starts
+// with the sequences its producer touched LAST.  Direction 1 is the exact mirror in time of direction 0 -- the same tiles, workgroups and rows,
+// visited in the opposite order; no arithmetic changes.  (Measured, profiles/walk_order.md: at 64 pairs the hand-off that large is FFN-up's output,
+// and FFN-down is where the time is won; the others fit the cache in either direction.)
+//
+// The persistent GEMM walk (gemm_ht.hip): virtual block vb -> logical tile; direction 0 is the XCD-contiguous map the kernel always had.
+__host__ __device__ inline int walk_tile(int vb, int ntiles, int reverse) { return xcd_remap(reverse ? ntiles - 1 - vb : vb, ntiles); }
+__host__ __device__ inline int xcd_chunk_start(int x, int n) { return xcd_remap(x, n); }   // first item of XCD x's chunk (x < 8)
+// The grid kernels (attention: workgroup = (sequence, head); LayerNorm: rows of a sequence): slot s of n sequences (pairs) -> the sequence visited s-th.
+// A GEMM walk is eight sawteeth, not one ramp: XCD x owns the contiguous sequences [xcd_chunk_start(x, n), xcd_chunk_start(x + 1, n)) and walks them in
+// super-rows of `grp` sequences (8 m-tiles), all eight XCDs in step.  Direction 0 lists the sequences in the order such a direction-0 walk completes them
+// (super-row t of every chunk before super-row t + 1 of any), direction 1 is its mirror: the sequences a direction-0 GEMM wrote last come first.
+__host__ __device__ inline int walk_seq(int slot, int n, int grp, int reverse) {
+  if (reverse) slot = n - 1 - slot;
+  const int q = n >> 3, r = n & 7;
+  for (int lo = 0, before = 0;; lo += grp) {
+    const int a = q + 1 - lo < grp ? (q + 1 - lo > 0 ? q + 1 - lo : 0) : grp;   // sequences of this super-row in a long chunk (the first r) ..
+    const int b = q - lo < grp ? (q - lo > 0 ? q - lo : 0) : grp;               // .. and in a short one
+    const int step = r * a + (8 - r) * b;
+    if (slot < before + step) {
+      int s = slot - before, x;
+      if (s < r * a) { x = s / a; s -= x * a; }
+      else { s -= r * a; x = s / b; s -= x * b; x += r; }
+      return xcd_chunk_start(x, n) + lo + s;
+    }
+    before += step;
+  }
+}
+// sequences (pairs) per super-row of the GEMM walk: 8 m-tiles of 128 tokens of a pair / 256 tokens of a plain sequence
+inline int walk_group(int seq_rows, bool pair) { const int tps = (seq_rows - 1) / (pair ? 128 : 256); return tps >= 8 ? 1 : tps >= 1 ? 8 / tps : 8; }
+// The row kernels (one wave per row or row pair): slot s of `rows` rows = whole sequences of seq_rows -> the row visited s-th.  The sequences follow
+// walk_seq, a sequence's rows keep their order (and are mirrored with everything else in direction 1).
+struct WalkRows { int seq_rows, grp, reverse; };
+__host__ __device__ inline int walk_row(int slot, int rows, const WalkRows& w) {
+  if (w.reverse) slot = rows - 1 - slot;
+  const int ss = slot / w.seq_rows;
+  return walk_seq(ss, rows / w.seq_rows, w.grp, 0) * w.seq_rows + (slot - ss * w.seq_rows);
+}
+// (rows that are not whole sequences of seq_rows, or seq_rows = 0: one run of rows, front to back or back to front)
+inline WalkRows walk_rows(int rows, int seq_rows, bool pair, int reverse) {
+  if (seq_rows <= 0 || rows % seq_rows) return WalkRows{rows, 8, reverse ? 1 : 0};
+  return WalkRows{seq_rows, walk_group(seq_rows, pair), reverse ? 1 : 0};
+}
+
 int gemm_tn(hipStream_t s, GemmEpi epi, const GemmArgs& a, int variant = 0);   // 0, or -1: lo-pass request outside the half-tile kernel's shapes
 bool gemm_ht_supported(GemmEpi epi, const GemmArgs& a);
 void gemm_ht(hipStream_t s, GemmEpi epi, const GemmArgs& a, int mt);
@@ -110,13 +159,13 @@ struct Fp4Rows { uint8_t* x4 = nullptr; uint8_t* x4s = nullptr; uint8_t* xl4 = n
 // ---- LayerNorm over rows of y[M,d] -> x_f32 (optional), x_h16 (optional), stats[M][2] = {mean, rstd} (optional) ---
 void layernorm_rows(hipStream_t s, const float* y, const float* gamma, const float* beta, float eps,
                     float* x_f32, h16* x_h16, float* stats, int M, int d, h16* x_lo = nullptr,
-                    const Fp4Rows& f4 = Fp4Rows{});   // x_lo: fp16(x - fp16(x)), optional
+                    const Fp4Rows& f4 = Fp4Rows{}, int reverse = 0, int seq_rows = 0);   // x_lo: fp16(x - fp16(x)), optional; reverse / seq_rows: the walk order (walk_row)
 
 // "CFG pair" forms (hidden = 768 / 1024 only; -1 otherwise): rows r < P are conditional, r + P their unconditional twins.  Writes
 // x_h16[r] = fp16(x_c), x_h16[r + P] = fp16(x_u - x_c), both rows' {mean, rstd}; optional f4: e2m1 copies of the CONDITIONAL rows.
 int layernorm_pair(hipStream_t s, const float* y, const float* gamma, const float* beta, float eps, h16* x_h16, float* stats, int P, int d,
-                   const Fp4Rows& f4 = Fp4Rows{});
-int pairify_rows(hipStream_t s, const float* x32, h16* x_h16, int P, int d, const Fp4Rows& f4 = Fp4Rows{});
+                   const Fp4Rows& f4 = Fp4Rows{}, int reverse = 0, int seq_rows = 0);
+int pairify_rows(hipStream_t s, const float* x32, h16* x_h16, int P, int d, const Fp4Rows& f4 = Fp4Rows{}, int reverse = 0, int seq_rows = 0);
 
 // ---- bit-token embed + class token + pos-emb + first LayerNorm (bert.py:440-454, 482-496) -------
 struct EmbedArgs {
@@ -144,7 +193,7 @@ void transpose_f32(hipStream_t s, const float* src /*[rows,cols]*/, float* dst /
 
 // ---- multi-head self-attention over packed qkv [nb*N, 3d] -> out [nb*N, d] -----------------------
 void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, int heads,
-               uint8_t* out4 = nullptr, uint8_t* out4s = nullptr);   // out4 / out4s (N = 257 or (N - 1) % 64 == 0 beyond the one-block kernel's length; head width 64): e2m1 of the outputs + lane-ordered scale
+               uint8_t* out4 = nullptr, uint8_t* out4s = nullptr, int reverse = 0);   // out4 / out4s (N = 257 or (N - 1) % 64 == 0 beyond the one-block kernel's length; head width 64): e2m1 of the outputs + lane-ordered scale
                                                                       // bytes for the out-proj GEMM's mini-tile pass
 // "CFG pair" attention: sequences [0, P) are conditional, [P, 2P) their unconditional twins; one workgroup runs a (pair, head) -- conditional pass,
 // then the twin with the conditional output tiles kept in registers -- and writes out[r + P*N] = fp16(att_u - att_c), the difference operand of the
@@ -152,7 +201,7 @@ void attention(hipStream_t s, const h16* qkv, h16* out, int nb, int N, int d, in
 // out4 / out4s (head dimension 64 only): e2m1 of the conditional output values, row stride 2d bytes, + lane-ordered E8M0 scale bytes (GemmArgs.lo)
 // out4l / out4ls (optional, with out4; precision 4): the same for the fp16 lo halves o_c - fp16(o_c) of the conditional outputs (the out-proj GEMM's activation-lo pass)
 int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d, int heads, uint8_t* out4 = nullptr, uint8_t* out4s = nullptr,
-                   uint8_t* out4l = nullptr, uint8_t* out4ls = nullptr);
+                   uint8_t* out4l = nullptr, uint8_t* out4ls = nullptr, int reverse = 0);   // reverse: the walk order (walk_seq above)
 // head-averaged attention weights [nb, N, N] fp32 of one layer (return_attn=True); -1 if the shape is not supported
 int attention_probs(hipStream_t s, const h16* qkv, float* out, int nb, int N, int d, int heads);
 

@@ -98,10 +98,11 @@ __device__ __forceinline__ void ln_finish(float4* v, const float* sc, int ns, in
 template <int NV>
 __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float eps, float* x_f32,
-                                                      h16* x_h16, float* stats, int M, int d, h16* x_lo, Fp4Rows f4) {
+                                                      h16* x_h16, float* stats, int M, int d, h16* x_lo, Fp4Rows f4, WalkRows wk) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot >= M) return;
+  const int row = walk_row(slot, M, wk);               // walk order (mb_kernels.h): which row this wave takes
   const float* yr = y + (size_t)row * d;
   constexpr bool VEC = NV > 0;
   float4 v[VEC ? NV : 1]; float sc[VEC ? 1 : MAXS];
@@ -159,10 +160,11 @@ __device__ __forceinline__ void pair_store(float4* xc, const float4* xu, int lan
 
 template <int NV>
 __global__ __launch_bounds__(256) void ln_pair_kernel(const float* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                      h16* __restrict__ x_h16, float* __restrict__ stats, int P, int d, Fp4Rows f4) {
+                                                      h16* __restrict__ x_h16, float* __restrict__ stats, int P, int d, Fp4Rows f4, WalkRows wk) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= P) return;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot >= P) return;
+  const int row = walk_row(slot, P, wk);               // walk order (mb_kernels.h): which row pair this wave takes
   float4 vc[NV], vu[NV];
 #pragma unroll
   for (int q = 0; q < NV; ++q) { vc[q] = *(const float4*)(y + (size_t)row * d + q * 256 + lane * 4); vu[q] = *(const float4*)(y + (size_t)(row + P) * d + q * 256 + lane * 4); }
@@ -173,10 +175,11 @@ __global__ __launch_bounds__(256) void ln_pair_kernel(const float* __restrict__ 
 
 // pair operands from fp32 rows that already exist (the embedding LayerNorm's output, the first residual): x32 [2P, d] -> x_h16 as above
 template <int NV>
-__global__ __launch_bounds__(256) void pairify_kernel(const float* __restrict__ x32, h16* __restrict__ x_h16, int P, int d, Fp4Rows f4) {
+__global__ __launch_bounds__(256) void pairify_kernel(const float* __restrict__ x32, h16* __restrict__ x_h16, int P, int d, Fp4Rows f4, WalkRows wk) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= P) return;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot >= P) return;
+  const int row = walk_row(slot, P, wk);
   float4 vc[NV], vu[NV];
 #pragma unroll
   for (int q = 0; q < NV; ++q) { vc[q] = *(const float4*)(x32 + (size_t)row * d + q * 256 + lane * 4); vu[q] = *(const float4*)(x32 + (size_t)(row + P) * d + q * 256 + lane * 4); }
@@ -184,27 +187,30 @@ __global__ __launch_bounds__(256) void pairify_kernel(const float* __restrict__ 
 }
 
 int layernorm_pair(hipStream_t s, const float* y, const float* gamma, const float* beta, float eps, h16* x_h16, float* stats, int P, int d,
-                   const Fp4Rows& f4) {
+                   const Fp4Rows& f4, int reverse, int seq_rows) {
   dim3 grid((P + 3) / 4), block(256);
-  if (d == 1024) hipLaunchKernelGGL(ln_pair_kernel<4>, grid, block, 0, s, y, gamma, beta, eps, x_h16, stats, P, d, f4);
-  else if (d == 768) hipLaunchKernelGGL(ln_pair_kernel<3>, grid, block, 0, s, y, gamma, beta, eps, x_h16, stats, P, d, f4);
+  const WalkRows wk = walk_rows(P, seq_rows, true, reverse);
+  if (d == 1024) hipLaunchKernelGGL(ln_pair_kernel<4>, grid, block, 0, s, y, gamma, beta, eps, x_h16, stats, P, d, f4, wk);
+  else if (d == 768) hipLaunchKernelGGL(ln_pair_kernel<3>, grid, block, 0, s, y, gamma, beta, eps, x_h16, stats, P, d, f4, wk);
   else return -1;
   return 0;
 }
-int pairify_rows(hipStream_t s, const float* x32, h16* x_h16, int P, int d, const Fp4Rows& f4) {
+int pairify_rows(hipStream_t s, const float* x32, h16* x_h16, int P, int d, const Fp4Rows& f4, int reverse, int seq_rows) {
   dim3 grid((P + 3) / 4), block(256);
-  if (d == 1024) hipLaunchKernelGGL(pairify_kernel<4>, grid, block, 0, s, x32, x_h16, P, d, f4);
-  else if (d == 768) hipLaunchKernelGGL(pairify_kernel<3>, grid, block, 0, s, x32, x_h16, P, d, f4);
+  const WalkRows wk = walk_rows(P, seq_rows, true, reverse);
+  if (d == 1024) hipLaunchKernelGGL(pairify_kernel<4>, grid, block, 0, s, x32, x_h16, P, d, f4, wk);
+  else if (d == 768) hipLaunchKernelGGL(pairify_kernel<3>, grid, block, 0, s, x32, x_h16, P, d, f4, wk);
   else return -1;
   return 0;
 }
 
 void layernorm_rows(hipStream_t s, const float* y, const float* gamma, const float* beta, float eps,
-                    float* x_f32, h16* x_h16, float* stats, int M, int d, h16* x_lo, const Fp4Rows& f4) {
+                    float* x_f32, h16* x_h16, float* stats, int M, int d, h16* x_lo, const Fp4Rows& f4, int reverse, int seq_rows) {
   dim3 grid((M + 3) / 4), block(256);      // f4 (e2m1 values / lo halves): vector path only (d = 768 / 1024; mb_gen_create restricts the modes to those)
-  if (d == 1024) hipLaunchKernelGGL(ln_rows_kernel<4>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, f4);
-  else if (d == 768) hipLaunchKernelGGL(ln_rows_kernel<3>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, f4);
-  else hipLaunchKernelGGL(ln_rows_kernel<0>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, Fp4Rows{});
+  const WalkRows wk = walk_rows(M, seq_rows, false, reverse);
+  if (d == 1024) hipLaunchKernelGGL(ln_rows_kernel<4>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, f4, wk);
+  else if (d == 768) hipLaunchKernelGGL(ln_rows_kernel<3>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, f4, wk);
+  else hipLaunchKernelGGL(ln_rows_kernel<0>, grid, block, 0, s, y, gamma, beta, eps, x_f32, x_h16, stats, M, d, x_lo, Fp4Rows{}, wk);
 }
 
 // One wave per (sequence, row).  Rows 0..seq-1 are image tokens, row seq is the class token (LAST,
