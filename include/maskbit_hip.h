@@ -22,7 +22,7 @@ extern "C" {
 #endif
 
 #define MB_ABI_VERSION 8
-enum { MB_PREC_FP16 = 0, MB_PREC_DIFF = 1, MB_PREC_WCORR = 2, MB_PREC_ALO = 3, MB_PREC_ALO_ALL = 4 };
+enum { MB_PREC_FP16 = 0, MB_PREC_DIFF = 1, MB_PREC_WCORR = 2, MB_PREC_ALO = 3, MB_PREC_ALO_ALL = 4, MB_PREC_F32 = 5 };
 
 typedef struct mb_gen mb_gen; /* generator engine  (modeling/bert.py LFQBert)            */
 typedef struct mb_dec mb_dec; /* tokenizer decoder (modeling/conv_vqgan.py ConvVQModel)  */
@@ -57,7 +57,14 @@ typedef struct {
    *   MB_PREC_ALO_ALL 4 + the FFN hiddens in FFN-down (the QKV set buys nothing in any measured configuration), and the zero-scale steps of a guided run
    *                    through the guided forward as well: what heavy-tailed ("trained-like") weights with massive-activation channels need (round 6).
    * Modes 1-4 need seq in {256, 1024}, hidden in {768, 1024}, mlp % 256 == 0 (2-4 also hidden / heads = 64); other shapes run mode 0 with hi + lo
-   * LayerNorm outputs.  The host's default is 2, 3 from 7 bits per group on, 4 for heavy-tailed checkpoints (LFQBert.resolved_precision). */
+   * LayerNorm outputs.  The host's default is 2, 3 from 7 bits per group on, 4 for heavy-tailed checkpoints (LFQBert.resolved_precision).
+   *   MB_PREC_F32   5  the fp32 REFERENCE mode (an addition; no other mode changes): no fp16 operand anywhere.  Accepted for every configuration
+   *                    mb_gen_create accepts (any seq / hidden / heads / mlp, prenorm, embed_tables).  The GEMM weights stay the checkpoint's fp32, the
+   *                    workspace is fp32, every GEMM output element is one ascending-k fmaf chain on the f32-input MFMA plus one bias add
+   *                    (maskbit_amd/csrc/gemm_f32.hip), attention and LayerNorm are fp32; the guided forward is the plain forward over
+   *                    [B cond | B dropped].  Deterministic and independent of the batch.  About 1/16 of the fp16 MFMA rate: an instrument for judging the
+   *                    other modes on a given checkpoint (maskbit_amd.check_checkpoint), never chosen by the host's auto rule.  mb_gen_forward_attn
+   *                    refuses it (-3); mb_gen_saturation_count reports 0. */
   int precision;
 } mb_gen_cfg;
 
@@ -102,7 +109,7 @@ void mb_gen_destroy(mb_gen* g);
 /* One call per checkpoint entry (key names of SURVEY.md 8b / BaseModel.load_pretrained,
  * modeling/modules/base_model.py:87-141).  `data` is a device fp32 tensor in the checkpoint's
  * own layout; GEMM weights are repacked to fp16 here (plus the e2m1 operands of the correction passes; the two head weights as fp16
- * hi + lo planes).  Unknown names return -2. */
+ * hi + lo planes; precision MB_PREC_F32: kept as fp32, no repack).  Unknown names return -2. */
 int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
 /* tokens int64 [nb,seq,m] (value C = masked), labels int64 [nb], drop uint8 [nb] (1 => label
  * replaced by nclass, bert.py:482-484; may be NULL) -> logits fp32 [nb,seq,m,C]. */

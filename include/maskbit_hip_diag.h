@@ -238,6 +238,19 @@ int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, v
 int mb_spatial_attention(const void* q, const void* k, const void* v, void* out_h16, unsigned* sat, int B, int N, int ld, int ldo, mb_stream stream);
 int mb_taming_set_tap(mb_taming* h, int block, void* out_h16);
 
+/* ---- the fp32 reference mode's kernels (gemm_f32.hip; mb_gen_cfg.precision = MB_PREC_F32), everything fp32 in device memory.
+ * mb_gemm_f32: out = epi(A[M,K] . W[N,K]^T + bias).  Every output element is acc = 0; for k = 0 .. K-1: acc = fmaf(A[m,k], W[n,k], acc) -- one chain,
+ * ascending k --, then one fp32 add of bias[n], then epi: 0 nothing, 1 gelu_erf with an accurate erff, 2 + residual[m,n] (out may alias residual),
+ * 3 logits -- row m with m % period == period - 1 is dropped, the others land in row (m / period) * (period - 1) + m % period; bias [N], or with
+ * bias_per_pos [period - 1][N], row m % period.  Any M >= 1, N >= 1, K >= 4 with K % 4 == 0; A and W 16-byte aligned.  residual is read by epi 2 only.
+ * Refusals, nothing launched: -1 a NULL required pointer or an epilogue outside 0 .. 3; -3 a shape outside the above (also: epi 3 with period < 2 or
+ * M % period, bias_per_pos outside epi 3) or a misaligned operand.
+ * mb_attention_f32: qkv fp32 [nb, N, 3d] (nn.MultiheadAttention's head split) -> out fp32 [nb, N, d] = softmax(Q K^T / sqrt(d / heads)) V per
+ * (sequence, head), fp32 throughout, keys streamed in tiles with a running max and sum.  Any N >= 1; d / heads = 32 or 64 (-3 otherwise). */
+int mb_gemm_f32(int epi, const float* A, const float* W, const float* bias, const float* residual, float* out, int M, int N, int K, int period,
+                int bias_per_pos, mb_stream stream);
+int mb_attention_f32(const float* qkv, float* out, int nb, int N, int d, int heads, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covar
 from .lpips import LPIPS
 from .inception import InceptionV3, get_inception_model
 from .editing import inpaint, sample_from_tokens
+from .checkpoint_check import CheckpointReport, check_checkpoint
 from .validation import MLMLoss, MaskedTokenEvaluator, get_mask_tokens
 from .harness import (eval_generation, eval_labels, eval_masked_prediction, eval_reconstruction, generate_uint8, mask_token_for,
                       to_evaluator_uint8)
@@ -21,4 +22,4 @@ __all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sa
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",
            "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance",
-           "InceptionV3", "get_inception_model"]
+           "InceptionV3", "get_inception_model", "check_checkpoint", "CheckpointReport"]

@@ -148,6 +148,8 @@ SIGNATURES = {
     "mb_taming_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
     "mb_taming_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mb_spatial_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "mb_gemm_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    "mb_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     "mb_set_cu_count":(C.c_int, [C.c_int]),
     "mb_gen_set_walk": (C.c_int, [C.c_void_p, C.c_int]),
     "mb_diag_set_walk": (C.c_int, [C.c_int]),

@@ -26,9 +26,11 @@ from .base_model import BaseModel, ParamSpec
 #   PREC_WCORR 2  + MX-fp4 weight-correction mini-tiles on every trunk GEMM, guided and plain (5.5e-4 over three reference runs of configs[2]; 5.3e-4 on configs[1])
 #   PREC_ALO   3  + activation-lo mini-tiles in out-proj (attention outputs) and FFN-up (LayerNorm outputs) of every layer of the guided forward (3.8e-4 over four 14-bit / 256-step runs)
 #   PREC_ALO_ALL 4 + activation-lo mini-tiles in FFN-down (FFN hiddens) as well, zero-scale steps through the guided forward: heavy-tailed checkpoints
+#   PREC_F32   5  the fp32 REFERENCE mode: fp32 weights, fp32 workspace, every GEMM an ascending-k fmaf chain on the f32-input MFMA -- any shape, about 1/16
+#                 of the fp16 rate; what check_checkpoint() measures the other modes against.  Only ever chosen explicitly.
 # -1 = auto: 2, or 3 from 7 bits per group on, or 4 when the checkpoint's statistics ask for it (weight_statistics()), degraded to what the shape allows
 # (resolved_precision()).
-PREC_AUTO, PREC_FP16, PREC_DIFF, PREC_WCORR, PREC_ALO, PREC_ALO_ALL = -1, 0, 1, 2, 3, 4
+PREC_AUTO, PREC_FP16, PREC_DIFF, PREC_WCORR, PREC_ALO, PREC_ALO_ALL, PREC_F32 = -1, 0, 1, 2, 3, 4, 5
 # Load-time escalation rule of the auto mode (round 6).  What the default modes are sensitive to, and Gaussian-like weights do not show: (a) HEAVY-TAILED
 # Linear weights -- an fp16 rounding error is +-ulp(w) / 2, so a few large weights per row set the scale of the e2m1 weight-error operand for the rest
 # (residual 9 % of the error energy at kurtosis 10.9 against 3 % at 3); measured as the pooled kurtosis of the trunk's Linear weights standardised per
@@ -164,6 +166,8 @@ class LFQBert(BaseModel):
         capable = pair_capable(self.seq_len, self.hidden_dim, self.mlp_dim, self.use_prenorm)
         mini = mini_capable(self.seq_len, self.hidden_dim, self.mlp_dim, self.heads)
         prec = int(self.precision)
+        if prec == PREC_F32:
+            return prec                                            # the fp32 reference mode serves every shape: no fallback touches it
         if prec < 0:
             prec = PREC_ALO if self.bits // self.splits >= 7 else PREC_WCORR
             if capable and mini and self.weight_statistics()["heavy_tailed"]:

@@ -445,4 +445,23 @@ int mb_spatial_attention(const void* q, const void* k, const void* v, void* out_
 }
 int mb_maxpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_maxpool2", mb::launch_maxpool2, x_h16, y_h16, B, H, W, C, stream); }
 
+// ---- the fp32 reference mode's two kernels on caller buffers (tests/test_hip_gemm_f32.py, test_hip_attention_f32.py) ----
+int mb_gemm_f32(int epi, const float* A, const float* W, const float* bias, const float* residual, float* out, int M, int N, int K, int period,
+                int bias_per_pos, mb_stream stream) {
+  if (!A || !W || !bias || !out || epi < 0 || epi > 3 || (epi == mb::F32_EPI_RES && !residual)) return fail(-1, "mb_gemm_f32: bad arguments");
+  mb::GemmF32Args a{epi, A, W, bias, residual, out, M, N, K, period, bias_per_pos};
+  ProfScope p("gemm_f32_diag", (hipStream_t)stream);
+  if (mb::gemm_f32((hipStream_t)stream, a))
+    return fail(-3, "mb_gemm_f32: M=%d N=%d K=%d (period %d) is outside the kernel's shapes: M, N >= 1, K >= 4 and K %% 4 == 0, 16-byte aligned A and W, "
+                    "logits rows in whole periods", M, N, K, period);
+  return launched();
+}
+int mb_attention_f32(const float* qkv, float* out, int nb, int N, int d, int heads, mb_stream stream) {
+  if (!qkv || !out) return fail(-1, "mb_attention_f32: null argument");
+  ProfScope p("attention_f32_diag", (hipStream_t)stream);
+  if (mb::attention_f32((hipStream_t)stream, qkv, out, nb, N, d, heads))
+    return fail(-3, "mb_attention_f32: nb=%d N=%d d=%d heads=%d is outside the kernel's shapes (d / heads = 32 or 64)", nb, N, d, heads);
+  return launched();
+}
+
 }  // extern "C"

@@ -86,6 +86,14 @@ struct mb_gen {
   // Walk order of the trunk launches (mb_kernels.h walk_tile / walk_seq): 1 = every launch of a forward walks the batch opposite to the launch in front of
   // it, so that it starts on what its producer wrote last (the product); 0 = every launch front to back (mb_gen_set_walk, diagnostic: the A/B of the two)
   int walk = 1;
+  // precision MB_PREC_F32, the fp32 reference mode (gemm_f32.hip): the GEMM weights stay the checkpoint's fp32 (layers32, wl32, wp32 -- Bert's tied
+  // head: the tables' first C rows per group), the workspace is fp32 only -- x_f32 = the LayerNorm output rows (GEMM operand AND residual), y_f32 = the
+  // pre-LayerNorm sum, qkv32 / att32 / h32 -- and none of the fp16 / e2m1 buffers above exist.  Every forward of such a handle is gen_forward_f32_impl.
+  bool f32 = false;
+  struct Layer32 { float *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr; };
+  std::vector<Layer32> layers32;
+  float *wl32 = nullptr, *wp32 = nullptr;
+  float *x_f32 = nullptr, *qkv32 = nullptr, *att32 = nullptr, *h32 = nullptr;
   int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
   uint8_t* drop_cfg = nullptr;
   float* logits = nullptr;
@@ -326,18 +334,73 @@ int gen_forward_pair_impl(mb_gen* g, const int64_t* tokens, const int64_t* label
   return 0;
 }
 
+// The fp32 reference forward (precision MB_PREC_F32): the straight chain embed -> depth x (QKV, attention, out-proj + residual, LayerNorm, FFN-up + GELU,
+// FFN-down + residual, LayerNorm) -> head, every operand, product and sum in fp32 (gemm_f32.hip: each GEMM output is one ascending-k fmaf chain).
+// Post-norm: x_f32 holds the LayerNorm output -- the next GEMM's operand and the residual that GEMM's successor adds --, y_f32 the pre-LayerNorm sum.
+// Pre-norm: y_f32 holds the stream x itself (the residual GEMMs add in place), x_f32 the LayerNorm output that feeds a GEMM.
+int gen_forward_f32_impl(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, int nb, hipStream_t s) {
+  using namespace mb;
+  const mb_gen_cfg& c = g->c;
+  const int d = c.hidden, f = c.mlp, N = g->N, M = nb * N;
+  int rc = 0;
+  auto gemm = [&](int epi, const float* A, const float* W, const float* bias, const float* res, float* out, int Nout, int K) {
+    GemmF32Args ga{epi, A, W, bias, res, out, M, Nout, K};
+    rc |= gemm_f32(s, ga);
+  };
+  auto ln = [&](const float* gamma, const float* beta) {
+    ProfScope p("layernorm", s, true);
+    layernorm_rows(s, g->y_f32, gamma, beta, 1e-12f, g->x_f32, nullptr, nullptr, M, d);
+  };
+  float* const stream = c.prenorm ? g->y_f32 : g->x_f32;     // what the residual GEMMs add
+  {
+    ProfScope p("embed_ln", s, true);
+    EmbedArgs e{tokens, labels, drop, g->w_in, g->b_in, g->class_emb, g->pos, g->ln0g, g->ln0b,
+                stream, nullptr, nb, c.seq, c.splits, g->gbits, d, c.nclass, g->tables};
+    embed_ln(s, e);
+  }
+  for (int l = 0; l < c.depth; ++l) {
+    const mb_gen::Layer& L = g->layers[l];
+    const mb_gen::Layer32& W = g->layers32[l];
+    if (c.prenorm) ln(L.ln1g, L.ln1b);
+    { ProfScope p("gemm_qkv", s, true); gemm(F32_EPI_PLAIN, g->x_f32, W.wqkv, L.bqkv, nullptr, g->qkv32, 3 * d, d); }
+    { ProfScope p("attention", s, true); rc |= attention_f32(s, g->qkv32, g->att32, nb, N, d, c.heads); }
+    { ProfScope p("gemm_attn_out", s, true); gemm(F32_EPI_RES, g->att32, W.wo, L.bo, stream, g->y_f32, d, d); }
+    ln(c.prenorm ? L.ln2g : L.ln1g, c.prenorm ? L.ln2b : L.ln1b);
+    { ProfScope p("gemm_ffn_up", s, true); gemm(F32_EPI_GELU, g->x_f32, W.w1, L.b1, nullptr, g->h32, f, d); }
+    { ProfScope p("gemm_ffn_down", s, true); gemm(F32_EPI_RES, g->h32, W.w2, L.b2, stream, g->y_f32, d, f); }
+    if (!c.prenorm) ln(L.ln2g, L.ln2b);
+  }
+  if (c.prenorm) ln(g->lnag, g->lnab);                       // norm_after_transformer
+  // the head (bert.py:411-417, 500-503): last_layer.0 + GELU, LayerNorm, prediction layer
+  { ProfScope p("gemm_head", s, true); gemm(F32_EPI_GELU, g->x_f32, g->wl32, g->bl, nullptr, g->y_f32, d, d); }
+  ln(g->lnhg, g->lnhb);
+  { ProfScope p("gemm_head", s, true);
+    GemmF32Args ga{F32_EPI_LOGITS, g->x_f32, g->wp32, c.embed_tables ? g->bias_pos : g->bp, nullptr, logits, M, c.splits * g->C, d, N, c.embed_tables};
+    rc |= gemm_f32(s, ga); }
+  if (int lrc = launched()) return lrc;
+  if (rc) return fail(-3, "fp32 reference forward: a kernel refused the shape (%d sequences x %d tokens, hidden %d, heads %d, mlp %d)", nb, N, d, c.heads, f);
+  return 0;
+}
+
+// One pass over nb <= chunk_seqs sequences: the fp32 reference chain at precision MB_PREC_F32 -- decided here, in front of every precision >= n test of
+// the fp16 schedules --, gen_forward_impl otherwise (attn: that schedule's attention maps; mb_gen_forward_attn refuses the fp32 mode itself)
+int gen_forward_pass(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, int nb, hipStream_t s, float* attn = nullptr) {
+  if (g->f32) return gen_forward_f32_impl(g, tokens, labels, drop, logits, nb, s);
+  return gen_forward_impl(g, tokens, labels, drop, logits, nb, s, attn);
+}
+
 // The kernels index with 32-bit element / byte offsets (rows * mlp * 4 < 2^32): forwards over more sequences than that allows run as
 // independent chunks (sequences never interact), which also bounds the workspace of very large batches.
 int gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, int nb, hipStream_t s,
                 float* attn = nullptr) {
   const int chunk = g->chunk_seqs;
   g_prof.begin_forward(true);
-  if (nb <= chunk) return gen_forward_impl(g, tokens, labels, drop, logits, nb, s, attn);
+  if (nb <= chunk) return gen_forward_pass(g, tokens, labels, drop, logits, nb, s, attn);
   if (attn) return fail(-3, "attention maps are limited to %d sequences per call", chunk);
   const size_t P = (size_t)g->c.seq * g->c.splits;
   for (int b0 = 0; b0 < nb; b0 += chunk) {
     const int nc = nb - b0 < chunk ? nb - b0 : chunk;
-    int rc = gen_forward_impl(g, tokens + (size_t)b0 * P, labels + b0, drop ? drop + b0 : nullptr, logits + (size_t)b0 * P * g->C, nc, s);
+    int rc = gen_forward_pass(g, tokens + (size_t)b0 * P, labels + b0, drop ? drop + b0 : nullptr, logits + (size_t)b0 * P * g->C, nc, s);
     if (rc) return rc;
   }
   return 0;
@@ -346,7 +409,7 @@ int gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, const u
 // Guided forward (sampling.py:83-88) over B samples: logits rows [0, B) conditional, [B, 2B) label-dropped.
 int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, float* logits, int B, hipStream_t s) {
   const size_t P = (size_t)g->c.seq * g->c.splits;
-  const bool pair = g->pair_ok && g->c.precision >= 1;
+  const bool pair = !g->f32 && g->pair_ok && g->c.precision >= 1;   // (the fp32 reference mode: the plain forward over [cond | dropped])
   const bool wmode = pair && g->c.precision >= 2;       // weight-rounding correction pass (every step: weight rounding costs parity late in the run too)
   const int chunk = g->chunk_seqs / 2;                  // pairs per pass
   if (chunk < 1) return fail(-1, "engine holds %d sequences: too few for a guided forward", g->chunk_seqs);
@@ -365,7 +428,7 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
     float* out = (nc == B) ? logits : g->logits_tmp;    // chunked: through a buffer of the engine's own, then to the two halves of the caller's
     if (b0 == 0) g_prof.begin_forward(false);           // one guided forward = all of its chunks
     int rc = pair ? gen_forward_pair_impl(g, g->tok_cfg, g->lab_cfg, g->drop_cfg, out, nc, wmode, s)
-                  : gen_forward_impl(g, g->tok_cfg, g->lab_cfg, g->drop_cfg, out, 2 * nc, s);
+                  : gen_forward_pass(g, g->tok_cfg, g->lab_cfg, g->drop_cfg, out, 2 * nc, s);
     if (rc) return rc;
     if (nc != B) {
       HIP_TRY(hipMemcpyAsync(logits + (size_t)b0 * P * g->C, out, nc * P * g->C * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -416,8 +479,10 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   if (C > 4096 || (c.splits * C) % 4) return fail(-1, "unsupported group codebook size %d (the fused step kernel holds up to 4096 codes per group)", C);
   if ((c.prenorm != 0 && c.prenorm != 1) || (c.embed_tables != 0 && c.embed_tables != 1)) return fail(-1, "prenorm / embed_tables must be 0 or 1");
   if (c.embed_tables && c.splits > 8) return fail(-1, "embed_tables supports up to 8 token groups");
-  if (c.precision < 0 || c.precision > 4) return fail(-1, "precision must be 0 .. 4 (MB_PREC_FP16 / _DIFF / _WCORR / _ALO / _ALO_ALL)");
+  if (c.precision < 0 || c.precision > MB_PREC_F32) return fail(-1, "precision must be 0 .. 5 (MB_PREC_FP16 / _DIFF / _WCORR / _ALO / _ALO_ALL / _F32)");
+  const bool f32 = c.precision == MB_PREC_F32;          // the fp32 reference mode: every configuration accepted above, fp32 weights and workspace only
   mb_gen* g = new mb_gen();
+  g->f32 = f32;
   g->c = c; g->max_seqs = max_seqs; g->N = c.seq + 1; g->gbits = c.bits / c.splits; g->C = C;
   (void)hipGetDevice(&g->device);
   // rows per forward pass: 32-bit byte offsets inside the kernels need rows * max(mlp, 3 * hidden) * 4 < 2^32 (gemm_ht_supported)
@@ -427,13 +492,14 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   const size_t d = c.hidden, f = c.mlp, M = (size_t)g->chunk_seqs * g->N;
   mb::DevArena& m = g->mem;
   g->layers.resize(c.depth);
-  m.get(&g->split_tmp, 1);
-  m.zeroed(&g->sat, 1);
-  for (auto& L : g->layers) {
-    m.get(&L.wqkv, 3 * d * d); m.get(&L.bqkv, 3 * d);
-    m.get(&L.wo, d * d); m.get(&L.bo, d);
-    m.get(&L.w1, f * d); m.get(&L.b1, f);
-    m.get(&L.w2, d * f); m.get(&L.b2, d);
+  if (f32) g->layers32.resize(c.depth);
+  else m.get(&g->split_tmp, 1);
+  m.zeroed(&g->sat, 1);                                 // (the fp32 mode has no fp16 store to clamp: the count stays 0)
+  for (int l = 0; l < c.depth; ++l) {
+    mb_gen::Layer& L = g->layers[l];
+    if (f32) { mb_gen::Layer32& W = g->layers32[l]; m.get(&W.wqkv, 3 * d * d); m.get(&W.wo, d * d); m.get(&W.w1, f * d); m.get(&W.w2, d * f); }
+    else { m.get(&L.wqkv, 3 * d * d); m.get(&L.wo, d * d); m.get(&L.w1, f * d); m.get(&L.w2, d * f); }
+    m.get(&L.bqkv, 3 * d); m.get(&L.bo, d); m.get(&L.b1, f); m.get(&L.b2, d);
     m.get(&L.ln1g, d); m.get(&L.ln1b, d); m.get(&L.ln2g, d); m.get(&L.ln2b, d);
   }
   m.get(&g->w_in, d * c.bits); m.get(&g->b_in, d);
@@ -441,19 +507,26 @@ int mb_gen_create(const mb_gen_cfg* cfg, int max_seqs, mb_gen** out) {
   if (c.embed_tables) { m.get(&g->tables, (size_t)c.splits * (C + 1) * d); m.get(&g->bias_pos, (size_t)c.seq * c.splits * C); }
   m.get(&g->class_emb, (size_t)(c.nclass + 1) * d); m.get(&g->pos, (size_t)g->N * d);
   m.get(&g->ln0g, d); m.get(&g->ln0b, d);
-  m.get(&g->wl, d * d); m.get(&g->wl_lo, d * d); m.get(&g->bl, d); m.get(&g->lnhg, d); m.get(&g->lnhb, d);
-  m.get(&g->wp, (size_t)c.splits * C * d); m.get(&g->bp, (size_t)c.splits * C); m.get(&g->head_scale, 2);
-  if (!c.embed_tables) m.get(&g->wp_lo, (size_t)c.splits * C * d);
-  m.get(&g->y_f32, M * d); m.get(&g->ln_stats, M * 2); m.get(&g->x_h16, M * d);
-  m.get(&g->x_lo, M * d);   // lo halves of the LayerNorm outputs: always for the head GEMMs, precision >= 1 for QKV / FFN-up of plain forwards
-  m.get(&g->qkv, M * 3 * d); m.get(&g->att, M * d); m.get(&g->h, M * f);
+  m.get(&g->bl, d); m.get(&g->lnhg, d); m.get(&g->lnhb, d); m.get(&g->bp, (size_t)c.splits * C);
+  m.get(&g->y_f32, M * d);
+  if (f32) {
+    m.get(&g->wl32, d * d); m.get(&g->wp32, (size_t)c.splits * C * d);
+    m.get(&g->x_f32, M * d); m.get(&g->qkv32, M * 3 * d); m.get(&g->att32, M * d); m.get(&g->h32, M * f);
+  } else {
+    m.get(&g->wl, d * d); m.get(&g->wl_lo, d * d);
+    m.get(&g->wp, (size_t)c.splits * C * d); m.get(&g->head_scale, 2);
+    if (!c.embed_tables) m.get(&g->wp_lo, (size_t)c.splits * C * d);
+    m.get(&g->ln_stats, M * 2); m.get(&g->x_h16, M * d);
+    m.get(&g->x_lo, M * d);   // lo halves of the LayerNorm outputs: always for the head GEMMs, precision >= 1 for QKV / FFN-up of plain forwards
+    m.get(&g->qkv, M * 3 * d); m.get(&g->att, M * d); m.get(&g->h, M * f);
+  }
   // MX-fp4 mini-tile passes (precision 2 / 3): 257- / 1025-token sequences, vector LayerNorm widths, heads of 64 (the attention kernels' e2m1 output), whole mini-tiles
-  g->mini_ok = c.precision >= 2 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && c.hidden / c.heads == 64;   // (FFN-up's N = mlp: whole 256-column tiles)
+  g->mini_ok = !f32 && c.precision >= 2 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && c.hidden / c.heads == 64;   // (FFN-up's N = mlp: whole 256-column tiles)
   // differential CFG forward: 257-token sequences (pair tiles = 2 x 128 tokens + the class pair), vector LayerNorm widths, plain fp16 operands
   // (round 5: also the 1024 + 1-token models of 512 x 512 images -- a pair tile is 128 tokens of a sequence pair whatever the sequence length)
   if (c.precision == 3) g->alo_mask = g->alo_mask_built = 6;                 // out-proj + FFN-up, every layer
-  if (c.precision >= 4) g->alo_mask = g->alo_mask_built = 14;                // + FFN-down
-  g->pair_ok = c.precision >= 1 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && g->chunk_seqs >= 2 &&
+  if (c.precision == 4) g->alo_mask = g->alo_mask_built = 14;                // + FFN-down
+  g->pair_ok = !f32 && c.precision >= 1 && (c.seq == 256 || c.seq == 1024) && (c.hidden == 768 || c.hidden == 1024) && c.mlp % 256 == 0 && g->chunk_seqs >= 2 &&
                (c.precision == 1 || g->mini_ok);
   if (g->mini_ok) {
     const size_t ntok = (size_t)g->chunk_seqs * c.seq;
@@ -543,7 +616,8 @@ int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* s
       const size_t rows = (size_t)g->C + 1;
       if (numel != rows * d) return fail(-4, "mb_gen_load: '%s' has %zu elements, expected %zu", name, numel, rows * d);
       HIP_TRY(hipMemcpyAsync(g->tables + (size_t)q * rows * d, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-      mb::cast_f32_to_h16(s, data, g->wp + (size_t)q * g->C * d, (size_t)g->C * d);
+      if (g->f32) HIP_TRY(hipMemcpyAsync(g->wp32 + (size_t)q * g->C * d, data, (size_t)g->C * d * sizeof(float), hipMemcpyDeviceToDevice, s));   // the tied head: fp32 table rows
+      else mb::cast_f32_to_h16(s, data, g->wp + (size_t)q * g->C * d, (size_t)g->C * d);
       g->loaded++;
       return 0;
     }
@@ -556,11 +630,16 @@ int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* s
       return 0;
     }
   }
+  if (g->f32 && sidx >= 0) {                           // a GEMM weight in the fp32 reference mode: kept as the checkpoint's fp32, no repack, no hi / lo planes
+    if (sidx < 4 * c.depth) { mb_gen::Layer32& W = g->layers32[sidx >> 2]; float* const w4[4] = {W.wqkv, W.wo, W.w1, W.w2}; dst_f = w4[sidx & 3]; }
+    else dst_f = sidx == 4 * c.depth ? g->wl32 : g->wp32;
+    dst_h = nullptr;
+  }
   if (!dst_f && !dst_h) return fail(-2, "mb_gen_load: unknown checkpoint entry '%s'", name);
   if (numel != want) return fail(-4, "mb_gen_load: '%s' has %zu elements, expected %zu", name, numel, want);
   if (dst_f == g->w_in) mb::transpose_f32(s, data, g->w_in, (int)d, c.bits);       // [d,K] -> [K,d] for the embed kernel
-  else if (dst_h == g->wl) mb::split_f32_to_h16_planes(s, data, g->wl, g->wl_lo, wrows, wcols, g->head_scale, g->split_tmp);
-  else if (dst_h == g->wp) mb::split_f32_to_h16_planes(s, data, g->wp, g->wp_lo, wrows, wcols, g->head_scale + 1, g->split_tmp);
+  else if (dst_h && dst_h == g->wl) mb::split_f32_to_h16_planes(s, data, g->wl, g->wl_lo, wrows, wcols, g->head_scale, g->split_tmp);
+  else if (dst_h && dst_h == g->wp) mb::split_f32_to_h16_planes(s, data, g->wp, g->wp_lo, wrows, wcols, g->head_scale + 1, g->split_tmp);
   else if (dst_h) {
     mb::cast_f32_to_h16(s, data, dst_h, numel);
     if (g->mini_ok && sidx >= 0 && sidx < 4 * c.depth) {
@@ -612,6 +691,7 @@ int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels,
                         int nb, mb_stream stream) {
   if (!g || !tokens || !labels || !logits || !attn) return fail(-1, "mb_gen_forward_attn: null argument");
   if (nb <= 0 || nb > g->max_seqs) return fail(-1, "mb_gen_forward_attn: nb=%d outside [1, %d]", nb, g->max_seqs);
+  if (g->f32) return fail(-3, "mb_gen_forward_attn: attention maps are not available in the fp32 reference mode (precision %d)", (int)MB_PREC_F32);
   return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
 }
 
@@ -751,7 +831,7 @@ int sample_run(mb_gen* g, mb_dec* d, const RunSpec& r, const int64_t* labels, in
     // forward is not run: the step is the plain conditional forward, bit for bit what the guided expression evaluates to.
     // (precision 4: the guided forward is also the MORE PRECISE conditional forward -- its pair tiles carry the activation-lo sets, the plain tiles do not --
     // and the first, almost fully masked steps are where near-ties flip: the zero-scale steps run it too; its unconditional half is then multiplied by 0)
-    if (id.guided && (r.scale[i] != 0.0f || (g->pair_ok && c.precision >= 4))) {
+    if (id.guided && (r.scale[i] != 0.0f || (!g->f32 && g->pair_ok && c.precision >= 4))) {
       rc = gen_forward_cfg(g, cur, labels, g->logits, B, s);
       a.logits_u = g->logits + (size_t)B * P * C;
       if (B <= g->chunk_seqs / 2) { run.cfg_labels = labels; run.cfg_B = B; }   // lab_cfg / drop_cfg stay valid for the rest of this call

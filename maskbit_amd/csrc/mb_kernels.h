@@ -145,6 +145,28 @@ bool gemm_ht_supported(GemmEpi epi, const GemmArgs& a);
 void gemm_ht(hipStream_t s, GemmEpi epi, const GemmArgs& a, int mt);
 void set_cu_count(int n);   // persistent grids are sized for n CUs (0 = the device's count): for launches on CU-masked streams
 
+// ---- the fp32 reference mode (gemm_f32.hip; MB_PREC_F32): everything fp32 in global memory -------------------------------------------------------
+// gemm_f32: out[M,N] = epi(A[M,K] . W[N,K]^T + bias) on the f32-input MFMA.  NUMERICAL CONTRACT: every output element is
+//   acc = 0; for k = 0 .. K-1: acc = fmaf(A[m,k], W[n,k], acc)   -- one chain, ascending k, continued across K-tiles in the same accumulator --,
+// then ONE fp32 add of the bias, then the epilogue: no split-K, no reordering, so the result does not depend on tile position, batch size or grid.
+// Any M >= 1, N >= 1, K >= 4 with K % 4 == 0 (A, W 16-byte aligned); ragged M / N / K-tile edges are guarded, nothing is read out of bounds.
+enum GemmF32Epi {
+  F32_EPI_PLAIN = 0,    // out = acc + bias                               (QKV)
+  F32_EPI_GELU = 1,     // out = gelu_erf(acc + bias), accurate erff      (FFN-up, last_layer.0)
+  F32_EPI_RES = 2,      // out = (acc + bias) + residual[m,n]             (out-proj, FFN-down; out may alias residual)
+  F32_EPI_LOGITS = 3,   // EPI_LOGITS_F32's rows: m % period == period - 1 dropped, the rest compacted; bias [N] or, bias_per_pos, [period - 1][N]
+};
+struct GemmF32Args {
+  int epi;
+  const float* A; const float* W; const float* bias; const float* residual; float* out;
+  int M, N, K;
+  int period = 0, bias_per_pos = 0;
+};
+int gemm_f32(hipStream_t s, const GemmF32Args& a);   // 0, or -1: refused (shape, alignment, a missing pointer), nothing launched
+// fp32 qkv [nb, N, 3d] (nn.MultiheadAttention's head split, as `attention` below) -> fp32 out [nb, N, d] = softmax(Q K^T / sqrt(dh)) V per (sequence,
+// head); scores, softmax and P V in fp32 on the VALU, keys streamed in tiles with a running max and sum.  Any N >= 1; d / heads = 32 or 64 (-1 otherwise).
+int attention_f32(hipStream_t s, const float* qkv, float* out, int nb, int N, int d, int heads);
+
 // e2m1 copy of a weight for the mini-tile passes: e2m1(fp16(W[n][k]) * 2^r) in the mini-tile-packed layout (w4_packed_offset; N K / 2 bytes), r per
 // (row, 128 columns) chosen to minimise the block's quantisation error; scale_out [N K / 128] in the kernel's lane order (w4_scale_index).  N % 64 == 0, K % 128 == 0.
 void w4_from_f32(hipStream_t s, const float* src, uint8_t* dst4, int N, int K, uint8_t* scale_out);
@@ -177,7 +199,7 @@ struct EmbedArgs {
   const float* class_emb;  // [nclass+1, d]
   const float* pos;        // [seq+1, d]
   const float* gamma; const float* beta;
-  float* x_f32; h16* x_h16;   // [nb*(seq+1), d]
+  float* x_f32; h16* x_h16;   // [nb*(seq+1), d]  (embed_ln: x_h16 may be null)
   int nb, seq, m, gbits, d, nclass;
   // Bert (modeling/bert.py:313-315): per-group embedding tables [m][2^gbits + 1][d] summed instead of the bit projection
   const float* tables = nullptr;

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(EmbedArgs a) {
       sc[q] = e;
     }
   }
-  ln_finish<NV>(v, sc, ns, d, lane, a.gamma, a.beta, 1e-12f, a.x_f32 + (size_t)row * d, a.x_h16 + (size_t)row * d, nullptr,
+  ln_finish<NV>(v, sc, ns, d, lane, a.gamma, a.beta, 1e-12f, a.x_f32 + (size_t)row * d, a.x_h16 ? a.x_h16 + (size_t)row * d : nullptr, nullptr,   // (x_h16 null: the fp32 reference mode)
                  a.x_lo ? a.x_lo + (size_t)row * d : nullptr,
                  (a.f4.x4 || a.f4.xl4) ? &a.f4 : nullptr, row);
 }

@@ -77,21 +77,21 @@ def tokens_in(g, i: int) -> torch.Tensor:
 
 def reference_noise(g, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """(exp_noise [S, B*n*2, C], conf_noise [S, B, n, 2]) exactly as the reference drew them (CPU default generator)."""
-    S, B, n = g["steps"].shape[0], g["steps"].shape[1], g["steps"].shape[2]
+    S, B, n, m = g["steps"].shape                                 # (m token groups: 2 in every recorded run of the reference)
     rt = float(g["kw"]["randomize_temperature"])
     torch.manual_seed(g["seed"])
     gum = torch.distributions.Gumbel(0.0, 1.0)
     qs, cs = [], []
     for i in range(S):
-        qs.append(torch.empty(B * n * 2, g["C"]).exponential_(1))
-        cs.append(gum.sample((B, n, 2)) * rt * (1 - (i + 1) / S))
+        qs.append(torch.empty(B * n * m, g["C"]).exponential_(1))
+        cs.append(gum.sample((B, n, m)) * rt * (1 - (i + 1) / S))
     return torch.stack(qs).to(device), torch.stack(cs).to(device)
 
 
 def plan_of(g):
     from maskbit_amd.sampling import build_plan
     kw = g["kw"]
-    return build_plan(int(kw["num_steps"]), 2 * g["steps"].shape[2], float(kw["guidance_scale"]), kw["guidance_annealing"], float(kw["scale_pow"]), 1.0, False,
+    return build_plan(int(kw["num_steps"]), g["steps"].shape[3] * g["steps"].shape[2], float(kw["guidance_scale"]), kw["guidance_annealing"], float(kw["scale_pow"]), 1.0, False,
                       kw["mask_schedule_strategy"])
 
 
@@ -156,7 +156,7 @@ def teacher_forced(gen, g=None, noise=None, batch: int = 0):
     y = g["labels"].to(dev)
     if NB > B:
         fill = torch.Generator().manual_seed(g["seed"] + 99)
-        y_all = torch.randint(0, 1000, (NB,), generator=fill).to(dev)
+        y_all = torch.randint(0, gen.nclass, (NB,), generator=fill).to(dev)      # (1000 for every recorded run)
         y_all[rows] = y
     per_step, remask = [], 0
     total = 0
@@ -171,7 +171,7 @@ def teacher_forced(gen, g=None, noise=None, batch: int = 0):
             tall = tall.contiguous()
         else:
             tall, y_all = tin, y
-        if float(g["kw"]["guidance_scale"]) != 0.0 and (scale[i] != 0.0 or gen.resolved_precision() >= 4):   # (precision 4: mb_sample runs the zero-scale steps through the guided forward too)
+        if float(g["kw"]["guidance_scale"]) != 0.0 and (scale[i] != 0.0 or gen.resolved_precision() == 4):   # (precision 4: mb_sample runs the zero-scale steps through the guided forward too)
             lg = gen.forward_cfg(tall, y_all)              # the guided forward of the loop (cond | label-dropped); as in mb_sample, the steps whose
                                                                      # annealed scale is exactly 0 run the conditional forward alone (c + 0 (c - u) == c)
             lc, lu = lg[:NB][rows].contiguous(), lg[NB:][rows].contiguous()
@@ -179,7 +179,7 @@ def teacher_forced(gen, g=None, noise=None, batch: int = 0):
             lc, lu = gen(tall, y_all, torch.zeros(NB, dtype=torch.bool, device=dev))[rows].contiguous(), None
         tout, pred = torch.empty_like(tin), torch.empty_like(tin)
         _lib.check(lib.mb_sample_step(lc.data_ptr(), lu.data_ptr() if lu is not None else None, scale[i], temp[i], q[i].data_ptr(), c[i].data_ptr(),
-                                      mask_len[i], tin.data_ptr(), tout.data_ptr(), pred.data_ptr(), B, g["steps"].shape[2], 2, g["C"],
+                                      mask_len[i], tin.data_ptr(), tout.data_ptr(), pred.data_ptr(), B, g["steps"].shape[2], g["steps"].shape[3], g["C"],
                                       torch.cuda.current_stream().cuda_stream), "mb_sample_step")
         msk = g["masks"][i]
         per_step.append(int((pred.cpu() != g["steps"][i])[msk].sum()))
