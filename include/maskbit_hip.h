@@ -343,6 +343,25 @@ size_t mb_is_workspace_bytes(int B, int C);
 int mb_is_accumulate(const void* logits, int dtype, int B, int C, int64_t row_stride, double* prob_total, double* kl_total, void* workspace,
                      mb_stream stream);
 
+/* ---- precision / recall: the k-NN manifolds of Kynkaanniemi et al. as ADM's evaluator computes them (manifold_radii / evaluate_pr) ----------- *
+ * Stateless: caller-owned buffers, no allocation, no synchronisation.  dtype and row_stride as above (0 = fp32 widened exactly, 1 = fp64; elements).
+ * For rows a, b of width D:   d2(a, b) = max(0, |a|^2 + |b|^2 - 2 a.b),   the three sums in fp64 (a.b on v_mfma_f64_16x16x4_f64), each in a fixed
+ * order over d that does not depend on where the row sits in its matrix, on N or on the launch geometry (csrc/manifold.hip states the orders), the
+ * combination as fma(-2, a.b, |a|^2 + |b|^2).  So a pair's value is a function of the two rows alone: results are bitwise reproducible, a row
+ * permutation of X permutes radii2 bit for bit, and mb_manifold_cover over any split of the queries leaves the bytes of one call.  The N x N
+ * matrix is never stored; no floating-point atomics.
+ * Bytes of workspace for N rows in all (mb_knn_radii: N; mb_manifold_cover: Nq + Nb) -- 145 doubles per row: its |a|^2, and for each of up to 16
+ * parts the column walk is cut into a list of 9 values (or a flag); 0 for a shape the entries do not take (N outside [1, 2^24], D outside
+ * [1, 2^20]). */
+size_t mb_manifold_workspace_bytes(int N, int D);
+/* radii2 double [N]: radii2[i] = the (k+1)-th smallest of { d2(x_i, x_j) : j = 0..N-1 } counted with multiplicity, d2(x_i, x_i) taken as exactly 0
+ * -- the squared distance to the k-th nearest neighbour other than the row itself (ADM's manifold_radii).  X [N, D]; 1 <= k <= 8, k + 1 <= N. */
+int mb_knn_radii(const void* x, int dtype, int N, int D, int64_t row_stride, int k, double* radii2, void* workspace, mb_stream stream);
+/* inside uint8 [Nq]: 1 iff some j has d2(q, b_j) <= radii2[j] (`<=` as in ADM's evaluate_pr), else 0.  Q [Nq, D] and B [Nb, D] may differ in dtype
+ * and stride; radii2 double [Nb] belongs to B. */
+int mb_manifold_cover(const void* q, int q_dtype, int Nq, int64_t q_stride, const void* b, int b_dtype, int Nb, int64_t b_stride, int D,
+                      const double* radii2, uint8_t* inside, void* workspace, mb_stream stream);
+
 /* ---- FID Inception-v3 (the network behind the reference's metrics.inception.get_inception_model(): pytorch-fid's pt_inception-2015-12-05) ------ *
  * fp16 NHWC activations, one general implicit-GEMM convolution on MFMA with a BatchNorm (eval) + ReLU epilogue (csrc/inception.hip); the graph
  * is the one written out in DESIGN.md "Inception-v3".  The handle holds the packed weights and the activation buffers for max_images images. */
@@ -357,6 +376,12 @@ int mb_inception_load(mb_inception* h, const char* name, const float* data, cons
  * fc.bias; a NULL output is skipped.  A row does not depend on B or on the other images (no floating-point atomics).  No synchronisation.
  * Fails (-1) before any launch when the checkpoint is incomplete or the geometry is not taken. */
 int mb_inception_forward(mb_inception* h, const uint8_t* u8, int B, int H, int W, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
+/* mb_inception_forward plus the spatial tap of sFID: spatial fp32 [B, 2023] (may be NULL) = the first 7 channels of Mixed_6d.branch1x1 after
+ * BatchNorm and ReLU on the 17 x 17 map, flattened in (h, w, c) order as ADM's evaluator reshapes `mixed_6/conv:0`[..., :7] of the NHWC tensor
+ * (Mixed_6d is the 2015 graph's mixed_6, its first conv the 1 x 1 branch).  Whether that graph tensor is the post-ReLU one could not be checked
+ * against TensorFlow; sFID values are therefore NOT claimed to match published ones (DESIGN.md "sFID").  The other outputs keep their bits. */
+int mb_inception_forward_spatial(mb_inception* h, const uint8_t* u8, int B, int H, int W, float* spatial, float* pool, float* logits_unbiased,
+                                 float* logits, mb_stream stream);
 /* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
 int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream);
 

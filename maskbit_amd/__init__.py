@@ -9,6 +9,7 @@ from .masking import get_masking_ratio
 from .sampling import sample, sample_seeded
 from .evaluator import TokenizerEvaluator
 from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covariance, inception_score
+from .manifold import knn_radii, manifold_coverage, precision_recall
 from .lpips import LPIPS
 from .inception import InceptionV3, get_inception_model
 from .editing import inpaint, sample_from_tokens
@@ -22,4 +23,5 @@ __all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sa
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",
            "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance",
-           "InceptionV3", "get_inception_model", "check_checkpoint", "CheckpointReport"]
+           "InceptionV3", "get_inception_model", "check_checkpoint", "CheckpointReport",
+           "knn_radii", "manifold_coverage", "precision_recall"]

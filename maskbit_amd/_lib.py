@@ -130,10 +130,15 @@ SIGNATURES = {
     "mb_fid_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_is_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mb_is_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_manifold_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mb_knn_radii": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_manifold_cover": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "mb_inception_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "mb_inception_destroy": (None, [C.c_void_p]),
     "mb_inception_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
     "mb_inception_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_inception_forward_spatial": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_inception_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
     "mb_convbn_layer": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(C.c_uint)] + [C.c_int] * 15 + [C.c_void_p]),
     "mb_pool3": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),

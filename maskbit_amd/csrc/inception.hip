@@ -260,6 +260,12 @@ __global__ __launch_bounds__(IC_THREADS) void fc_head_kernel(const float* __rest
   }
 }
 
+// out fp32 [B][HW][C] = channels [off, off + C) of x fp16 [B, HW, cs]: a tap of the first channels of a map, flattened in (h, w, c) order
+__global__ __launch_bounds__(IC_THREADS) void channel_tap_kernel(const h16* __restrict__ x, float* __restrict__ out, size_t n, int C, int off, int cs) {
+  for (size_t i = (size_t)blockIdx.x * IC_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * IC_THREADS)
+    out[i] = (float)x[(i / C) * cs + off + i % C];
+}
+
 unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>(16384, std::max<size_t>(1, (n + IC_THREADS - 1) / IC_THREADS)); }
 
 }  // namespace
@@ -339,6 +345,11 @@ void launch_spatial_mean(hipStream_t s, const h16* x, float* mean, int B, int HW
   }
 }
 
+void launch_channel_tap(hipStream_t s, const h16* x, float* out, int B, int HW, int C, int off, int cs) {
+  const size_t n = (size_t)B * HW * C;
+  hipLaunchKernelGGL(channel_tap_kernel, dim3(grid_for(n)), dim3(IC_THREADS), 0, s, x, out, n, C, off, cs);
+}
+
 void launch_fc_head(hipStream_t s, const float* pool, const float* w, const float* bias, float* unbiased, float* biased, int B, int D, int N) {
   hipLaunchKernelGGL(fc_head_kernel, dim3((N + 3) / 4, (B + 7) / 8), dim3(IC_THREADS), 0, s, pool, w, bias, unbiased, biased, B, D, N);
 }
@@ -353,7 +364,7 @@ struct IcConv {
   float *bn = nullptr, *scale = nullptr, *shift = nullptr;     // bn [4][cout]: gamma, beta, running mean, running variance
 };
 struct IcView { int buf, off, cs, H, W, C; };                  // channels [off, off + C) of buffer `buf`, [B, H, W, cs]
-enum { IC_OP_CONV, IC_OP_POOL, IC_OP_MEAN, IC_OP_MAP };
+enum { IC_OP_CONV, IC_OP_POOL, IC_OP_MEAN, IC_OP_MAP, IC_OP_SPATIAL };
 struct IcOp { int kind, idx; IcView in, out; std::string scope; };   // idx: the convolution, the pool mode, the fp32 tap (0 .. 2) or the fp16 map (0 .. 3)
 constexpr int IC_NBUF = 5;                                     // 0 / 1: a block's input and output in turn; 2 / 3: a branch's intermediates; 4: the pooled input
 
@@ -382,6 +393,7 @@ struct IcNet {
   }
   void mean(IcView in, int tap) { ops.push_back({IC_OP_MEAN, tap, in, in, "inception_mean"}); }
   void map(IcView in, int id) { ops.push_back({IC_OP_MAP, id, in, in, ""}); }
+  void spatial(IcView in, int channels) { in.C = channels; ops.push_back({IC_OP_SPATIAL, 0, in, in, "inception_spatial"}); }
   static IcView whole(IcView part, int cs) { return {part.buf, 0, cs, part.H, part.W, cs}; }
 
   IcView block_a(const std::string& n, IcView x, int pf, int y) {
@@ -459,6 +471,7 @@ struct IcNet {
     x = block_c("Mixed_6b", x, 128, 0);
     x = block_c("Mixed_6c", x, 160, 1);
     x = block_c("Mixed_6d", x, 160, 0);
+    spatial(x, IC_SPATIAL_C);                 // the first channels of Mixed_6d.branch1x1, which the block wrote at channel 0 of its output
     x = block_c("Mixed_6e", x, 192, 1);
     mean(x, 2); map(x, 2);
     group = "Mixed_7";
@@ -491,7 +504,7 @@ using namespace mb;
 
 namespace {
 
-struct IcOut { void* map[4]; float* tap[3]; float *pool, *unbiased, *biased; };
+struct IcOut { void* map[4]; float* tap[3]; float *pool, *unbiased, *biased; float* spatial = nullptr; };
 
 int check_inception(const char* what, mb_inception* h, const uint8_t* u8, int B, int H, int W) {
   if (!h || !u8) return fail(-1, "%s: null argument", what);
@@ -518,6 +531,11 @@ void run_inception(mb_inception* h, const uint8_t* u8, int B, int H, int W, cons
     } else if (op.kind == IC_OP_MEAN) {
       ProfScope p(op.scope.c_str(), s);
       if (o.tap[op.idx]) launch_spatial_mean(s, at(h, op.in), o.tap[op.idx], B, op.in.H * op.in.W, op.in.C);
+    } else if (op.kind == IC_OP_SPATIAL) {
+      if (o.spatial) {
+        ProfScope p(op.scope.c_str(), s);
+        launch_channel_tap(s, at(h, op.in), o.spatial, B, op.in.H * op.in.W, op.in.C, op.in.off, op.in.cs);
+      }
     } else if (o.map[op.idx]) {
       (void)hipMemcpyAsync(o.map[op.idx], at(h, op.in), (size_t)B * op.in.H * op.in.W * op.in.C * sizeof(h16), hipMemcpyDeviceToDevice, s);
     }
@@ -597,6 +615,17 @@ int mb_inception_forward(mb_inception* h, const uint8_t* u8, int B, int H, int W
   hipStream_t s = (hipStream_t)stream;
   ProfScope p("inception", s);
   run_inception(h, u8, B, H, W, IcOut{{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, pool, logits_unbiased, logits}, s);
+  return launched();
+}
+
+int mb_inception_forward_spatial(mb_inception* h, const uint8_t* u8, int B, int H, int W, float* spatial, float* pool, float* logits_unbiased,
+                                 float* logits, mb_stream stream) {
+  if (int rc = check_inception("mb_inception_forward_spatial", h, u8, B, H, W)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope p("inception", s);
+  IcOut o{{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, pool, logits_unbiased, logits};
+  o.spatial = spatial;
+  run_inception(h, u8, B, H, W, o, s);
   return launched();
 }
 

@@ -12,6 +12,7 @@ namespace mb {
 constexpr int IC_CK = 32;                 // input channels per MFMA step
 constexpr int IC_BN = 64;                 // output channels are padded to whole 64-channel tiles in the packed weights
 constexpr int IC_SIDE = 299;              // the network's input resolution
+constexpr int IC_SPATIAL_C = 7;           // channels of the sFID tap: Mixed_6d.branch1x1[..., :7] on the 17 x 17 map = 2023 values
 constexpr int IC_INC = 8;                 // channels of the input image buffer (3 + 5 zeros: one 16-byte slot)
 
 inline int ic_cin_pad(int cin) { return (cin + IC_CK - 1) / IC_CK * IC_CK; }
@@ -46,6 +47,8 @@ void launch_pool3(hipStream_t s, const Pool3& q);
 void launch_inception_input(hipStream_t s, const uint8_t* u8, h16* out, int B, int H, int W);
 // x fp16 [B, HW, C] (C % 8 == 0) -> mean fp32 [B, C]: per image a fixed-order fp32 sum, / float(HW)
 void launch_spatial_mean(hipStream_t s, const h16* x, float* mean, int B, int HW, int C);
+// out fp32 [B, HW * C] = channels [off, off + C) of x fp16 [B, HW, cs], (pixel, channel) order
+void launch_channel_tap(hipStream_t s, const h16* x, float* out, int B, int HW, int C, int off, int cs);
 // pool fp32 [B, D] x w fp32 [N, D] -> unbiased [B, N] (or null), biased [B, N] = unbiased + bias (or null); D % 256 == 0, D <= 2048
 void launch_fc_head(hipStream_t s, const float* pool, const float* w, const float* bias, float* unbiased, float* biased, int B, int D, int N);
 

@@ -10,6 +10,11 @@ rank-B update that reads and writes the upper half of that state once, and ``mb_
 evaluator.py:553-564 in float64.  The state -- ``total`` [D], ``sigma`` [D, D], ``prob_total`` / ``kl_total`` [C], the index histogram -- stays on
 the device; updates enqueue on the current stream and never synchronise; ``result()`` makes one device-to-host copy.  There is no CPU path for
 the evaluator; ``frechet_distance``, ``inception_score`` and ``get_covariance`` are plain torch and take CPU tensors.
+
+Beyond the reference, the rest of ADM's table: ``use_precision_recall(reference_features)`` collects the pool features on the device and ``result()``
+adds ``Precision`` / ``Recall`` (``maskbit_amd.manifold``, ``csrc/manifold.hip``); ``use_spatial_statistics((mu_s, sigma_s))`` accumulates a second
+state over the extractor's ``"spatial"`` features and ``result()`` adds ``sFID``.  Both are methods, not constructor keywords, and without them
+``result()`` is what it was.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .manifold import MAX_K, precision_recall
 
 _IS_EPS = 1e-16                          # evaluator.py:509
 _HOW_TO_ATTACH = ("attach a feature extractor first: evaluator.use_inception(extractor, real_statistics), where extractor(uint8 [B,3,H,W]) returns "
@@ -164,13 +170,21 @@ class ScoreStatistics:
                                         self._workspace.data_ptr(), torch.cuda.current_stream().cuda_stream), "mb_is_accumulate")
 
 
-def extract(extractor: Callable, u8_nchw: torch.Tensor, want_pool: bool, want_logits: bool):
-    """Runs the attached network on uint8 [B, 3, H, W] -> (pool or None, logits or None), checking the contract of ``get_inception_model()``."""
+def extract_all(extractor: Callable, u8_nchw: torch.Tensor, want_pool: bool, want_logits: bool, want_spatial: bool):
+    """Runs the attached network on uint8 [B, 3, H, W] -> (pool or None, logits or None, spatial or None), checking the contract of
+    ``get_inception_model()``; ``spatial`` is the key of sFID (``InceptionV3(features_list=[..., "spatial"])``)."""
     out = extractor(u8_nchw)
-    for key, want in (("2048", want_pool), ("logits_unbiased", want_logits)):
+    for key, want in (("2048", want_pool), ("logits_unbiased", want_logits), ("spatial", want_spatial)):
         if want and (not isinstance(out, Mapping) or key not in out):
-            raise ValueError(f"the feature extractor must return a mapping with the key {key!r} (metrics/inception.py)")
-    return (out["2048"] if want_pool else None), (out["logits_unbiased"] if want_logits else None)
+            raise ValueError(f"the feature extractor must return a mapping with the key {key!r} (metrics/inception.py)" if key != "spatial" else
+                             "use_spatial_statistics() is attached: the feature extractor must also return the key 'spatial' "
+                             "(InceptionV3(features_list=['2048', 'logits_unbiased', 'spatial']))")
+    return (out["2048"] if want_pool else None), (out["logits_unbiased"] if want_logits else None), (out["spatial"] if want_spatial else None)
+
+
+def extract(extractor: Callable, u8_nchw: torch.Tensor, want_pool: bool, want_logits: bool):
+    """``extract_all`` without the spatial features -> (pool or None, logits or None)."""
+    return extract_all(extractor, u8_nchw, want_pool, want_logits, False)[:2]
 
 
 def to_uint8(images: torch.Tensor) -> torch.Tensor:
@@ -214,6 +228,14 @@ class GeneratorEvaluator:
         self._is: Optional[ScoreStatistics] = None
         self._hist: Optional[torch.Tensor] = None
         self._out_of_range: Optional[torch.Tensor] = None
+        self._pr_reference: Optional[torch.Tensor] = None  # use_precision_recall: [Nr, D] as given, moved to the device by result()
+        self._pr_k = 3
+        self._pr_capacity = 0                              # rows the buffer is allocated with at the first update
+        self._pr_rows: Optional[torch.Tensor] = None       # fp32 [capacity, D] on the device; the first _pr_count rows are the pass's pool features
+        self._pr_count = 0
+        self._sfid_real_mu: Optional[torch.Tensor] = None  # use_spatial_statistics
+        self._sfid_real_sigma: Optional[torch.Tensor] = None
+        self._sfid: Optional[FeatureStatistics] = None
         self.reset_metrics()
 
     def _bind_device(self) -> torch.device:
@@ -234,6 +256,9 @@ class GeneratorEvaluator:
         if self._hist is not None:
             self._hist.zero_()
             self._out_of_range.zero_()
+        self._pr_count = 0
+        if self._sfid is not None:
+            self._sfid.reset()
 
     def use_inception(self, extractor: Optional[Callable], real_statistics=None) -> None:
         """Attaches the feature extractor (``None`` detaches) and, if given, the real statistics FID is measured against: ``(mu, sigma)`` or the
@@ -244,6 +269,69 @@ class GeneratorEvaluator:
         if real_statistics is not None:
             self._fid_real_mu, self._fid_real_sigma = load_statistics(real_statistics)
         self._inception_model = extractor
+
+    def use_precision_recall(self, reference_features: Optional[torch.Tensor], k: int = 3, max_samples: Optional[int] = None) -> None:
+        """Attaches the reference set of the improved precision / recall (``manifold.precision_recall``, ADM's ``compute_prec_recall``):
+        ``reference_features`` [Nr, D], the pool features of the reference images, on any device; ``None`` detaches.  From then on every update
+        also appends its pool features to an fp32 device buffer -- allocated with ``max_samples`` rows if given (50 000 x 2048 is 410 MB), doubled
+        whenever it is full -- without synchronising, and ``result()`` reports ``Precision`` and ``Recall`` after its other keys.  Rows collected
+        so far are kept; ``reset_metrics()`` empties the buffer."""
+        if reference_features is None:
+            self._pr_reference = self._pr_rows = None
+            self._pr_count = self._pr_capacity = 0
+            return
+        if not self._enable_fid:
+            raise ValueError("use_precision_recall needs the pool features: construct the evaluator with enable_fid=True")
+        r = reference_features
+        if not isinstance(r, torch.Tensor) or r.dim() != 2 or not r.is_floating_point():
+            raise ValueError(f"reference_features must be a floating-point [Nr, D] tensor, got {tuple(r.shape) if isinstance(r, torch.Tensor) else type(r).__name__}")
+        k = int(k)
+        if k < 1 or k > MAX_K:
+            raise ValueError(f"k = {k}: 1 <= k <= {MAX_K}")
+        if int(r.shape[0]) < k + 1 or int(r.shape[1]) < 1:
+            raise ValueError(f"reference_features of {tuple(r.shape)}: at least k + 1 = {k + 1} rows are needed")
+        if max_samples is not None and int(max_samples) < 1:
+            raise ValueError(f"max_samples = {max_samples}: at least one row, or None")
+        if self._fid is not None and self._fid.width is not None and int(r.shape[1]) != self._fid.width:
+            raise ValueError(f"reference_features have {int(r.shape[1])} columns; this pass was started with {self._fid.width}")
+        self._pr_reference, self._pr_k = r.detach(), k
+        self._pr_capacity = int(max_samples) if max_samples is not None else 0
+
+    def use_spatial_statistics(self, real_statistics_s) -> None:
+        """Attaches the real statistics of sFID: ``(mu_s, sigma_s)`` or the path of an ``.npz`` with those two keys (the names in ADM's reference
+        batches), of the width of the extractor's ``"spatial"`` features (2023 for ``InceptionV3``); ``None`` detaches.  From then on the attached
+        extractor must return ``"spatial"`` (``update_features_spatial`` takes the features directly), a second running state of that width is
+        accumulated by ``mb_fid_accumulate``, and ``result()`` reports ``sFID`` after its other keys.  What the spatial features are, and why no parity
+        with published sFID values is claimed, is stated in DESIGN.md "sFID"."""
+        if real_statistics_s is None:
+            self._sfid_real_mu = self._sfid_real_sigma = self._sfid = None
+            return
+        if self._num_examples:
+            raise ValueError("use_spatial_statistics: a pass is in progress; attach before the first update or after reset_metrics()")
+        if isinstance(real_statistics_s, (str, os.PathLike)):
+            if not os.path.isfile(real_statistics_s):
+                raise ValueError(f"statistics file does not exist at {real_statistics_s}")
+            with np.load(real_statistics_s) as z:
+                for key in ("mu_s", "sigma_s"):
+                    if key not in z:
+                        raise ValueError(f'spatial statistics file must contain a "{key}" key')
+                real_statistics_s = (z["mu_s"], z["sigma_s"])
+        self._sfid_real_mu, self._sfid_real_sigma = load_statistics(real_statistics_s)
+        self._sfid = None                                  # bound to the device at the next update
+
+    def _collect(self, pool: torch.Tensor, dev: torch.device) -> None:
+        """Appends a batch's pool features to the buffer of use_precision_recall.  Enqueued on the current stream, no synchronisation."""
+        B, D = (int(v) for v in pool.shape)
+        need = self._pr_count + B
+        if self._pr_rows is None or self._pr_rows.shape[1] != D or need > self._pr_rows.shape[0]:
+            have = 0 if self._pr_rows is None or self._pr_rows.shape[1] != D else int(self._pr_rows.shape[0])
+            rows = max(need, 2 * have, self._pr_capacity, 1024)
+            grown = torch.empty((rows, D), dtype=torch.float32, device=dev)
+            if self._pr_count:
+                grown[:self._pr_count].copy_(self._pr_rows[:self._pr_count])
+            self._pr_rows = grown
+        self._pr_rows[self._pr_count:need].copy_(pool.detach())
+        self._pr_count = need
 
     # -- the three ways in -----------------------------------------------------------------------------------------------------------------
     def update(self, generated_images: torch.Tensor, codebook_indices: Optional[torch.Tensor] = None):
@@ -263,8 +351,9 @@ class GeneratorEvaluator:
             return self._update(int(u8_nchw.shape[0]), None, None, codebook_indices)
         self._require_extractor()
         self._check_indices(codebook_indices)
-        pool, logits = extract(self._inception_model, u8_nchw, self._enable_fid, self._enable_inception_score)
-        self._update(int(u8_nchw.shape[0]), pool, logits, codebook_indices)
+        pool, logits, spatial = extract_all(self._inception_model, u8_nchw, self._enable_fid, self._enable_inception_score,
+                                            self._sfid_real_mu is not None)
+        self._update(int(u8_nchw.shape[0]), pool, logits, codebook_indices, spatial)
 
     def update_features(self, pool: Optional[torch.Tensor], logits: Optional[torch.Tensor], codebook_indices: Optional[torch.Tensor] = None):
         """Adds a batch whose features are already at hand: ``pool`` [B, D] (needed when FID is enabled) and ``logits`` [B, C] (needed when the
@@ -273,6 +362,15 @@ class GeneratorEvaluator:
         if given is None or not isinstance(given, torch.Tensor) or given.dim() != 2:
             raise ValueError("update_features needs pool [B, D] or logits [B, C]")
         self._update(int(given.shape[0]), pool, logits, codebook_indices)
+
+    def update_features_spatial(self, pool: Optional[torch.Tensor], logits: Optional[torch.Tensor], spatial: torch.Tensor,
+                                codebook_indices: Optional[torch.Tensor] = None):
+        """``update_features`` with the batch's spatial features [B, S] for sFID (``use_spatial_statistics`` must be attached)."""
+        if self._sfid_real_mu is None:
+            raise ValueError("update_features_spatial: no spatial statistics are attached (use_spatial_statistics)")
+        if not isinstance(spatial, torch.Tensor) or spatial.dim() != 2:
+            raise ValueError("update_features_spatial needs spatial [B, S]")
+        self._update(int(spatial.shape[0]), pool, logits, codebook_indices, spatial)
 
     def _require_extractor(self) -> None:
         if self._inception_model is None:
@@ -286,7 +384,7 @@ class GeneratorEvaluator:
         if codebook_indices.is_floating_point() or codebook_indices.is_complex():
             raise ValueError(f"codebook_indices must be an integer tensor, got {codebook_indices.dtype}")
 
-    def _update(self, B: int, pool, logits, codebook_indices) -> None:
+    def _update(self, B: int, pool, logits, codebook_indices, spatial=None) -> None:
         """Every check first, then the device work."""
         if B < 1:
             raise ValueError("empty batch")
@@ -300,13 +398,29 @@ class GeneratorEvaluator:
                 raise ValueError(f"{what} of {tuple(x.shape)} for a batch of {B}")
         if self._enable_fid and self._fid_real_mu is not None and int(pool.shape[1]) != self._fid_real_mu.numel():
             raise ValueError(f"features have {int(pool.shape[1])} columns, the real statistics {self._fid_real_mu.numel()}")
+        if self._pr_reference is not None and int(pool.shape[1]) != int(self._pr_reference.shape[1]):
+            raise ValueError(f"features have {int(pool.shape[1])} columns, the reference features of use_precision_recall {int(self._pr_reference.shape[1])}")
+        if self._sfid_real_mu is not None:
+            if spatial is None:
+                raise ValueError("use_spatial_statistics() is attached: spatial features [B, S] are required (update_features_spatial, or an "
+                                 "extractor that returns 'spatial')")
+            if _check_rows(spatial, "spatial features", self._sfid.width if self._sfid else None)[0] != B:
+                raise ValueError(f"spatial features of {tuple(spatial.shape)} for a batch of {B}")
+            if int(spatial.shape[1]) != self._sfid_real_mu.numel():
+                raise ValueError(f"spatial features have {int(spatial.shape[1])} columns, the real spatial statistics {self._sfid_real_mu.numel()}")
         self._check_indices(codebook_indices)
         dev = self._bind_device()
+        if self._sfid_real_mu is not None and self._sfid is None:
+            self._sfid = FeatureStatistics(dev)
         self._num_examples += B
         self._num_updates += 1
         with torch.cuda.device(dev):
             if self._enable_fid:
                 self._fid.add(pool)
+                if self._pr_reference is not None:
+                    self._collect(pool, dev)
+            if self._sfid is not None:
+                self._sfid.add(spatial)
             if self._enable_inception_score:
                 self._is.add(logits)
             if self._codebook:
@@ -326,6 +440,12 @@ class GeneratorEvaluator:
             raise ValueError("no FID statistics: enable_fid and at least one update are needed")
         return self._num_examples, self._fid.total.clone(), self._fid.full_sigma()
 
+    def spatial_statistics(self) -> Tuple[int, torch.Tensor, torch.Tensor]:
+        """``fid_statistics()`` of the spatial features behind sFID: ``(n, total [S], sigma [S, S])``."""
+        if self._sfid is None or self._sfid.width is None:
+            raise ValueError("no spatial statistics: use_spatial_statistics() and at least one update are needed")
+        return self._num_examples, self._sfid.total.clone(), self._sfid.full_sigma()
+
     def is_statistics(self) -> Tuple[int, torch.Tensor, torch.Tensor]:
         """``(n, prob_total [C], kl_total [C])`` as float64 device tensors."""
         if not self._enable_inception_score or self._is is None or self._is.width is None:
@@ -335,12 +455,16 @@ class GeneratorEvaluator:
     def result(self) -> Mapping[Text, Union[float, torch.Tensor]]:
         """Keys, order and types of evaluator.py:579-641: Python floats, except ``CodebookEntropy``, a 0-d float64 tensor on the evaluator's
         device.  One device-to-host copy of the state.  ``RuntimeError`` for FID without real statistics -- ``result()`` of an evaluator without
-        ``enable_fid`` reports the rest; ``IndexError`` if an index fell outside [0, num_codebook_entries)."""
+        ``enable_fid`` reports the rest; ``IndexError`` if an index fell outside [0, num_codebook_entries).  After them, when attached: ``sFID``
+        (``use_spatial_statistics``; a second copy of its S x S state), ``Precision`` and ``Recall`` (``use_precision_recall``; two counts)."""
         if self._num_examples < 1:
             raise ValueError("No examples to evaluate.")
         if self._enable_fid and self._fid_real_mu is None:
             raise RuntimeError("FID needs the real statistics: use_inception(extractor, real_statistics=(mu, sigma) or an .npz path). "
                                "fid_statistics(), the Inception score and the codebook figures do not (construct without enable_fid).")
+        if self._pr_reference is not None and self._pr_count < self._pr_k + 1:
+            raise ValueError(f"Precision / Recall with k = {self._pr_k} need at least {self._pr_k + 1} samples, {self._pr_count} were collected "
+                             "(rows are collected from use_precision_recall() on)")
         n = self._num_examples
         parts, entropy = [], None
         if self._enable_fid:
@@ -370,4 +494,11 @@ class GeneratorEvaluator:
             eval_score["CodebookUsage"] = float(int(host[-2])) / self._num_codebook_entries
         if self._enable_codebook_entropy_measure:
             eval_score["CodebookEntropy"] = entropy
+        if self._sfid is not None:                         # its own copy: 2023^2 doubles, kept out of the state above so that its layout stands
+            total_s, sigma_s = self._sfid.total.cpu(), self._sfid.full_sigma().cpu()
+            eval_score["sFID"] = frechet_distance(self._sfid_real_mu, self._sfid_real_sigma, total_s / n, get_covariance(sigma_s, total_s, n))
+        if self._pr_reference is not None:
+            with torch.cuda.device(self._device):
+                self._pr_reference = self._pr_reference.to(self._device)
+                eval_score["Precision"], eval_score["Recall"] = precision_recall(self._pr_reference, self._pr_rows[:self._pr_count], self._pr_k)
         return eval_score

@@ -11,7 +11,9 @@ the file (or a state dict with its keys) over once.  A forward before that raise
 NOT been compared against the real thing: tests hold it to a float64 restatement of that specification on seeded weights.
 
 ``forward`` takes uint8 ``[B, 3, H, W]`` of any H, W >= 2 (resized to 299 x 299 inside the input kernel) and returns the keys of ``features_list``
-(``'64'``, ``'192'``, ``'768'``, ``'2048'``, ``'logits_unbiased'``, ``'logits'``).  Activations are fp16 with fp32 accumulation where the reference runs
+(``'64'``, ``'192'``, ``'768'``, ``'2048'``, ``'logits_unbiased'``, ``'logits'``, and ``'spatial'``: fp32 ``[B, 2023]``, the first 7 channels of
+``Mixed_6d.branch1x1`` after BatchNorm and ReLU on the 17 x 17 map in (h, w, c) order -- ADM's sFID tap ``mixed_6/conv:0``[..., :7] as far as it can
+be told without the TensorFlow graph, DESIGN.md "sFID").  Activations are fp16 with fp32 accumulation where the reference runs
 float64; what that costs is stated in DESIGN.md "Precision" and measured in profiles/inception.md.  A row is bitwise independent of the batch it
 sits in and of the chunking.  There is no CPU path.
 """
@@ -29,8 +31,10 @@ from .synth import INCEPTION_FC, inception_convs
 
 WEIGHTS_FILE = "pt_inception-2015-12-05-6726825d.pth"
 WEIGHTS_ENV = "MASKBIT_INCEPTION_WEIGHTS"
-FEATURE_KEYS = ("64", "192", "768", "2048", "logits_unbiased", "logits")
-FEATURE_WIDTH = {"64": 64, "192": 192, "768": 768, "2048": 2048, "logits_unbiased": INCEPTION_FC[0], "logits": INCEPTION_FC[0]}
+FEATURE_KEYS = ("64", "192", "768", "2048", "logits_unbiased", "logits", "spatial")
+SPATIAL_WIDTH = 17 * 17 * 7              # the sFID tap: Mixed_6d.branch1x1[..., :7] on the 17 x 17 map, (h, w, c) order
+FEATURE_WIDTH = {"64": 64, "192": 192, "768": 768, "2048": 2048, "logits_unbiased": INCEPTION_FC[0], "logits": INCEPTION_FC[0],
+                 "spatial": SPATIAL_WIDTH}
 DEFAULT_FEATURES = ("2048", "logits_unbiased")
 StateLike = Union[str, os.PathLike, Mapping[str, torch.Tensor]]
 _BN = ("weight", "bias", "running_mean", "running_var")
@@ -130,16 +134,22 @@ class InceptionV3(BaseModel):
         h = self.engine(chunk)
         out = {k: torch.empty(B, FEATURE_WIDTH[k], dtype=torch.float32, device=dev) for k in self.features_list}
         lib = _lib.load()
-        spatial = any(k in out for k in ("64", "192", "768"))
+        taps = any(k in out for k in ("64", "192", "768"))
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
             for b0 in range(0, B, chunk):
                 n = min(chunk, B - b0)
                 ptr = {k: (out[k][b0:b0 + n].data_ptr() if k in out else None) for k in FEATURE_KEYS}
                 src = x[b0:b0 + n].data_ptr()
-                if spatial:
+                if taps:
                     _lib.check(lib.mb_inception_taps(h, src, n, H, W, None, None, None, None, ptr["64"], ptr["192"], ptr["768"], ptr["2048"],
                                                      ptr["logits_unbiased"], ptr["logits"], stream), "mb_inception_taps")
+                    if "spatial" in out:   # the pooled taps and the spatial one together: a second pass for the latter alone
+                        _lib.check(lib.mb_inception_forward_spatial(h, src, n, H, W, ptr["spatial"], None, None, None, stream),
+                                   "mb_inception_forward_spatial")
+                elif "spatial" in out:
+                    _lib.check(lib.mb_inception_forward_spatial(h, src, n, H, W, ptr["spatial"], ptr["2048"], ptr["logits_unbiased"], ptr["logits"],
+                                                                stream), "mb_inception_forward_spatial")
                 else:
                     _lib.check(lib.mb_inception_forward(h, src, n, H, W, ptr["2048"], ptr["logits_unbiased"], ptr["logits"], stream), "mb_inception_forward")
         return out
