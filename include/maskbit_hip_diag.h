@@ -1,7 +1,8 @@
 /* libmaskbit_hip.so -- DIAGNOSTIC entry points: single kernels of the engine on caller buffers, for the unit tests (tests/test_hip_gemm.py,
  * test_hip_pair.py, test_hip_conv.py; the row kernels -- mb_layernorm, mb_layernorm_f4_seq, mb_layernorm_pair, mb_pairify, mb_embed_ln, mb_embed_pair --
- * in test_hip_rows.py) and the tools under tools/.  Nothing here is part of the reference's surface and no host binding of the product needs it:
- * include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered, 0 / negative return, mb_last_error()).
+ * in test_hip_rows.py; the quantizer kernels in test_hip_quantizer.py) and the tools under tools/.  Nothing here is part of the reference's
+ * surface and no host binding of the product needs it: include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered,
+ * 0 / negative return, mb_last_error()).
  */
 #ifndef MASKBIT_HIP_DIAG_H
 #define MASKBIT_HIP_DIAG_H
@@ -157,6 +158,30 @@ int mb_seeded_noise(const int64_t* seeds, int step, float randomize_temperature,
  * idx int64 [N] = argmin_j ||z - e_j||^2 (ties to the lowest index), dist fp32 [N] (may be NULL) = that squared distance; splits = codebook splits
  * across workgroups (0 = automatic; clamped to [1, min(64, C / 64 rounded up)]). */
 int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream);
+
+/* ---- the quantizer kernels one launch sequence at a time (vq.hip; lfq_kernel, latent_kernel, pack_image_kernel of conv.hip), each through the
+ * product's own launchers on stream-ordered temporaries (tests/test_hip_quantizer.py).  Refused (-1, nothing launched): a NULL required pointer, a
+ * size <= 0, a shape outside what is stated.
+ * mb_vq_encode_rows: the lookup encode as mb_enc_encode_vq runs it after the encoder -- vq_prep_codebook, vq_prep_rows, vq_search -- over N = B * HW
+ * rows.  Exactly one of z_h16 (fp16 rows of K values at a row stride of stride16 >= K elements; the elements beyond K are never read) and z_f32
+ * (fp32 [N, K]) is non-NULL.  codebook fp32 [C, K], 2 <= C <= 65 536, 1 <= K <= 256, N <= 2^24; l2, splits as for mb_vq_argmin.  Outputs, each may be NULL:
+ * idx int64 [N], dist fp32 [N], zq_nchw fp32 [B, K, HW] = the chosen (prepared) codebook rows, zraw_nchw fp32 [B, K, HW] = the rows as given. */
+int mb_vq_encode_rows(const void* z_h16, int stride16, const float* z_f32, const float* codebook, int B, int HW, int C, int K, int l2, int splits,
+                      int64_t* idx, float* zq_nchw, float* zraw_nchw, float* dist, mb_stream stream);
+/* vq_prep_codebook + vq_gather: codes int64 [npix] (clamped to [0, C)) -> out_h16 fp16 [npix, cin_pad], channels >= K zero; cin_pad >= K a multiple
+ * of 64; *sat (device, required) += stored elements beyond +-65504 (stored as +-65504). */
+int mb_vq_gather(const int64_t* codes, const float* codebook, int64_t npix, int C, int K, int l2, int cin_pad, void* out_h16, unsigned* sat,
+                 mb_stream stream);
+/* vq_pack_latent: z_nchw fp32 [B, K, HW] -> out_h16 fp16 [B * HW, cin_pad], K in [1, 256], cin_pad and *sat as for mb_vq_gather. */
+int mb_vq_pack_latent(const float* z_nchw, int B, int K, int HW, int cin_pad, void* out_h16, unsigned* sat, mb_stream stream);
+/* launch_lfq: z_h16 fp16 [B * HW, Kp] (Kp >= K; columns >= K are never read), K in [1, 64] -> idx int64 [B * HW] (required), bit j = (z_j > 0), LSB
+ * first (K = 64: bit 63 is the sign bit of the int64); zq_nchw / zraw_nchw fp32 [B, K, HW] (each may be NULL) = +-1 / the values as given. */
+int mb_lfq_pack(const void* z_h16, int B, int HW, int K, int Kp, int64_t* idx, float* zq_nchw, float* zraw_nchw, mb_stream stream);
+/* launch_latent: tokens int64 [npix], K in [1, 64] -> out_h16 fp16 [npix, 64]: channel j < K = +1 if bit j of the token is set, else -1; 0 beyond. */
+int mb_lfq_latent(const int64_t* tokens, int64_t npix, int K, void* out_h16, mb_stream stream);
+/* launch_pack_image: img_nchw fp32 [B, C, H, W], C in [1, 4] (what the tokenizer handle accepts) -> out_h16 fp16 [B * H * W, 64], channels < C the
+ * saturating fp16 of the image, 0 beyond. */
+int mb_pack_image(const float* img_nchw, int B, int C, int H, int W, void* out_h16, mb_stream stream);
 
 /* ---- single tokenizer layers (conv.hip) on caller buffers, through the handle's own launch_conv / launch_gn / weight repack on a scratch
  * context.  These four synchronise the stream.

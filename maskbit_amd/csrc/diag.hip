@@ -4,6 +4,8 @@
 // (mb_gen_set_alo, the one entry of that header that needs the generator handle's members, is in engine.hip.)
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
 #include "mb_conv.h"
@@ -42,6 +44,31 @@ int pool_entry(const char* what, decltype(mb::launch_s2d)* launch, const void* x
   launch((hipStream_t)stream, (const h16*)x, (h16*)y, B, H, W, C);
   return launched();
 }
+
+// The quantizer entries: the shapes mb_dec_create_vq / vq_argmin accept, the codebook descriptor the handle fills, and temporaries that are
+// allocated and freed in stream order (no synchronisation: a free waits for the launches queued before it).
+bool vq_shape_ok(int C, int K) { return C >= 2 && C <= 65536 && K >= 1 && K <= 256; }
+mb::VqCodebook vq_shape(int C, int K, int l2) {
+  mb::VqCodebook q;
+  q.C = C; q.K = K; q.Kp = mb::vq_kp(K); q.Cpad = mb::vq_cpad(C); q.l2 = l2 ? 1 : 0;
+  return q;
+}
+struct StreamTemps {
+  explicit StreamTemps(hipStream_t stream) : s(stream) {}
+  StreamTemps(const StreamTemps&) = delete;
+  StreamTemps& operator=(const StreamTemps&) = delete;
+  ~StreamTemps() { for (void* p : owned) (void)hipFreeAsync(p, s); }
+  template <class T>
+  void get(T** out, size_t n) {
+    void* p = nullptr;
+    *out = nullptr;
+    if (ok && hipMallocAsync(&p, n * sizeof(T), s) == hipSuccess) { owned.push_back(p); *out = (T*)p; }
+    else ok = false;
+  }
+  hipStream_t s;
+  std::vector<void*> owned;
+  bool ok = true;
+};
 
 // The optional e2m1 outputs of a row kernel (values x4 / x4_scale, fp16 lo halves xl4 / xl4_scale) over `rows` rows of `seq_rows` each, the class
 // token last: the vector kernels alone write them (d = 768 / 1024), and the lane-ordered scale arrays hold whole 64-token groups.
@@ -312,6 +339,72 @@ int mb_seeded_noise(const int64_t* seeds, int step, float randomize_temperature,
 int mb_vq_argmin(const float* z, const float* codebook, int N, int C, int K, int l2, int splits, int64_t* idx, float* dist, mb_stream stream) {
   if (!z || !codebook || !idx) return fail(-1, "mb_vq_argmin: null argument");
   if (int rc = mb::vq_argmin(z, codebook, N, C, K, l2, splits, idx, dist, (hipStream_t)stream)) return rc;
+  return launched();
+}
+
+// ---- the quantizer kernels (vq.hip; lfq / latent / pack_image of conv.hip) through the launchers the tokenizer handle calls, in its order ----
+int mb_vq_encode_rows(const void* z_h16, int stride16, const float* z_f32, const float* codebook, int B, int HW, int C, int K, int l2, int splits,
+                      int64_t* idx, float* zq_nchw, float* zraw_nchw, float* dist, mb_stream stream) {
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
+  if (!codebook || (z_h16 != nullptr) == (z_f32 != nullptr)) return fail(-1, "mb_vq_encode_rows: a codebook and exactly one of z_h16 / z_f32 required");
+  if (!vq_shape_ok(C, K)) return fail(-1, "mb_vq_encode_rows: C in [2, 65536], K in [1, 256] required");
+  if (B < 1 || HW < 1 || (int64_t)B * HW > (1 << 24)) return fail(-1, "mb_vq_encode_rows: B >= 1, HW >= 1, B * HW <= 2^24 required");
+  if (z_h16 && stride16 < K) return fail(-1, "mb_vq_encode_rows: stride16 = %d is below K = %d", stride16, K);
+  const int N = B * HW, Npad = vq_npad(N);
+  VqCodebook q = vq_shape(C, K, l2);
+  splits = vq_splits(q, N, splits);
+  StreamTemps t(s);
+  float *zT = nullptr, *ps = nullptr;
+  int* pi = nullptr;
+  t.get(&q.cb, (size_t)C * K); t.get(&q.cbT, (size_t)q.Kp * q.Cpad); t.get(&q.cbn, (size_t)q.Cpad);
+  t.get(&zT, (size_t)q.Kp * Npad); t.get(&ps, (size_t)splits * Npad); t.get(&pi, (size_t)splits * Npad);
+  if (!t.ok) return fail(-10, "mb_vq_encode_rows: device allocation failed");
+  vq_prep_codebook(q, codebook, s);
+  vq_prep_rows(q, (const h16*)z_h16, stride16, z_f32, N, HW, zT, zraw_nchw, s);
+  vq_search(q, zT, N, HW, splits, ps, pi, idx, zq_nchw, dist, s);
+  return launched();
+}
+int mb_vq_gather(const int64_t* codes, const float* codebook, int64_t npix, int C, int K, int l2, int cin_pad, void* out_h16, unsigned* sat,
+                 mb_stream stream) {
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
+  if (!codes || !codebook || !out_h16 || !sat) return fail(-1, "mb_vq_gather: null argument");
+  if (!vq_shape_ok(C, K)) return fail(-1, "mb_vq_gather: C in [2, 65536], K in [1, 256] required");
+  if (npix < 1 || npix > (1 << 24)) return fail(-1, "mb_vq_gather: npix in [1, 2^24] required");
+  if (cin_pad < K || cin_pad % CK) return fail(-1, "mb_vq_gather: cin_pad = %d must be a multiple of 64 and at least K = %d", cin_pad, K);
+  VqCodebook q = vq_shape(C, K, l2);
+  StreamTemps t(s);
+  t.get(&q.cb, (size_t)C * K); t.get(&q.cbT, (size_t)q.Kp * q.Cpad); t.get(&q.cbn, (size_t)q.Cpad);
+  if (!t.ok) return fail(-10, "mb_vq_gather: device allocation failed");
+  vq_prep_codebook(q, codebook, s);
+  vq_gather(q, codes, (size_t)npix, (h16*)out_h16, cin_pad, sat, s);
+  return launched();
+}
+int mb_vq_pack_latent(const float* z_nchw, int B, int K, int HW, int cin_pad, void* out_h16, unsigned* sat, mb_stream stream) {
+  if (!z_nchw || !out_h16 || !sat) return fail(-1, "mb_vq_pack_latent: null argument");
+  if (B < 1 || HW < 1 || (int64_t)B * HW > (1 << 24) || K < 1 || K > 256) return fail(-1, "mb_vq_pack_latent: B >= 1, HW >= 1, B * HW <= 2^24, K in [1, 256] required");
+  if (cin_pad < K || cin_pad % mb::CK) return fail(-1, "mb_vq_pack_latent: cin_pad = %d must be a multiple of 64 and at least K = %d", cin_pad, K);
+  mb::vq_pack_latent(z_nchw, B, K, HW, (h16*)out_h16, cin_pad, sat, (hipStream_t)stream);
+  return launched();
+}
+int mb_lfq_pack(const void* z_h16, int B, int HW, int K, int Kp, int64_t* idx, float* zq_nchw, float* zraw_nchw, mb_stream stream) {
+  if (!z_h16 || !idx) return fail(-1, "mb_lfq_pack: null argument");
+  if (B < 1 || HW < 1 || (int64_t)B * HW > (1 << 24)) return fail(-1, "mb_lfq_pack: B >= 1, HW >= 1, B * HW <= 2^24 required");
+  if (K < 1 || K > mb::CK || Kp < K) return fail(-1, "mb_lfq_pack: K in [1, 64] and Kp >= K required");
+  mb::launch_lfq((hipStream_t)stream, (const h16*)z_h16, idx, zq_nchw, zraw_nchw, B, HW, K, Kp);
+  return launched();
+}
+int mb_lfq_latent(const int64_t* tokens, int64_t npix, int K, void* out_h16, mb_stream stream) {
+  if (!tokens || !out_h16) return fail(-1, "mb_lfq_latent: null argument");
+  if (npix < 1 || npix > (1 << 24) || K < 1 || K > mb::CK) return fail(-1, "mb_lfq_latent: npix in [1, 2^24] and K in [1, 64] required");
+  mb::launch_latent((hipStream_t)stream, tokens, (h16*)out_h16, (size_t)npix, K);
+  return launched();
+}
+int mb_pack_image(const float* img_nchw, int B, int C, int H, int W, void* out_h16, mb_stream stream) {
+  if (!img_nchw || !out_h16) return fail(-1, "mb_pack_image: null argument");
+  if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (1 << 24) || C < 1 || C > 4) return fail(-1, "mb_pack_image: B, H, W >= 1, B * H * W <= 2^24, C in [1, 4] required");
+  mb::launch_pack_image((hipStream_t)stream, img_nchw, (h16*)out_h16, B, C, H, W);
   return launched();
 }
 

@@ -4,6 +4,7 @@ layout, determinism, and sample() / generate_uint8() with the embedding-table Be
 import pytest
 import torch
 
+import quantizer_reference as QR
 from conftest import load_golden
 from hip_helpers import Cfg
 from oracle import maskbit_oracle as O
@@ -30,14 +31,18 @@ def fp64_dist(z, cb, l2):
     return torch.cdist(zd, e).pow(2), zd, e
 
 
-@pytest.mark.parametrize("CK", [(4096, 64), (1024, 256), (1000, 48)])
+@pytest.mark.parametrize("CK", [(4096, 64), (1024, 256), (1000, 48), *QR.ARGMIN_L2_ADDED])
 @pytest.mark.parametrize("l2", [False, True])
 def test_argmin_exact_vs_fp64(CK, l2):
     Cn, K = CK
     g = torch.Generator(device=DEV).manual_seed(Cn + K + int(l2))
-    cb = torch.randn(Cn, K, device=DEV, generator=g)
+    if CK in QR.ARGMIN_L2_ADDED:      # 64 < K <= 128, the Kp = 128 search; CPU-seeded: tests/test_quantizer_cpu.py computes the clear-row share of these
+        cb, rows = QR.argmin_inputs(Cn, K, l2)
+        cb = cb.to(DEV)
+    else:
+        cb, rows = torch.randn(Cn, K, device=DEV, generator=g), None
     for N in (1, 255, 16401):
-        z = torch.randn(N, K, device=DEV, generator=g) * 1.1 + 0.05
+        z = rows[N].to(DEV) if rows else torch.randn(N, K, device=DEV, generator=g) * 1.1 + 0.05
         idx, dist = vq_argmin(z, cb, l2)
         d, zd, e = fp64_dist(z, cb, l2)
         top2 = d.topk(2, dim=1, largest=False)

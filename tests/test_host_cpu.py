@@ -21,7 +21,10 @@ def test_library_exports_every_declared_symbol():
     from maskbit_amd import _lib
     abi = open(os.path.join(ROOT, "include", "maskbit_hip.h")).read()
     header = abi + open(os.path.join(ROOT, "include", "maskbit_hip_diag.h")).read()
-    assert not re.findall(r"\b(mb_gemm[a-z0-9_]*|mb_layernorm[a-z0-9_]*|mb_w4[a-z0-9_]*|mb_set_cu_count|mb_conv[a-z0-9_]*|mb_groupnorm[a-z0-9_]*|mb_avgpool[a-z0-9_]*|mb_s2d[a-z0-9_]*|mb_embed[a-z0-9_]*|mb_pairify[a-z0-9_]*|mb_cast[a-z0-9_]*|mb_split[a-z0-9_]*)\s*\(", abi)
+    assert not re.findall(r"\b(mb_gemm[a-z0-9_]*|mb_layernorm[a-z0-9_]*|mb_w4[a-z0-9_]*|mb_set_cu_count|mb_conv[a-z0-9_]*|mb_groupnorm[a-z0-9_]*|mb_avgpool[a-z0-9_]*|mb_s2d[a-z0-9_]*|mb_embed[a-z0-9_]*|mb_pairify[a-z0-9_]*|mb_cast[a-z0-9_]*|mb_split[a-z0-9_]*|mb_vq_[a-z0-9_]*|mb_lfq_[a-z0-9_]*|mb_pack_image[a-z0-9_]*)\s*\(", abi)
+    diag = header[len(abi):]
+    for name in ("mb_vq_argmin", "mb_vq_encode_rows", "mb_vq_gather", "mb_vq_pack_latent", "mb_lfq_pack", "mb_lfq_latent", "mb_pack_image"):
+        assert re.search(r"\b%s\s*\(" % name, diag) and name in _lib.SIGNATURES, name
     declared = set(re.findall(r"\b(mb_[a-z0-9_]+)\s*\(", header))
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     lib = _lib.load()
