@@ -260,6 +260,53 @@ int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64
                      float randomize_temperature, const float* conf_weight, int64_t* step_tokens, int64_t* tokens_out,
                      float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
 
+/* ---- per-sample sampling arguments: mixed requests in one seeded batch ---------------------------------------------------------------------- *
+ * A seeded run whose B samples ("requests") each bring their own num_steps N_b, guidance scale and annealing, temperatures and mask schedule, next
+ * to their own seed, label and (optionally) start tokens.  The step kernels read their constants per sample from a device table instead of from
+ * kernel arguments; the noise definition and the threshold rule are those of the seeded section above, unchanged.
+ *
+ * SEMANTICS
+ *   - The run lasts S = max_b N_b global steps.  Request b is RIGHT-ALIGNED: it is inactive while t < S - N_b, and at global step t it executes its
+ *     own local step i = t - (S - N_b).  All requests finish at t = S - 1; one combine and one decode serve the whole batch.
+ *   - Noise counter (step), conf_weight, scale, temperature and mask ratio of request b at global step t are those of local step i of an N_b-step
+ *     run.  Consequence: a request's tokens are exactly what it would produce alone.
+ *   - The caller orders the requests by N_b descending, so the active set at step t is a prefix [0, active[t]) and active[] is non-decreasing, with
+ *     active[S - 1] = B.  At step t the forward, the step kernels and the writes to step_tokens cover that prefix only: inactive samples are
+ *     untouched.  Both token buffers of the engine are initialised with the start state (all masked, or init_tokens) at step 0, so an inactive
+ *     sample needs no copy while the buffers ping-pong.  Cost: sum_b N_b sequence-forwards instead of B * S.
+ *   - use_guidance is ONE flag for the run.  In a guided run EVERY step runs the guided forward, also where all active scales are 0: what a request
+ *     sees must not depend on its neighbours' schedules, and at precision 4 the guided forward is not the plain forward bit for bit.  A request
+ *     with scale 0 in a guided run gets c + 0 * (c - u).  So a request's result is a function of (its own fields, use_guidance) and nothing else.
+ *     THIS DIFFERS from mb_sample_seeded, which runs the plain forward on zero-scale steps below precision 4: a requests run equals a seeded run
+ *     of the same settings where both run the same forwards (no zero-scale step in a guided run, or no guidance at all).
+ *   - Threshold rule: the per-sample rule of the edit and seeded steps.
+ * One record per (global step, position in the batch); an inactive record has step = -1 and is never read. */
+typedef struct {
+  float scale;                   /* annealed guidance scale of the request's local step */
+  float temperature;             /* softmax temperature of that step */
+  float mask_ratio;              /* float32 masking ratio of that step */
+  float randomize_temperature;
+  float conf_weight;             /* float32(1 - (i + 1) / N_b) */
+  int32_t step;                  /* local step i = the noise counter; -1: inactive */
+} mb_request_step;
+typedef struct {
+  int num_steps;                 /* S */
+  int use_guidance;
+  const int* active;             /* HOST [S]: the active prefix per global step */
+  const mb_request_step* table;  /* DEVICE [S, B] */
+} mb_request_plan;
+/* mb_sample_step_seeded with the constants of sample b read from table_row[b] (device [B]: one row of the table). */
+int mb_sample_step_requests(const float* logits_c, const float* logits_u, const mb_request_step* table_row, const int64_t* seeds,
+                            const int32_t* num_regen, const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out,
+                            int B, int n, int m, int C, mb_stream stream);
+/* The whole run, one call (no step chunks: there is no noise tensor to bound).  labels, seeds, init_tokens (may be NULL = every slot masked) in the
+ * descending-N_b order of the plan.  step_tokens int64 [S, B, n, m] (may be NULL): only the active (t, b) are written.  tokens_out, images: as in
+ * mb_sample.  The call ends any run in progress on the handle: a step chunk of another kind does not continue it.  Refused before any launch: null
+ * arguments; active[] not non-decreasing or outside [1, B]; active[S - 1] != B; an image without a decoder; 2 B (guided) or B sequences beyond the
+ * engine's. */
+int mb_sample_requests(mb_gen* g, mb_dec* d, const mb_request_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens,
+                       const int64_t* seeds, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
+
 /* ---- tokenizer evaluation: TokenizerEvaluator.update, evaluator/evaluator.py:262-375 (scripts/eval_tokenizer.py:137-149) ---------------- *
  * Stateless: the caller owns every buffer (and zeroes its running state once); nothing is allocated, nothing synchronises.
  * Bytes of workspace mb_eval_images needs for this shape (one slot of three doubles per 32 x 32 tile of every image plane); 0 for a shape it

@@ -35,6 +35,16 @@ class EditPlan(C.Structure):
                 ("temperature", C.POINTER(C.c_float)), ("mask_ratio", C.POINTER(C.c_float)), ("step_begin", C.c_int), ("step_end", C.c_int)]
 
 
+class RequestStep(C.Structure):
+    """mb_request_step: the constants of one request at one global step (24 bytes; ``step`` = -1: inactive)."""
+    _fields_ = [("scale", C.c_float), ("temperature", C.c_float), ("mask_ratio", C.c_float), ("randomize_temperature", C.c_float),
+                ("conf_weight", C.c_float), ("step", C.c_int32)]
+
+
+class RequestPlan(C.Structure):
+    _fields_ = [("num_steps", C.c_int), ("use_guidance", C.c_int), ("active", C.POINTER(C.c_int)), ("table", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/maskbit_hip.h (the ABI) and include/maskbit_hip_diag.h (single-kernel test entries) declare
 SIGNATURES = {
     "mb_gen_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
@@ -75,6 +85,10 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_sample_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EditPlan), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                    C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_sample_step_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mb_sample_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RequestPlan), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_seeded_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p]),
     "mb_edit_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -702,7 +702,7 @@ static int sample_step_checked(const char* who, const mb::StepArgs& a, const int
   if (!a.logits_c || (!a.seeds && (!a.exp_noise || !a.conf_noise)) || !tokens_in || !a.tokens) return fail(-1, "%s: null argument", who);
   if (tokens_in == a.tokens) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
   if (a.B <= 0 || a.P <= 0 || a.C <= 0) return fail(-1, "%s: bad sizes", who);
-  ProfScope p(a.seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", s);
+  ProfScope p(a.req ? "sample_step_requests" : a.seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", s);
   if (mb::sample_step(s, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, a.C, a.P);
   return launched();
 }
@@ -741,6 +741,19 @@ int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float sc
   a.seeds = seeds; a.step = step; a.rand_temp = randomize_temperature; a.conf_w = conf_weight;
   a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
   return sample_step_checked("mb_sample_step_seeded", a, tokens_in, num_regen, mask_ratio, (hipStream_t)stream);
+}
+
+static_assert(sizeof(mb::RequestStep) == sizeof(mb_request_step) && sizeof(mb_request_step) == 24, "mb_request_step is the kernels' RequestStep");
+
+int mb_sample_step_requests(const float* logits_c, const float* logits_u, const mb_request_step* table_row, const int64_t* seeds, const int32_t* num_regen,
+                            const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
+  if (!table_row || !seeds || !num_regen) return fail(-1, "mb_sample_step_requests: null argument");
+  if (pred_out && (pred_out == tokens_out || pred_out == tokens_in)) return fail(-1, "mb_sample_step_requests: pred_out must not alias tokens_in or tokens_out");
+  mb::StepArgs a{};
+  a.logits_c = logits_c; a.logits_u = logits_u;
+  a.seeds = seeds; a.req = (const mb::RequestStep*)table_row;
+  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
+  return sample_step_checked("mb_sample_step_requests", a, tokens_in, num_regen, 0.f, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -866,9 +879,87 @@ int sample_run(mb_gen* g, mb_dec* d, const RunSpec& r, const int64_t* labels, in
   return launched();
 }
 
+// The fourth kind of run, "requests" (include/maskbit_hip.h "per-sample sampling arguments"): a seeded run whose step t covers the prefix
+// [0, active[t]) of the batch and whose step kernels read their constants per sample from plan.table.  A sibling of sample_run that shares its pieces --
+// the start state, the two forwards, the checked step, combine and decode -- and has none of its step chunks.  Every argument check is in front of the
+// first launch, those that need no handle in front of the handle's own (the entry is refused the same way with or without a device).
+int sample_requests_run(mb_gen* g, mb_dec* d, const mb_request_plan& plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
+                        const RunOut& out, hipStream_t s) {
+  const char* who = "mb_sample_requests";
+  const int S = plan.num_steps;
+  if (!plan.active || !plan.table || !labels || !seeds) return fail(-1, "%s: null argument", who);
+  if (S <= 0 || B <= 0) return fail(-1, "%s: bad sizes (num_steps = %d, B = %d)", who, S, B);
+  for (int t = 0; t < S; ++t) {
+    if (plan.active[t] < 1 || plan.active[t] > B) return fail(-1, "%s: active[%d] = %d outside [1, %d]", who, t, plan.active[t], B);
+    if (t && plan.active[t] < plan.active[t - 1])
+      return fail(-1, "%s: active[] is not non-decreasing (active[%d] = %d after %d): order the requests by num_steps descending", who, t, plan.active[t], plan.active[t - 1]);
+  }
+  if (plan.active[S - 1] != B) return fail(-1, "%s: active[%d] = %d, but all %d requests run the last step", who, S - 1, plan.active[S - 1], B);
+  if (!d && (out.img_nchw || out.img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
+  if (!g) return fail(-1, "%s: null argument (no generator handle)", who);
+  const bool guided = plan.use_guidance != 0;
+  const int nbf = guided ? 2 * B : B;
+  if (nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
+  const mb_gen_cfg& c = g->c;
+  const int n = c.seq, m = c.splits, C = g->C;
+  const size_t P = (size_t)n * m;
+  mb_gen::Run& run = g->run;
+  run.next = -1;                                       // ends any run in progress: no chunk of another kind continues this one
+  // The start state in BOTH token buffers: a request that becomes active at step t reads whichever buffer is `cur` then, and nothing has touched its rows
+  if (init_tokens) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);
+  else {
+    mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
+    mb::edit_load_tokens(s, g->tok_a, nullptr, g->num_regen, B, (int)P, C);
+  }
+  HIP_TRY(hipMemcpyAsync(g->tok_b, g->tok_a, (size_t)B * P * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  int64_t* cur = g->tok_a;
+  int64_t* nxt = g->tok_b;
+  int64_t* last_pred = g->pred;
+  struct CfgReady { mb_gen::Run& run; ~CfgReady() { run.cfg_labels = nullptr; } } cfg_ready{run};
+  run.cfg_labels = nullptr;
+  mb::StepArgs a{};
+  a.logits_c = g->logits; a.P = (int)P; a.C = C;
+  a.seeds = seeds;
+  for (int t = 0; t < S; ++t) {
+    const int Bt = plan.active[t];
+    int rc;
+    // The forward is chosen by the run's flag alone, never by the scales of the step: a request with scale 0 gets c + 0 (c - u) from the guided forward
+    if (guided) {
+      rc = gen_forward_cfg(g, cur, labels, g->logits, Bt, s);
+      a.logits_u = g->logits + (size_t)Bt * P * C;
+      if (Bt <= g->chunk_seqs / 2) { run.cfg_labels = labels; run.cfg_B = Bt; }   // valid until the prefix grows: gen_forward_cfg then refreshes lab_cfg / drop_cfg
+      else run.cfg_labels = nullptr;
+    } else {
+      rc = gen_forward(g, cur, labels, nullptr, g->logits, Bt, s);
+      a.logits_u = nullptr;
+    }
+    if (rc) return rc;
+    a.B = Bt;
+    a.req = (const mb::RequestStep*)plan.table + (size_t)t * B;
+    a.tokens = nxt; a.pred = out.step_tokens ? out.step_tokens + (size_t)t * B * P : g->pred;
+    rc = sample_step_checked(who, a, cur, g->num_regen, 0.f, s);
+    if (rc) return rc;
+    last_pred = a.pred;                                // (the last step runs all B requests: its predictions are the whole batch's)
+    int64_t* tmp = cur; cur = nxt; nxt = tmp;
+  }
+  int64_t* codes = out.codes ? out.codes : g->codes;
+  mb::combine_groups(s, last_pred, codes, (size_t)B * n, m, g->gbits);
+  if (d) {
+    int rc = mb_dec_decode(d, codes, out.img_nchw, out.img_nhwc_u8, B, (mb_stream)s);
+    if (rc) return rc;
+  }
+  return launched();
+}
+
 }  // namespace
 
 extern "C" {
+
+int mb_sample_requests(mb_gen* g, mb_dec* d, const mb_request_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
+                       int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
+  if (!plan) return fail(-1, "mb_sample_requests: null argument");
+  return sample_requests_run(g, d, *plan, labels, B, init_tokens, seeds, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
+}
 
 int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B, const float* exp_noise,
               const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,

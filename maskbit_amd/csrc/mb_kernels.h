@@ -228,6 +228,8 @@ int attention_pair(hipStream_t s, const h16* qkv, h16* out, int P, int N, int d,
 int attention_probs(hipStream_t s, const h16* qkv, float* out, int nb, int N, int d, int heads);
 
 // ---- fused sampling step (sampling.py:90-131) ----------------------------------------------------
+// The constants of one sample at one step of a requests run (mb_request_step of include/maskbit_hip.h, field for field)
+struct RequestStep { float scale, temperature, mask_ratio, rand_temp, conf_w; int32_t step; };
 struct StepArgs {
   const float* logits_c; const float* logits_u;   // [B, n*m, C]
   float scale, temperature;
@@ -243,6 +245,9 @@ struct StepArgs {
   const int64_t* seeds = nullptr;
   int step = 0;
   float rand_temp = 0.f, conf_w = 0.f;
+  // req != null (with seeds): the PER-SAMPLE step (mb_sample_step_requests) -- scale, temperature, step, rand_temp, conf_w above and the mask_ratio of
+  // sample_step are not read; sample b takes them from req[b] (device [B]).
+  const RequestStep* req = nullptr;
 };
 // num_regen != null: the EDIT step (mb_sample_step_edit) -- per sample b the mask length is floor(mask_ratio * num_regen[b]), the masked count is the
 // sample's own, and a sample with fewer than two masked slots is not re-masked; a.k_mask_len is not read.

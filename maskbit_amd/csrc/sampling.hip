@@ -58,8 +58,11 @@ __device__ __forceinline__ float seeded_noise(uint64_t seed, int step, int slot,
 // The arithmetic per row and the order statistic are unchanged (bit-exact with the oracle: tests/test_hip_parity.py).
 // SEEDED: the two noise values are computed in registers from (seeds[row / P], step, slot, class) instead of read (four lanes recompute one Philox block:
 // no exchange, no LDS; profiles/seeded_noise.md); everything after the noise is the same code.
-template <int CPL, bool SEEDED>   // logits per lane: C <= 64*CPL
+// REQ (with SEEDED; include/maskbit_hip.h "per-sample sampling arguments"): scale, temperature, step, randomize temperature and confidence weight are those of
+// the sample's record a.req[row / P] instead of the kernel arguments -- one record per wave and row, a uniform read; everything after the constants is the same code.
+template <int CPL, bool SEEDED, bool REQ = false>   // logits per lane: C <= 64*CPL
 __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int64_t* __restrict__ tokens_in) {
+  static_assert(SEEDED || !REQ, "the per-sample records go with the seeded noise");
   const int C = a.C;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t mask_tok = (int64_t)C;
@@ -72,10 +75,16 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
     const float* lu = a.logits_u ? a.logits_u + row * C : nullptr;
     const float* qn = SEEDED ? nullptr : a.exp_noise + row * C;
     uint64_t seed = 0; int slot = 0;
+    float scale = a.scale, temperature = a.temperature, rand_temp = a.rand_temp, conf_w = a.conf_w;
+    int step = a.step;
     if constexpr (SEEDED) {
       const size_t b = row / (size_t)a.P;
       seed = (uint64_t)a.seeds[b];
       slot = (int)(row - b * (size_t)a.P);
+      if constexpr (REQ) {
+        const RequestStep rs = a.req[__builtin_amdgcn_readfirstlane((int)b)];   // (a wave works on one row: the index is uniform)
+        scale = rs.scale; temperature = rs.temperature; step = rs.step; rand_temp = rs.rand_temp; conf_w = rs.conf_w;
+      }
     }
     float l[CPL];
     float mx = -INFINITY;
@@ -85,8 +94,8 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
       float v = -INFINITY;
       if (c < C) {
         v = lc[c];
-        if (lu) v = cfg_combine(v, lu[c], a.scale);
-        v = v / a.temperature;                          // :105
+        if (lu) v = cfg_combine(v, lu[c], scale);
+        v = v / temperature;                            // :105
       }
       l[i] = v;
       mx = fmaxf(mx, v);
@@ -112,7 +121,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
           // live across it.  Up to CPL = 16 that saves a round's multiplies; at CPL = 32 it costs 186 VGPRs instead of 122 and at CPL = 64 scratch: the
           // empty statement makes c opaque there, which keeps the products inside the loop)
           if constexpr (CPL >= 32) asm volatile("" : "+v"(cc));
-          q = seeded_noise(seed, a.step, slot, cc, false, 0.f, 0.f, nullptr);
+          q = seeded_noise(seed, step, slot, cc, false, 0.f, 0.f, nullptr);
         }
         else q = qn[c];
         const float ratio = (l[i] / psum) / q;
@@ -134,7 +143,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
     pv = __shfl(pv, pred & 63);
     if (lane == 0) {
       float cn;
-      if constexpr (SEEDED) cn = seeded_noise(seed, a.step, slot, 0, true, a.rand_temp, a.conf_w, nullptr);
+      if constexpr (SEEDED) cn = seeded_noise(seed, step, slot, 0, true, rand_temp, conf_w, nullptr);
       else cn = a.conf_noise[row];
       const float conf = (masked ? logf(pv) : INFINITY) + cn;    // :113-118
       a.tokens[row] = (int64_t)(((uint64_t)(uint32_t)pred << 32) | (uint64_t)__float_as_uint(conf));
@@ -148,7 +157,8 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(StepArgs a, const int6
 //   nm >= 2: k = min(max(mask_len, 1), nm - 1) -- k - 1 <= nm - 2, so the threshold is a MASKED slot's confidence and a known slot (+inf) is never re-masked;
 //   nm <= 1: nothing is re-masked (tokens_out = pred).  The reference's clamp reaches k = 0 there, sorted[-1] = +inf, and every token of the image,
 //            the known ones included, would be masked again (DESIGN.md "Editing").
-template <bool EDIT>
+// REQ (with EDIT): the ratio is the sample's own, a.req[b].mask_ratio.
+template <bool EDIT, bool REQ = false>
 __global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const int64_t* __restrict__ tokens_in, float ratio, const int* __restrict__ num_regen) {
   extern __shared__ float sm[];
   const int P = a.P;
@@ -159,6 +169,7 @@ __global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const i
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int b = blockIdx.x;
   const int64_t mask_tok = (int64_t)a.C;
+  if constexpr (REQ) ratio = a.req[b].mask_ratio;
   // num_masked of SAMPLE 0 (sampling.py:109 reads index [0] for the whole batch); EDIT: of this sample
   const int64_t* tin = EDIT ? tokens_in + (size_t)b * P : tokens_in;
   int mycnt = 0;
@@ -198,27 +209,30 @@ __global__ __launch_bounds__(1024) void sample_thresh_kernel(StepArgs a, const i
   }
 }
 
-template <bool SEEDED>
+template <bool SEEDED, bool REQ = false>
 static void launch_rows(hipStream_t s, const StepArgs& a, const int64_t* tokens_in) {
   const size_t nrows = (size_t)a.B * a.P;
   dim3 grid((unsigned)((nrows + 15) / 16)), block(256);
-  if (a.C <= 64) hipLaunchKernelGGL((sample_rows_kernel<1, SEEDED>), grid, block, 0, s, a, tokens_in);
-  else if (a.C <= 128) hipLaunchKernelGGL((sample_rows_kernel<2, SEEDED>), grid, block, 0, s, a, tokens_in);
-  else if (a.C <= 256) hipLaunchKernelGGL((sample_rows_kernel<4, SEEDED>), grid, block, 0, s, a, tokens_in);
-  else if (a.C <= 512) hipLaunchKernelGGL((sample_rows_kernel<8, SEEDED>), grid, block, 0, s, a, tokens_in);
-  else if (a.C <= 1024) hipLaunchKernelGGL((sample_rows_kernel<16, SEEDED>), grid, block, 0, s, a, tokens_in);   // single-group codebooks (codebook_splits = 1)
-  else if (a.C <= 2048) hipLaunchKernelGGL((sample_rows_kernel<32, SEEDED>), grid, block, 0, s, a, tokens_in);
-  else hipLaunchKernelGGL((sample_rows_kernel<64, SEEDED>), grid, block, 0, s, a, tokens_in);
+  if (a.C <= 64) hipLaunchKernelGGL((sample_rows_kernel<1, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
+  else if (a.C <= 128) hipLaunchKernelGGL((sample_rows_kernel<2, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
+  else if (a.C <= 256) hipLaunchKernelGGL((sample_rows_kernel<4, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
+  else if (a.C <= 512) hipLaunchKernelGGL((sample_rows_kernel<8, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
+  else if (a.C <= 1024) hipLaunchKernelGGL((sample_rows_kernel<16, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);   // single-group codebooks (codebook_splits = 1)
+  else if (a.C <= 2048) hipLaunchKernelGGL((sample_rows_kernel<32, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
+  else hipLaunchKernelGGL((sample_rows_kernel<64, SEEDED, REQ>), grid, block, 0, s, a, tokens_in);
 }
 
 int sample_step(hipStream_t s, const StepArgs& a, const int64_t* tokens_in, const int* num_regen, float mask_ratio) {
   if (a.C > 4096 || a.P > 8192) return -1;
   if (a.seeds && !num_regen) return -1;             // a seeded step re-masks by the per-sample rule only
-  if (a.seeds) launch_rows<true>(s, a, tokens_in);
+  if (a.req && !a.seeds) return -1;                 // the per-sample records go with the seeded noise
+  if (a.req) launch_rows<true, true>(s, a, tokens_in);
+  else if (a.seeds) launch_rows<true>(s, a, tokens_in);
   else launch_rows<false>(s, a, tokens_in);
   const size_t shm = (size_t)a.P * 8 + 16 * 4 + 16;
   const dim3 tblock(a.P >= 1024 ? 1024 : 512);
-  if (num_regen) hipLaunchKernelGGL(sample_thresh_kernel<true>, dim3(a.B), tblock, shm, s, a, tokens_in, mask_ratio, num_regen);
+  if (a.req) hipLaunchKernelGGL((sample_thresh_kernel<true, true>), dim3(a.B), tblock, shm, s, a, tokens_in, 0.f, num_regen);
+  else if (num_regen) hipLaunchKernelGGL(sample_thresh_kernel<true>, dim3(a.B), tblock, shm, s, a, tokens_in, mask_ratio, num_regen);
   else hipLaunchKernelGGL(sample_thresh_kernel<false>, dim3(a.B), tblock, shm, s, a, tokens_in, 0.f, (const int*)nullptr);
   return 0;
 }

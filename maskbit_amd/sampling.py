@@ -13,7 +13,8 @@ combine, softmax, draw, confidence, k-th-smallest re-mask, combine, decode) neve
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Text, Tuple
+import dataclasses
+from typing import List, Optional, Sequence, Text, Tuple
 
 import torch
 
@@ -370,6 +371,148 @@ def sample_seeded(
     vqgan_model.eval()
     img, _, step_tokens, _ = run_chunked(model, vqgan_model, labels.reshape(-1), plan, randomize_temperature, seeds=seeds)
     return img, list(step_tokens.unbind(0))
+
+
+@dataclasses.dataclass(frozen=True)
+class SampleRequest:
+    """One request of a ``sample_requests`` batch: its seed and label, and its own sampling arguments with the defaults of ``sample_seeded``."""
+    seed: int
+    label: int
+    num_steps: int = 12
+    guidance_scale: float = 3.0
+    guidance_annealing: Text = "none"
+    scale_pow: float = 4.0
+    softmax_temperature: float = 1.0
+    use_sampling_annealing: bool = False
+    randomize_temperature: float = 4.5
+    mask_schedule_strategy: Text = "linear"
+
+
+REQUEST_COLUMNS = ("scale", "temperature", "mask_ratio", "randomize_temperature", "conf_weight", "step")   # mb_request_step, field for field
+
+
+def build_request_plan(requests: Sequence[SampleRequest]):
+    """The host side of a requests run (include/maskbit_hip.h "per-sample sampling arguments") -> ``(order, active, table)``; no device is touched.
+    ``order``: the stable permutation that sorts the requests by ``num_steps`` descending (position p of the run holds ``requests[order[p]]``; ties keep
+    request order).  ``active``: for each of the S = max ``num_steps`` global steps the number of requests that run it -- a prefix of the sorted batch,
+    since request b is right-aligned: it runs its local step i = t - (S - N_b) at global step t >= S - N_b.  ``table``: int32 [S, B, 6], one
+    ``mb_request_step`` record per (global step, position) in the order of ``REQUEST_COLUMNS`` -- the first five columns hold float32 BIT PATTERNS
+    (``table.view(torch.float32)``): scale, temperature and masking ratio of local step i from ``seeded_plan`` of the request's settings, its
+    randomize temperature, and float32(1 - (i + 1) / N_b); the sixth is i, the step's noise counter.  Inactive records are zero with step = -1.
+    ``ValueError``: no requests, a ``num_steps`` below 1, an unknown annealing or schedule, a seed outside [0, 2**64)."""
+    requests = list(requests)
+    if not requests:
+        raise ValueError("no requests")
+    for r in requests:
+        if not isinstance(r, SampleRequest):
+            raise TypeError(f"a request must be a SampleRequest, got {type(r).__name__}")
+        if isinstance(r.num_steps, bool) or not isinstance(r.num_steps, int) or r.num_steps < 1:
+            raise ValueError(f"num_steps must be an int >= 1, got {r.num_steps!r}")
+    check_seeds([r.seed for r in requests], len(requests))
+    B, S = len(requests), max(r.num_steps for r in requests)
+    order = sorted(range(B), key=lambda b: -requests[b].num_steps)            # (sorted is stable)
+    table = torch.zeros((S, B, len(REQUEST_COLUMNS)), dtype=torch.int32)
+    table[:, :, 5] = -1
+    as_f32 = table.view(torch.float32)                                         # the same memory: the float columns are written through it
+    columns = {}                                                               # one seeded_plan per distinct setting
+    for p, b in enumerate(order):
+        r = requests[b]
+        N = r.num_steps
+        key = (N, r.guidance_scale, r.guidance_annealing, r.scale_pow, r.softmax_temperature, r.use_sampling_annealing, r.mask_schedule_strategy)
+        if key not in columns:
+            scale, temp, ratio = seeded_plan(*key)
+            conf_w = [1 - (i + 1) / N for i in range(N)]                       # float32(1 - progress) once stored: the expression of _run
+            columns[key] = torch.tensor([scale, temp, ratio, conf_w], dtype=torch.float64).to(torch.float32).t()   # [N, 4]; one rounding, as ctypes' c_float
+        col = columns[key]
+        as_f32[S - N:, p, 0:3] = col[:, 0:3]
+        as_f32[S - N:, p, 3] = float(r.randomize_temperature)
+        as_f32[S - N:, p, 4] = col[:, 3]
+        table[S - N:, p, 5] = torch.arange(N, dtype=torch.int32)
+    active = [sum(1 for r in requests if r.num_steps >= S - t) for t in range(S)]
+    return order, active, table
+
+
+def run_requests(model: LFQBert, vqgan_model: Optional[ConvVQModel], requests: Sequence[SampleRequest], guided: Optional[bool] = None,
+                 init_tokens: Optional[torch.Tensor] = None, want_image: bool = True, want_u8: bool = False):
+    """One ``mb_sample_requests`` call (``run_seeded`` for requests) -> (image or None, uint8 NHWC or None -- both in REQUEST order --, step tokens
+    [S, B, n, m] in the run's own order, of which only the active (t, position) are written, position [B]: request b ran at ``position[b]``).
+    ``vqgan_model`` None: tokens only.  Arguments as ``sample_requests``; every check of the requests comes before any device work."""
+    order, active, table = build_request_plan(requests)
+    requests = list(requests)
+    B, S = len(requests), len(active)
+    any_scale = any(r.guidance_scale != 0.0 for r in requests)
+    if guided is None:
+        guided = any_scale
+    elif not guided and any_scale:
+        raise ValueError("guided=False, but a request has a non-zero guidance_scale")
+    n, m = model.seq_len, model.splits
+    labels = torch.tensor([int(requests[b].label) for b in order], dtype=torch.int64)
+    model._check_labels(labels)
+    if init_tokens is not None:
+        if not isinstance(init_tokens, torch.Tensor) or init_tokens.dtype != torch.int64:
+            raise TypeError("init_tokens must be an int64 tensor")
+        if tuple(init_tokens.shape) != (B, n, m):
+            raise ValueError(f"init_tokens must be [{B}, {n}, {m}], got {tuple(init_tokens.shape)}")
+        if init_tokens.device.type == "cpu" and (int(init_tokens.min()) < 0 or int(init_tokens.max()) > model.mask_token):
+            raise ValueError(f"token outside [0, {model.mask_token}] (mask_token = {model.mask_token} marks a slot to regenerate)")
+    seeds = check_seeds([requests[b].seed for b in order], B)
+    dev = model._require_cuda("sample_requests")
+    identity = order == list(range(B))
+    position = torch.empty(B, dtype=torch.int64)
+    position[torch.tensor(order)] = torch.arange(B)                            # request b runs at position[b]
+    # (every upload pinned and asynchronous, as _run uploads the seeds: a pageable copy would hold the host until the device has run the previous batch)
+    up = lambda cpu: cpu.pin_memory().to(dev, non_blocking=True)
+    with torch.cuda.device(dev):
+        labels, seeds, table = up(labels), up(seeds), up(table)
+        if not identity:
+            order_dev, position_dev = up(torch.tensor(order)), up(position)
+        if init_tokens is not None:
+            init_tokens = init_tokens.to(dev) if init_tokens.device.type != "cpu" else up(init_tokens.contiguous())
+            init_tokens = (init_tokens if identity else init_tokens[order_dev]).contiguous()
+        step_tokens = torch.empty((S, B, n, m), dtype=torch.int64, device=dev)
+        img = u8 = hdec = None
+        if vqgan_model is not None and (want_image or want_u8):
+            side = int(round(n ** 0.5))
+            res = side << (vqgan_model.num_resolutions - 1)
+            if want_image:
+                img = torch.empty((B, vqgan_model.num_channels, res, res), dtype=torch.float32, device=dev)
+            if want_u8:
+                u8 = torch.empty((B, res, res, vqgan_model.num_channels), dtype=torch.uint8, device=dev)
+            hdec = vqgan_model.engine(B, side)
+        hgen = model.engine(2 * B if guided else B)
+        cplan = _lib.RequestPlan(S, 1 if guided else 0, (C.c_int * S)(*active), table.data_ptr())
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().mb_sample_requests(hgen, hdec, C.byref(cplan), labels.data_ptr(), B, ptr(init_tokens), seeds.data_ptr(), step_tokens.data_ptr(),
+                                                  None, ptr(img), ptr(u8), torch.cuda.current_stream().cuda_stream), "mb_sample_requests")
+        if not identity:
+            img, u8 = (None if t is None else t[position_dev] for t in (img, u8))
+    return img, u8, step_tokens, position
+
+
+def request_steps(requests: Sequence[SampleRequest], step_tokens: torch.Tensor, position: torch.Tensor) -> List[List[torch.Tensor]]:
+    """Per request the list of its own ``num_steps`` step tokens [n, m], out of what ``run_requests`` returns (views: nothing is copied)."""
+    S = step_tokens.shape[0]
+    return [list(step_tokens[S - r.num_steps:, p].unbind(0)) for r, p in zip(requests, position.tolist())]
+
+
+@torch.no_grad()
+def sample_requests(model, vqgan_model, requests: Sequence[SampleRequest], *, guided: Optional[bool] = None, init_tokens: Optional[torch.Tensor] = None,
+                    return_uint8: bool = False) -> Tuple[torch.Tensor, List[List[torch.Tensor]]]:
+    """``sample_seeded`` for a batch of requests that each bring their own sampling arguments (``SampleRequest``): one ``mb_sample_requests`` call runs
+    them together, each right-aligned in max ``num_steps`` global steps, at the cost of sum ``num_steps`` sequence-forwards.  A request's tokens and
+    image depend on its own fields and on ``guided`` alone -- not on the other requests, its position or the batch size.
+    ``guided``: one flag for the run.  None: guided if any request has a non-zero ``guidance_scale``; False with a non-zero scale raises; True forces
+    the guided forward.  In a guided run EVERY step runs the guided forward (a zero scale gets ``c + 0 * (c - u)``) -- unlike ``sample_seeded``, which
+    runs the plain forward on zero-scale steps below precision 4; the two agree where both run the same forwards.
+    ``init_tokens`` int64 [B, n, m], in request order: each request starts from its own token map, as ``sample_from_tokens(seeds=)`` does.
+    -> (images in REQUEST order: float32 [B, 3, H, W] unclamped, or with ``return_uint8`` uint8 [B, H, W, 3]; per request the list of its own
+    ``num_steps`` step tokens [n, m]).  Nothing synchronises with the host, no torch generator is consumed."""
+    check_models(model, vqgan_model, "sample_requests")
+    requests = list(requests)
+    model.eval()
+    vqgan_model.eval()
+    img, u8, step_tokens, position = run_requests(model, vqgan_model, requests, guided, init_tokens, want_image=not return_uint8, want_u8=return_uint8)
+    return (u8 if return_uint8 else img), request_steps(requests, step_tokens, position)
 
 
 @torch.no_grad()
