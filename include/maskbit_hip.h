@@ -307,6 +307,64 @@ int mb_sample_step_requests(const float* logits_c, const float* logits_u, const 
 int mb_sample_requests(mb_gen* g, mb_dec* d, const mb_request_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens,
                        const int64_t* seeds, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream);
 
+/* ---- sampling session: requests join and leave a running batch ------------------------------------------------------------------------------------ *
+ * A requests run (above) is closed: planned for a fixed set, right-aligned, the handle busy for max N_b steps.  A SESSION is the open form: a batch of
+ * at most max_active rows that requests enter (mb_session_admit) and leave (when their own N steps are done) while it runs, one step per
+ * mb_session_tick.  Additions only, MB_ABI_VERSION unchanged.
+ *
+ * STATE  A session is created for one generator configuration (seq, splits and bits of mb_gen_cfg: n = seq positions of m = splits groups of
+ * C = 2^(bits / splits) codes; every tick takes a generator handle of that configuration) with a capacity max_active, a max_steps and ONE
+ * use_guidance flag, which follows the mb_sample_requests rule: in a guided session every tick runs the guided forward, and a zero scale gets
+ * c + 0 * (c - u).  It owns, on the device, both token buffers and a prediction buffer [max_active, n, m]; per row its label, seed, num_regen,
+ * schedule slot, local step and N; a schedule pool of mb_request_step records [max_active, max_steps]; the step's table row, a codes buffer and the
+ * plan snapshot -- allocated by the first admit that passes its checks (mb_session_create itself touches no device).  The active requests are the
+ * dense row prefix [0, A).
+ *
+ * ADMIT appends K requests at rows [A, A + K): labels, seeds (device int64 [K]), num_steps (HOST int [K], 1 <= N <= max_steps) and the schedule --
+ * request k's N_k records, local step i of an N_k-step run (table[i][0] of build_request_plan([r]): step = i), packed one request after the other in
+ * one device array of sum_k N_k records.  init_tokens (device int64 [K, n, m], or NULL = every slot masked) go into the buffer the next tick reads,
+ * clamped to [0, C], and num_regen is counted on the device, both as mb_sample_edit does.  tickets (HOST uint64 [K]) receives one ticket per request:
+ * they count from 0 in admission order.  A + K > max_active is refused without any launch.
+ *
+ * TICK runs one step for the rows [0, A), in this order:
+ *   1. row table   row[r] = pool[slot[r]][local_step[r]], then local_step[r] += 1 -- a kernel; nothing is uploaded per tick.
+ *   2. forward and step over A rows, exactly one global step of mb_sample_requests.  The predictions go to pred_out ([A, n, m]) or, NULL, to the
+ *      session's own buffer.
+ *   3. retire and compact   F = {r : local_step[r] == N[r]}, k = |F|, A' = A - k.  The predictions of the rows of F are combined
+ *      (combine_factorized_tokens) into codes [k, n] IN ASCENDING ROW ORDER (codes_out, or NULL: the session's buffer).  The holes H = F below A' and
+ *      the movers M = the unfinished rows at or above A', both ascending, have the same length, and row M[j] moves to H[j]: its tokens in the buffer
+ *      the next tick reads, and label, seed, num_regen, slot, local step and N.  Sources lie at or above A', destinations below: the moves are
+ *      disjoint and run in parallel in place.  F, H and M are taken ONCE, by a plan kernel into a snapshot; the move kernel acts on the snapshot
+ *      alone (it overwrites local_step[dst], from which F was derived).
+ *   4. decode   with a decoder the k codes are decoded by mb_dec_decode into img_nchw / img_nhwc_u8 ([k, ...], each may be NULL).
+ * The session keeps a host mirror of (ticket, local step, N) per row and applies the same rule to it, so a tick reports without reading the device:
+ * *num_finished = k, finished (HOST uint64 [>= mb_session_due()]) = the tickets of the finished requests in output order, ran (HOST uint64 [A], may
+ * be NULL) = the ticket of every row that ran this tick, row by row -- what pred_out's rows belong to.  mb_session_due: how many requests the NEXT
+ * tick finishes (size the image buffers by it); mb_session_active: A.  A tick with A = 0 does nothing.  Every tick and every admit is enqueue-only:
+ * no synchronisation, no host read, and no host-to-device copy.
+ *
+ * CONSEQUENCES
+ *   - A request admitted before tick t runs its local step i at tick t + i and finishes at tick t + N - 1.
+ *   - Its tokens, codes and image are bit for bit what mb_sample_requests gives for it alone under the same use_guidance -- whatever else is in the
+ *     session and however its row has moved: noise is a function of (seed, local step, slot, class), the threshold rule is per sample, the step
+ *     kernels read their constants per sample, the forwards and the decoder do not depend on the batch.
+ *   - The guided forward's [labels | labels] / [0 | 1] cache of the handle is keyed by the label pointer, and the session's label buffer keeps its
+ *     address while its contents move: the session invalidates the cache whenever membership changed (an admit, a tick that retired a request).
+ *   - A tick ends any chunked run in progress on the handle, as mb_sample_requests does.
+ *   - The session owns its token state: other calls on the same handle (mb_sample, mb_sample_seeded, ...) may run between two ticks without changing
+ *     the session's results, and the handle may be replaced by another of the same configuration.
+ * Refused before any launch, the checks that need no handle first: null arguments; max_active, max_steps or K below 1; an N outside [1, max_steps];
+ * A + K > max_active; an image without a decoder; a handle of another configuration, or one that holds fewer than 2 A (guided) or A sequences. */
+typedef struct mb_session mb_session;
+int mb_session_create(int seq, int splits, int bits, int max_active, int max_steps, int use_guidance, mb_session** out);
+void mb_session_destroy(mb_session* s);
+int mb_session_admit(mb_session* s, int K, const int64_t* labels, const int64_t* seeds, const int* num_steps, const mb_request_step* schedule,
+                     const int64_t* init_tokens, uint64_t* tickets, mb_stream stream);
+int mb_session_due(const mb_session* s);      /* requests the next tick finishes; -1: null */
+int mb_session_active(const mb_session* s);   /* A; -1: null */
+int mb_session_tick(mb_session* s, mb_gen* g, mb_dec* d, int64_t* pred_out, int64_t* codes_out, float* img_nchw, uint8_t* img_nhwc_u8,
+                    uint64_t* finished, uint64_t* ran, int* num_finished, mb_stream stream);
+
 /* ---- tokenizer evaluation: TokenizerEvaluator.update, evaluator/evaluator.py:262-375 (scripts/eval_tokenizer.py:137-149) ---------------- *
  * Stateless: the caller owns every buffer (and zeroes its running state once); nothing is allocated, nothing synchronises.
  * Bytes of workspace mb_eval_images needs for this shape (one slot of three doubles per 32 x 32 tile of every image plane); 0 for a shape it

@@ -276,6 +276,30 @@ int mb_gemm_f32(int epi, const float* A, const float* W, const float* bias, cons
                 int bias_per_pos, mb_stream stream);
 int mb_attention_f32(const float* qkv, float* out, int nb, int N, int d, int heads, mb_stream stream);
 
+/* ---- the sampling session's kernels (session.hip; include/maskbit_hip.h "sampling session") on caller-owned arrays, no generator
+ * (tests/test_hip_session.py).  mb_session_rows: the per-row state of a session of max_active rows, all device arrays -- slot a permutation of
+ * [0, max_active), pool [max_active, max_steps] records.
+ * mb_session_row_table: row_out[r] = pool[slot[r]][local_step[r]], local_step[r] += 1 for r < A.
+ * mb_session_admit_rows: what mb_session_admit enqueues for K requests at rows [A, A + K) of tokens [max_active, n, m]: the start tokens (init_tokens
+ * [K, n, m] clamped to [0, C], or NULL: all C), num_regen = their masked count, label, seed, N = num_steps[k] (HOST), local step 0 and the request's
+ * records (packed in schedule) into pool[slot[A + k]].
+ * mb_session_retire: step 3 of a tick -- the plan kernel into plan (int32 [2 + 3 max_active]: k, moves, finished rows, sources, destinations), the
+ * finished rows' pred [A, n, m] combined into codes_out [k, n] in ascending row order (codes_all [A, n]: scratch), and the moves in tokens and in
+ * every field of rows.  The launches are sized by A (the session sizes them by its host mirror); rows beyond the snapshot's counts do nothing.
+ * Refused (-1, nothing launched): a NULL pointer, A or K below 1, rows beyond max_active, an N outside [1, max_steps], n m beyond 8192, C no power of
+ * two up to 4096. */
+typedef struct {
+  int64_t* label; int64_t* seed;
+  int32_t* num_regen; int32_t* slot; int32_t* local_step; int32_t* N;
+  mb_request_step* pool;
+  int max_active, max_steps;
+} mb_session_rows;
+int mb_session_row_table(const mb_session_rows* rows, mb_request_step* row_out, int A, mb_stream stream);
+int mb_session_admit_rows(const mb_session_rows* rows, int64_t* tokens, int A, int K, const int64_t* labels, const int64_t* seeds, const int* num_steps,
+                          const mb_request_step* schedule, const int64_t* init_tokens, int n, int m, int C, mb_stream stream);
+int mb_session_retire(const mb_session_rows* rows, int64_t* tokens, const int64_t* pred, int64_t* codes_all, int64_t* codes_out, int32_t* plan,
+                      int A, int n, int m, int C, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ from .taming_vqgan import OriginalVQModel
 from .factorization import combine_factorized_tokens, split_factorized_tokens
 from .masking import get_masking_ratio
 from .sampling import SampleRequest, sample, sample_requests, sample_seeded
+from .session import Finished, SamplingSession
 from .evaluator import TokenizerEvaluator
 from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covariance, inception_score
 from .manifold import knn_radii, manifold_coverage, precision_recall
@@ -18,7 +19,7 @@ from .validation import MLMLoss, MaskedTokenEvaluator, get_mask_tokens
 from .harness import (eval_generation, eval_labels, eval_masked_prediction, eval_reconstruction, generate_uint8, mask_token_for,
                       to_evaluator_uint8)
 
-__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sample", "sample_seeded", "SampleRequest", "sample_requests", "get_masking_ratio",
+__all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sample", "sample_seeded", "SampleRequest", "sample_requests", "SamplingSession", "Finished", "get_masking_ratio",
            "combine_factorized_tokens", "split_factorized_tokens", "eval_labels", "generate_uint8", "mask_token_for", "to_evaluator_uint8",
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",

@@ -45,6 +45,11 @@ class RequestPlan(C.Structure):
     _fields_ = [("num_steps", C.c_int), ("use_guidance", C.c_int), ("active", C.POINTER(C.c_int)), ("table", C.c_void_p)]
 
 
+class SessionRows(C.Structure):
+    """mb_session_rows (diagnostic): the per-row device arrays of a sampling session of ``max_active`` rows."""
+    _fields_ = [(n, C.c_void_p) for n in ("label", "seed", "num_regen", "slot", "local_step", "N", "pool")] + [("max_active", C.c_int), ("max_steps", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/maskbit_hip.h (the ABI) and include/maskbit_hip_diag.h (single-kernel test entries) declare
 SIGNATURES = {
     "mb_gen_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
@@ -89,6 +94,18 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_sample_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RequestPlan), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_session_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mb_session_destroy": (None, [C.c_void_p]),
+    "mb_session_admit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "mb_session_due": (C.c_int, [C.c_void_p]),
+    "mb_session_active": (C.c_int, [C.c_void_p]),
+    "mb_session_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p]),
+    "mb_session_row_table": (C.c_int, [C.POINTER(SessionRows), C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_session_admit_rows": (C.c_int, [C.POINTER(SessionRows), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mb_session_retire": (C.c_int, [C.POINTER(SessionRows), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p]),
     "mb_seeded_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p]),
     "mb_edit_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

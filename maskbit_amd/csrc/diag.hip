@@ -557,4 +557,45 @@ int mb_attention_f32(const float* qkv, float* out, int nb, int N, int d, int hea
   return launched();
 }
 
+// ---- the sampling session's kernels on caller-owned arrays (tests/test_hip_session.py) ----
+static_assert(sizeof(mb_session_rows) == sizeof(mb::SessionRows), "mb_session_rows is the kernels' SessionRows");
+static const char* session_rows_check(const mb_session_rows* r, int rows_used, int n, int m, int C, int* gbits) {
+  if (!r || !r->label || !r->seed || !r->num_regen || !r->slot || !r->local_step || !r->N || !r->pool) return "null argument";
+  if (r->max_active < 1 || r->max_steps < 1 || rows_used < 1 || rows_used > r->max_active) return "rows outside [1, max_active]";
+  if (n < 1 || m < 1 || (size_t)n * m > 8192) return "n * m outside [1, 8192]";
+  if (C < 2 || C > 4096 || (C & (C - 1))) return "C must be a power of two up to 4096";
+  *gbits = 0;
+  while ((1 << *gbits) < C) ++*gbits;
+  return nullptr;
+}
+static mb::SessionRows session_rows(const mb_session_rows* r) {
+  return mb::SessionRows{r->label, r->seed, r->num_regen, r->slot, r->local_step, r->N, (mb::RequestStep*)r->pool, r->max_active, r->max_steps};
+}
+int mb_session_row_table(const mb_session_rows* rows, mb_request_step* row_out, int A, mb_stream stream) {
+  int gbits;
+  if (const char* why = session_rows_check(rows, A, 1, 1, 2, &gbits)) return fail(-1, "mb_session_row_table: %s", why);
+  if (!row_out) return fail(-1, "mb_session_row_table: null argument");
+  mb::session_row_table((hipStream_t)stream, session_rows(rows), (mb::RequestStep*)row_out, A);
+  return launched();
+}
+int mb_session_admit_rows(const mb_session_rows* rows, int64_t* tokens, int A, int K, const int64_t* labels, const int64_t* seeds, const int* num_steps,
+                          const mb_request_step* schedule, const int64_t* init_tokens, int n, int m, int C, mb_stream stream) {
+  int gbits;
+  if (A < 0 || K < 1) return fail(-1, "mb_session_admit_rows: bad sizes (A = %d, K = %d)", A, K);
+  if (const char* why = session_rows_check(rows, A + K, n, m, C, &gbits)) return fail(-1, "mb_session_admit_rows: %s", why);
+  if (!tokens || !labels || !seeds || !num_steps || !schedule) return fail(-1, "mb_session_admit_rows: null argument");
+  for (int k = 0; k < K; ++k)
+    if (num_steps[k] < 1 || num_steps[k] > rows->max_steps) return fail(-1, "mb_session_admit_rows: num_steps[%d] = %d outside [1, %d]", k, num_steps[k], rows->max_steps);
+  mb::session_admit((hipStream_t)stream, session_rows(rows), tokens, init_tokens, num_steps, labels, seeds, (const mb::RequestStep*)schedule, A, K, n * m, C);
+  return launched();
+}
+int mb_session_retire(const mb_session_rows* rows, int64_t* tokens, const int64_t* pred, int64_t* codes_all, int64_t* codes_out, int32_t* plan,
+                      int A, int n, int m, int C, mb_stream stream) {
+  int gbits;
+  if (const char* why = session_rows_check(rows, A, n, m, C, &gbits)) return fail(-1, "mb_session_retire: %s", why);
+  if (!tokens || !pred || !codes_all || !codes_out || !plan) return fail(-1, "mb_session_retire: null argument");
+  mb::session_retire((hipStream_t)stream, session_rows(rows), plan, tokens, pred, codes_all, codes_out, A, n, m, gbits, A, A / 2);   // (at most min(k, A - k) moves)
+  return launched();
+}
+
 }  // extern "C"

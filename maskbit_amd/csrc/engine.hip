@@ -420,6 +420,7 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
     if (!(pair && !g->c.embed_tables && g->c.bits <= 24))
       HIP_TRY(hipMemcpyAsync(g->tok_cfg + nc * P, tokens + (size_t)b0 * P, nc * P * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (!(nc == B && g->run.cfg_labels == labels && g->run.cfg_B == B)) {       // (the sampling loop marks them ready for the steps of one call)
+      g->run.cfg_labels = nullptr;                      // whatever they were marked ready for is overwritten: a session's mark outlives its call
       HIP_TRY(hipMemcpyAsync(g->lab_cfg, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemcpyAsync(g->lab_cfg + nc, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemsetAsync(g->drop_cfg, 0, nc, s));
@@ -992,6 +993,177 @@ int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64
   r.init_tokens = init_tokens;
   r.noise.seeds = seeds; r.noise.rand_temp = randomize_temperature; r.noise.conf_weight = conf_weight;
   return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// sampling session (include/maskbit_hip.h "sampling session"; kernels: session.hip)
+// ================================================================================================
+// The session object: the device state of max_active rows (allocated by the first admit that passes its checks) and the HOST MIRROR of the rule the
+// kernels apply -- per active row its ticket, local step and N --, from which a tick knows k, the moves and the finished tickets without reading the
+// device.  tok[cur] is the buffer the next tick reads.
+struct mb_session {
+  int n = 0, m = 0, C = 0, gbits = 0, cap = 0, max_steps = 0;
+  bool guided = false, allocated = false;
+  size_t P = 0;
+  struct Row { uint64_t ticket; int local_step, N; };
+  std::vector<Row> rows;                                // [A]
+  uint64_t next_ticket = 0;
+  int64_t* tok[2] = {nullptr, nullptr};
+  int cur = 0;
+  int64_t *pred = nullptr, *codes_all = nullptr, *codes = nullptr;
+  mb::SessionRows st{};
+  mb::RequestStep* row = nullptr;                       // [cap]: the step's table row
+  int* plan = nullptr;                                  // the snapshot of a tick's retire step (mb::session_plan_ints)
+  bool cfg_dirty = true;                                // membership changed since the handle's lab_cfg / drop_cfg were filled from st.label
+  mb::DevArena mem;
+};
+
+namespace {
+
+int session_allocate(mb_session* s) {
+  if (s->allocated) return 0;
+  mb::DevArena& m = s->mem;
+  const size_t cap = (size_t)s->cap;
+  m.get(&s->tok[0], cap * s->P); m.get(&s->tok[1], cap * s->P); m.get(&s->pred, cap * s->P);
+  m.get(&s->codes_all, cap * s->n); m.get(&s->codes, cap * s->n);
+  m.get(&s->st.label, cap); m.get(&s->st.seed, cap);
+  m.get(&s->st.num_regen, cap); m.get(&s->st.slot, cap); m.zeroed(&s->st.local_step, cap); m.zeroed(&s->st.N, cap);
+  m.get(&s->st.pool, cap * s->max_steps);
+  m.get(&s->row, cap); m.get(&s->plan, mb::session_plan_ints(s->cap));
+  if (int rc = m.failed("mb_session_admit")) return rc;
+  std::vector<int> iota(cap);
+  for (size_t r = 0; r < cap; ++r) iota[r] = (int)r;    // every pool slot free: row r would take slot r
+  HIP_TRY(hipMemcpy(s->st.slot, iota.data(), cap * sizeof(int), hipMemcpyHostToDevice));
+  s->st.cap = s->cap; s->st.max_steps = s->max_steps;
+  s->allocated = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mb_session_create(int seq, int splits, int bits, int max_active, int max_steps, int use_guidance, mb_session** out) {
+  if (!out) return fail(-1, "mb_session_create: null argument");
+  if (max_active < 1 || max_steps < 1) return fail(-1, "mb_session_create: bad sizes (max_active = %d, max_steps = %d: both at least 1)", max_active, max_steps);
+  if (seq < 1 || splits < 1 || bits < 1 || bits > 24 || bits % splits || (size_t)seq * splits > 8192 || (1 << (bits / splits)) > 4096)
+    return fail(-1, "mb_session_create: seq = %d, splits = %d, bits = %d is no generator configuration (mb_gen_create)", seq, splits, bits);
+  if ((size_t)max_active * max_steps > ((size_t)1 << 27)) return fail(-1, "mb_session_create: max_active * max_steps = %zu schedule records exceed 2^27", (size_t)max_active * max_steps);
+  mb_session* s = new mb_session();
+  s->n = seq; s->m = splits; s->gbits = bits / splits; s->C = 1 << s->gbits; s->P = (size_t)seq * splits;
+  s->cap = max_active; s->max_steps = max_steps; s->guided = use_guidance != 0;
+  s->rows.reserve(max_active);
+  *out = s;
+  return 0;
+}
+
+void mb_session_destroy(mb_session* s) { delete s; }
+
+int mb_session_active(const mb_session* s) { return s ? (int)s->rows.size() : -1; }
+
+int mb_session_due(const mb_session* s) {
+  if (!s) return -1;
+  int due = 0;
+  for (const mb_session::Row& r : s->rows) due += r.local_step + 1 == r.N;
+  return due;
+}
+
+int mb_session_admit(mb_session* s, int K, const int64_t* labels, const int64_t* seeds, const int* num_steps, const mb_request_step* schedule,
+                     const int64_t* init_tokens, uint64_t* tickets, mb_stream stream) {
+  const char* who = "mb_session_admit";
+  if (K < 1) return fail(-1, "%s: bad sizes (K = %d)", who, K);
+  if (!s || !labels || !seeds || !num_steps || !schedule || !tickets) return fail(-1, "%s: null argument", who);
+  for (int k = 0; k < K; ++k)
+    if (num_steps[k] < 1 || num_steps[k] > s->max_steps) return fail(-1, "%s: num_steps[%d] = %d outside [1, %d]", who, k, num_steps[k], s->max_steps);
+  const int A = (int)s->rows.size();
+  if (K > s->cap - A) return fail(-1, "%s: %d active + %d new requests exceed max_active = %d", who, A, K, s->cap);
+  if (int rc = session_allocate(s)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the start state goes into the buffer the next tick reads; the other one is written by that tick's step before anything reads it
+  mb::session_admit(st, s->st, s->tok[s->cur], init_tokens, num_steps, labels, seeds, (const mb::RequestStep*)schedule, A, K, (int)s->P, s->C);
+  for (int k = 0; k < K; ++k) {
+    tickets[k] = s->next_ticket;
+    s->rows.push_back({s->next_ticket++, 0, num_steps[k]});
+  }
+  s->cfg_dirty = true;
+  return launched();
+}
+
+int mb_session_tick(mb_session* s, mb_gen* g, mb_dec* d, int64_t* pred_out, int64_t* codes_out, float* img_nchw, uint8_t* img_nhwc_u8, uint64_t* finished,
+                    uint64_t* ran, int* num_finished, mb_stream stream) {
+  const char* who = "mb_session_tick";
+  if (!s || !num_finished) return fail(-1, "%s: null argument", who);
+  *num_finished = 0;
+  const int A = (int)s->rows.size();
+  if (A == 0) return 0;                                  // an empty session: nothing to run, nothing launched
+  if (!finished && mb_session_due(s) > 0) return fail(-1, "%s: null argument (%d requests finish, no ticket array)", who, mb_session_due(s));
+  if (!d && (img_nchw || img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
+  if (!g) return fail(-1, "%s: null argument (no generator handle)", who);
+  const mb_gen_cfg& c = g->c;
+  if (c.seq != s->n || c.splits != s->m || g->C != s->C)
+    return fail(-1, "%s: the session was created for %d positions x %d groups of %d codes, the generator has %d x %d of %d", who, s->n, s->m, s->C, c.seq, c.splits, g->C);
+  const int nbf = s->guided ? 2 * A : A;
+  if (nbf > g->max_seqs) return fail(-1, "%s: %d active requests need %d sequences, engine holds %d", who, A, nbf, g->max_seqs);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t P = s->P;
+  mb_gen::Run& run = g->run;
+  run.next = -1;                                         // ends any chunked run in progress, as mb_sample_requests does
+  // 1. the step's table row, gathered on the device
+  mb::session_row_table(st, s->st, s->row, A);
+  // 2. one global step of sample_requests_run over the A rows.  lab_cfg / drop_cfg of the handle stay marked ready ACROSS ticks (nothing else leaves a
+  // mark behind, and gen_forward_cfg drops it when it overwrites them), but never across a change of membership: the label buffer keeps its address
+  int64_t* cur = s->tok[s->cur];
+  int64_t* nxt = s->tok[s->cur ^ 1];
+  if (s->cfg_dirty && run.cfg_labels == s->st.label) run.cfg_labels = nullptr;
+  mb::StepArgs a{};
+  a.logits_c = g->logits; a.B = A; a.P = (int)P; a.C = s->C;
+  a.seeds = s->st.seed; a.req = s->row;
+  int rc;
+  if (s->guided) {
+    rc = gen_forward_cfg(g, cur, s->st.label, g->logits, A, st);
+    a.logits_u = g->logits + (size_t)A * P * s->C;
+    if (A <= g->chunk_seqs / 2) { run.cfg_labels = s->st.label; run.cfg_B = A; }
+    else run.cfg_labels = nullptr;
+    s->cfg_dirty = false;
+  } else {
+    rc = gen_forward(g, cur, s->st.label, nullptr, g->logits, A, st);
+  }
+  if (rc) return rc;
+  int64_t* pred = pred_out ? pred_out : s->pred;
+  a.tokens = nxt; a.pred = pred;
+  rc = sample_step_checked(who, a, cur, s->st.num_regen, 0.f, st);
+  if (rc) return rc;
+  s->cur ^= 1;
+  // 3. retire and compact: the mirror applies the kernels' rule -- F ascending, holes = F below A', movers = the unfinished rows at or above A'
+  std::vector<mb_session::Row>& rows = s->rows;
+  int k = 0;
+  for (int r = 0; r < A; ++r) {
+    if (ran) ran[r] = rows[r].ticket;
+    if (++rows[r].local_step == rows[r].N) finished[k++] = rows[r].ticket;
+  }
+  *num_finished = k;
+  if (k == 0) return launched();
+  const int Ap = A - k;
+  int moves = 0;
+  for (int hole = 0, mover = Ap; hole < Ap; ++hole) {
+    if (rows[hole].local_step != rows[hole].N) continue;
+    while (rows[mover].local_step == rows[mover].N) ++mover;   // (as many unfinished rows at or above A' as finished ones below)
+    rows[hole] = rows[mover++];
+    ++moves;
+  }
+  rows.resize(Ap);
+  s->cfg_dirty = true;
+  if (run.cfg_labels == s->st.label) run.cfg_labels = nullptr;
+  int64_t* codes = codes_out ? codes_out : s->codes;
+  mb::session_retire(st, s->st, s->plan, s->tok[s->cur], pred, s->codes_all, codes, A, s->n, s->m, s->gbits, k, moves);
+  // 4. decode the k finished requests
+  if (d && (img_nchw || img_nhwc_u8)) {
+    rc = mb_dec_decode(d, codes, img_nchw, img_nhwc_u8, k, (mb_stream)st);
+    if (rc) return rc;
+  }
+  return launched();
 }
 
 }  // extern "C"

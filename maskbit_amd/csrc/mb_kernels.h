@@ -272,6 +272,33 @@ void edit_token_mask(hipStream_t s, const uint8_t* pixel_mask, uint8_t* token_ma
 int edit_composite(hipStream_t s, const float* gen, const float* orig, const uint8_t* pixel_mask, float* out_nchw, uint8_t* out_u8, int B, int C, int H, int W);
 void combine_groups(hipStream_t s, const int64_t* tokens /*[rows,m]*/, int64_t* codes /*[rows]*/, size_t rows, int m, int gbits);
 
+// ---- sampling session (session.hip): the per-row state of the active prefix [0, A) and the kernels that keep it dense ----------------------------
+// Device arrays of `cap` rows (mb_session_rows of include/maskbit_hip_diag.h, field for field): slot[] is a permutation of [0, cap) -- rows [0, A) hold
+// the pool slots in use --, pool [cap, max_steps] the schedule records of the request in each slot.
+struct SessionRows {
+  int64_t* label; int64_t* seed;
+  int* num_regen; int* slot; int* local_step; int* N;
+  RequestStep* pool;
+  int cap, max_steps;
+};
+// What one admit launch carries in its kernel arguments: num_steps of up to MAX requests and where each one's records begin in the packed schedule
+struct AdmitBatch { enum { MAX = 64 }; int n[MAX]; int off[MAX]; };
+// ints of the plan snapshot of a session of cap rows: {k, moves, finished[cap], src[cap], dst[cap]}
+inline size_t session_plan_ints(int cap) { return 2 + 3 * (size_t)cap; }
+// row[r] = pool[slot[r]][local_step[r]]; local_step[r] += 1, r < A (A >= 1)
+void session_row_table(hipStream_t s, const SessionRows& st, RequestStep* row, int A);
+// Rows [A, A + K) of tokens [cap, P]: the start tokens (init_tokens [K, P] clamped to [0, C], or null: all C) and num_regen = their masked count -- both
+// edit_load_tokens' --, label, seed, N = num_steps[k] (HOST [K]), local step 0, and request k's num_steps[k] records -- packed one request after the
+// other in sched (device) -- into pool[slot[A + k]]
+void session_admit(hipStream_t s, const SessionRows& st, int64_t* tokens, const int64_t* init_tokens, const int* num_steps, const int64_t* labels,
+                   const int64_t* seeds, const RequestStep* sched, int A, int K, int P, int C);
+// Step 3 of a tick.  The snapshot: finished rows F = {r < A : local_step[r] == N[r]} ascending, holes (dst) = F below A' = A - |F| ascending, movers
+// (src) = the unfinished rows at or above A' ascending.  Then codes_out [k, n] = combine_groups(pred [A, n, m]) of the rows of F (codes_all [A, n]:
+// scratch), and row src[j] -> row dst[j]: the n m tokens of the row in `tokens` [cap, n m], label, seed, num_regen, local step, N; slots swapped.
+// k and moves size the two launches: the exact counts (the session's host mirror), or upper bounds (rows beyond the snapshot's counts do nothing)
+void session_retire(hipStream_t s, const SessionRows& st, int* plan, int64_t* tokens, const int64_t* pred, int64_t* codes_all, int64_t* codes_out,
+                    int A, int n, int m, int gbits, int k, int moves);
+
 // ---- fp32 -> h16 repack ------------------------------------------------------------------------
 void cast_f32_to_h16(hipStream_t s, const float* src, h16* dst, size_t n);
 // W[N,K] fp32 -> two planes hi[N,K] = fp16(W*2^S), lo[N,K] = fp16(W*2^S - hi) (GemmArgs.W / W2), S chosen from max|W| (tmp: one device uint32 of
