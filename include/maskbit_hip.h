@@ -515,6 +515,42 @@ int mb_taming_decode_latent(mb_taming* h, const float* z_nchw, float* img_nchw, 
  * Synchronises `stream`; nothing else of this handle does. */
 int mb_taming_saturation_count(mb_taming* h, unsigned* count, int reset, mb_stream stream);
 
+/* ---- image transform: the data loader's eval_transform (data/webdataset_reader.py:79-85: torchvision Resize -> CenterCrop -> ToTensor on a PIL
+ * image) and guided-diffusion's center_crop_arr (the ADM reference batches), bit for bit what Pillow computes (csrc/image.hip) ------------------- *
+ * Stateless: caller-owned buffers, no allocation, no synchronisation; additions, MB_ABI_VERSION unchanged.  One call is one PASS over B jobs:
+ * Pillow's antialiased resize (ImagingResample, 8 bits per channel) of each job's whole source to res_h x res_w with one filter -- 0 BOX,
+ * 1 BILINEAR, 2 BICUBIC (a = -0.5) --, horizontal pass first into a uint8 intermediate, then vertical, an axis whose size does not change skipped;
+ * of the result only the window [win_y, win_y + win_h) x [win_x, win_x + win_w) is computed and written (the crop; every output depends on its own
+ * taps alone, so this changes no bit).  The recipes ("reference": one pass; "adm": BOX halvings, each a pass with the window equal to the image,
+ * then a BICUBIC pass) are host arithmetic on sizes: maskbit_amd.ImageTransform.plan.
+ * A job (72 bytes; the host array and its device copy hold the same records):
+ *   src_offset   bytes from `src` to the source's pixel (0, 0); packed RGB, 3 bytes per pixel, rows src_stride bytes apart (any alignment)
+ *   dst_offset   PIXELS from the output bases to the job's first output: uint8 HWC [win_h, win_w, 3] at out_u8 + 3 dst_offset, float32 planes
+ *                [3, win_h, win_w] = byte / 255 (IEEE float32 division, what ToTensor() gives) at out_f32 + 3 dst_offset
+ *   work_offset, kx, ky   the job's slot in the workspace and the taps per output of its two coefficient tables: FILLED IN by
+ *                mb_image_workspace_bytes, which is therefore called on the host array before it is copied to the device
+ *   src_h, src_w, src_stride, res_h, res_w, win_y, win_x, win_h, win_w   as above; sides in [1, 16384], src_stride in [3 src_w, 2^20] */
+typedef struct {
+  int64_t src_offset, dst_offset, work_offset;
+  int32_t src_h, src_w, src_stride;
+  int32_t res_h, res_w;
+  int32_t win_y, win_x, win_h, win_w;
+  int32_t kx, ky;
+  int32_t reserved;
+} mb_image_job;
+/* Lays the B jobs of one pass out in a workspace (fills work_offset, kx, ky of every job; HOST array) and returns its size in bytes -- per job the
+ * two int32 coefficient tables and src_h rows of the intermediate; 0 for a job or a filter the pass does not take. */
+size_t mb_image_workspace_bytes(mb_image_job* jobs, int B, int filter);
+/* One pass: coefficients, horizontal, vertical + crop + formats, three launches over the whole ragged batch.  jobs_host: the laid-out records (read
+ * before returning, for the checks and the grid sizes); jobs_dev: their copy in device memory (8-byte aligned; the upload is the caller's, on this
+ * stream).  src .. src + src_bytes: the device buffer the sources lie in.  out_u8 / out_f32: either may be NULL, not both; out_pixels = pixels
+ * either holds (a job writes [dst_offset, dst_offset + win_h win_w)).  workspace: 16-byte aligned, workspace_bytes of it.
+ * Refused before any launch (-1, message prefixed "mb_image_resample:"): a NULL pointer among jobs, source and workspace; a filter outside 0 .. 2;
+ * a source side outside [1, 16384]; a window (the resolution R) below 1 or outside the resized image; a job that reads beyond src_bytes, writes
+ * beyond out_pixels, or does not carry the layout of mb_image_workspace_bytes; a workspace too small; B outside [1, 4096]. */
+int mb_image_resample(const mb_image_job* jobs_host, const mb_image_job* jobs_dev, int B, int filter, const uint8_t* src, size_t src_bytes,
+                      uint8_t* out_u8, float* out_f32, int64_t out_pixels, void* workspace, size_t workspace_bytes, mb_stream stream);
+
 /* ---- measurement hooks used by bench.py (not part of the reference surface) ----------------- */
 int mb_prof_enable(int on); /* 0 off; n >= 1: HIP-event timing of every kernel of every n-th generator forward (forwards n/2, n/2 + n, ..) and of all other calls */
 int mb_prof_read(char* buf, int buflen); /* host buffer; writes "name calls total_ms\n" lines */

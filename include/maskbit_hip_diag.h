@@ -300,6 +300,13 @@ int mb_session_admit_rows(const mb_session_rows* rows, int64_t* tokens, int A, i
 int mb_session_retire(const mb_session_rows* rows, int64_t* tokens, const int64_t* pred, int64_t* codes_all, int64_t* codes_out, int32_t* plan,
                       int A, int n, int m, int C, mb_stream stream);
 
+/* ---- the image transform's coefficient tables alone (image.hip; include/maskbit_hip.h "image transform"; tests/test_hip_image_transform.py): the
+ * coefficient kernel's own device function for outputs [first, first + count) of one axis resized from in_size to out_size, on caller-owned
+ * arrays -- xmin int32 [count], n int32 [count], taps int32 [count, ksize] (zero beyond n); ksize must be Pillow's (int)ceil(support) * 2 + 1, or 1
+ * for in_size == out_size (the identity table of a skipped axis).  Refused (-1, nothing launched): a NULL pointer, a filter outside 0 .. 2, a
+ * size outside [1, 16384], a range outside the axis, another ksize. */
+int mb_image_coeffs(int in_size, int out_size, int filter, int first, int count, int ksize, int32_t* xmin, int32_t* n, int32_t* taps, mb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

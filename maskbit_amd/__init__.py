@@ -12,6 +12,7 @@ from .evaluator import TokenizerEvaluator
 from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covariance, inception_score
 from .manifold import knn_radii, manifold_coverage, precision_recall
 from .lpips import LPIPS
+from .image_transform import ImageTransform, transformed
 from .inception import InceptionV3, get_inception_model
 from .editing import inpaint, sample_from_tokens
 from .checkpoint_check import CheckpointReport, check_checkpoint
@@ -25,4 +26,4 @@ __all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sa
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS",
            "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance",
            "InceptionV3", "get_inception_model", "check_checkpoint", "CheckpointReport",
-           "knn_radii", "manifold_coverage", "precision_recall"]
+           "knn_radii", "manifold_coverage", "precision_recall", "ImageTransform", "transformed"]

@@ -50,6 +50,12 @@ class SessionRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("label", "seed", "num_regen", "slot", "local_step", "N", "pool")] + [("max_active", C.c_int), ("max_steps", C.c_int)]
 
 
+class ImageJob(C.Structure):
+    """mb_image_job: one source of one resampling pass (72 bytes); ``work_offset``, ``kx``, ``ky`` are filled by mb_image_workspace_bytes."""
+    _fields_ = ([(n, C.c_int64) for n in ("src_offset", "dst_offset", "work_offset")]
+                + [(n, C.c_int32) for n in ("src_h", "src_w", "src_stride", "res_h", "res_w", "win_y", "win_x", "win_h", "win_w", "kx", "ky", "reserved")])
+
+
 # name -> (restype, argtypes); every symbol include/maskbit_hip.h (the ABI) and include/maskbit_hip_diag.h (single-kernel test entries) declare
 SIGNATURES = {
     "mb_gen_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
@@ -171,6 +177,10 @@ SIGNATURES = {
     "mb_knn_radii": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_manifold_cover": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "mb_image_workspace_bytes": (C.c_size_t, [C.POINTER(ImageJob), C.c_int, C.c_int]),
+    "mb_image_resample": (C.c_int, [C.POINTER(ImageJob), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mb_image_coeffs": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 4),
     "mb_inception_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "mb_inception_destroy": (None, [C.c_void_p]),
     "mb_inception_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

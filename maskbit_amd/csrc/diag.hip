@@ -9,6 +9,7 @@
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
 #include "mb_conv.h"
+#include "mb_image.h"
 #include "mb_kernels.h"
 #include "mb_spattn.h"
 #include "mb_vq.h"
@@ -595,6 +596,18 @@ int mb_session_retire(const mb_session_rows* rows, int64_t* tokens, const int64_
   if (const char* why = session_rows_check(rows, A, n, m, C, &gbits)) return fail(-1, "mb_session_retire: %s", why);
   if (!tokens || !pred || !codes_all || !codes_out || !plan) return fail(-1, "mb_session_retire: null argument");
   mb::session_retire((hipStream_t)stream, session_rows(rows), plan, tokens, pred, codes_all, codes_out, A, n, m, gbits, A, A / 2);   // (at most min(k, A - k) moves)
+  return launched();
+}
+
+// ---- the image transform's coefficient tables (image.hip) on caller-owned arrays
+int mb_image_coeffs(int in_size, int out_size, int filter, int first, int count, int ksize, int32_t* xmin, int32_t* n, int32_t* taps, mb_stream stream) {
+  if (!xmin || !n || !taps) return fail(-1, "mb_image_coeffs: null argument");
+  if (filter < 0 || filter > 2) return fail(-1, "mb_image_coeffs: filter is 0 (box), 1 (bilinear) or 2 (bicubic), got %d", filter);
+  if (in_size < 1 || in_size > mb::IMG_MAX_SIDE || out_size < 1 || out_size > mb::IMG_MAX_SIDE)
+    return fail(-1, "mb_image_coeffs: sizes in [1, %d] required (got %d -> %d)", mb::IMG_MAX_SIDE, in_size, out_size);
+  if (first < 0 || count < 1 || first > out_size - count) return fail(-1, "mb_image_coeffs: outputs [%d, %d + %d) outside [0, %d)", first, first, count, out_size);
+  if (ksize != mb::image_ksize(in_size, out_size, filter)) return fail(-1, "mb_image_coeffs: ksize %d, the axis has %d", ksize, mb::image_ksize(in_size, out_size, filter));
+  mb::image_coeffs_launch(in_size, out_size, filter, first, count, ksize, xmin, n, taps, (hipStream_t)stream);
   return launched();
 }
 
