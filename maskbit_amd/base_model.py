@@ -11,10 +11,13 @@ are the weight store the engine is (re)loaded from whenever they change.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import Callable, Dict, Iterable, Optional, Tuple, Union
 
 import torch
+
+from . import _lib
 
 
 class _Node(torch.nn.Module):
@@ -147,7 +150,31 @@ class BaseModel(torch.nn.Module):
         except Exception:
             pass
 
-    # subclasses provide: _engine_create(capacity) -> handle, _engine_destroy(handle), _engine_load(handle, key, tensor, stream)
+    # subclasses provide _engine_create(capacity) -> handle and _ABI, the family of their handle's entry points: mb_{_ABI}_load / _destroy /
+    # _saturation_count ("gen", "dec", "lpips", "inception", "taming")
+    _ABI = ""
+    _COUNTS = ""                       # what saturation_count() counts in this class, in words
+
+    def _engine_destroy(self, h) -> None:
+        getattr(_lib.load(), f"mb_{self._ABI}_destroy")(h)
+
+    def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
+        entry = f"mb_{self._ABI}_load"
+        shape = (C.c_int64 * t.dim())(*t.shape)
+        _lib.check(getattr(_lib.load(), entry)(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"{entry}({key})")
+
+    def saturation_count(self, reset: bool = True) -> int:
+        """What the current engine clamped at the fp16 range (+-65504) since the last reset -- the class's ``_COUNTS`` says what is counted; 0
+        without an engine.  A checkpoint whose activations need more range shows up here instead of being clipped silently.  Synchronises the
+        current stream."""
+        if self._engine is None:
+            return 0
+        entry = f"mb_{self._ABI}_saturation_count"
+        n = C.c_uint(0)
+        with torch.cuda.device(self._require_cuda("saturation_count")):
+            _lib.check(getattr(_lib.load(), entry)(self._engine, C.byref(n), 1 if reset else 0, torch.cuda.current_stream().cuda_stream), entry)
+        return int(n.value)
+
     def _ensure_engine(self, capacity: int):
         """Create (or grow) the device engine and (re)load weights if the torch parameters changed."""
         dev = self._require_cuda("forward")

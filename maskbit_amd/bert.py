@@ -85,6 +85,9 @@ def _generator_specs(d: int, f: int, depth: int, seq: int, bits: int, nclass: in
 
 
 class LFQBert(BaseModel):
+    _ABI = "gen"
+    _COUNTS = "lanes of the trunk's fp16 QKV / FFN-up epilogues that clamped a value: 0 for every configuration tested"
+
     def __init__(self, img_size=256, hidden_dim=768, codebook_size=1024, codebook_splits=1, depth=24, heads=8,
                  mlp_dim=3072, dropout=0.1, nclass=1000, input_stride: int = 16, use_prenorm: bool = False):
         super().__init__()
@@ -176,13 +179,6 @@ class LFQBert(BaseModel):
             prec = PREC_DIFF
         return prec
 
-    def _engine_destroy(self, h) -> None:
-        _lib.load().mb_gen_destroy(h)
-
-    def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.load().mb_gen_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_gen_load({key})")
-
     def engine(self, min_seqs: int):
         """Device engine able to hold ``min_seqs`` sequences (CFG needs 2 x batch)."""
         self._sig_hint = None
@@ -195,17 +191,6 @@ class LFQBert(BaseModel):
         finally:
             self._sig_hint = None
         return h
-
-    def saturation_count(self, reset: bool = True) -> int:
-        """Lanes of the trunk's fp16 QKV / FFN-up epilogues that clamped a value at +-65504 since the last reset (mb_gen_saturation_count): 0 for every
-        configuration tested; a checkpoint whose activations need more range shows up here instead of being clipped silently."""
-        if self._engine is None:
-            return 0
-        n = C.c_uint(0)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mb_gen_saturation_count(self._engine, C.byref(n), int(reset), torch.cuda.current_stream().cuda_stream),
-                       "mb_gen_saturation_count")
-        return int(n.value)
 
     def _check_labels(self, labels: torch.Tensor) -> None:
         """Host-resident labels are range-checked here (an out-of-range class would index past class_emb, where the

@@ -29,7 +29,8 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .base_model import BaseModel, ParamSpec
+from .base_model import ParamSpec
+from .tokenizer import TokenizerModel, _ptr
 
 
 def _cfg_get(config, key, default=None):
@@ -105,7 +106,11 @@ def legacy_to_canonical(state_dict, num_resolutions: int):
     return {_legacy_level(k, num_resolutions): v for k, v in state_dict.items()}
 
 
-class ConvVQModel(BaseModel):
+class ConvVQModel(TokenizerModel):
+    _ABI, _DECODE, _DECODE_LATENT, _ENCODE = "dec", "mb_dec_decode", "mb_dec_decode_latent", "mb_enc_encode_vq"
+    _COUNTS = ("4-channel activation groups clamped (the activations are stored as fp16), over every conv layer of decode / encode calls: 0 for "
+               "every configuration tested")
+
     def __init__(self, config, legacy: bool = False, finetune_decoder: bool = False):
         super().__init__()
         qt = _cfg_get(config, "quantizer_type", "lookup-free")
@@ -141,7 +146,6 @@ class ConvVQModel(BaseModel):
         if self.legacy:
             specs = [(_legacy_level(k, self.num_resolutions), shape, kind) for k, shape, kind in specs]
         self._build(specs)
-        self._latent_size = 16
         if qt == "lookup":                                                                  # quantizer.py:36-37
             self._attach("quantize.embedding.weight",
                          torch.empty(self.codebook_size, self.token_size).uniform_(-1.0 / self.codebook_size, 1.0 / self.codebook_size))
@@ -173,153 +177,60 @@ class ConvVQModel(BaseModel):
         _lib.check(_lib.load().mb_dec_create(C.byref(cfg), capacity, C.byref(h)), "mb_dec_create")
         return h
 
-    def _engine_destroy(self, h) -> None:
-        _lib.load().mb_dec_destroy(h)
-
     def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
         if self.legacy:
             key = _legacy_level(key, self.num_resolutions)                  # the engine speaks the canonical layout
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.load().mb_dec_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_dec_load({key})")
+        super()._engine_load(h, key, t, stream)
 
-    def engine(self, min_batch: int, latent_size: int = 16):
-        if latent_size != self._latent_size:
-            self._drop_engine()
-            self._latent_size = latent_size
-        have = self._engine_key[1] if self._engine_key else 0
-        return self._ensure_engine(max(min_batch, have, 8))
-
-    # ---- decode -----------------------------------------------------------------------------
-    def _decode_codes(self, codes: torch.Tensor, want_u8: bool = False):
-        dev = self._require_cuda("decode_tokens")
-        b, n = codes.shape
+    # ---- shapes -----------------------------------------------------------------------------
+    def _grid_side(self, n: int) -> int:
         side = int(math.sqrt(float(n)))
         if side * side != n:
             raise ValueError(f"decode_tokens expects a square token grid, got {n} tokens")
-        res = side << (self.num_resolutions - 1)
-        img = torch.empty((b, self.num_channels, res, res), dtype=torch.float32, device=dev)
-        u8 = torch.empty((b, res, res, self.num_channels), dtype=torch.uint8, device=dev) if want_u8 else None
-        h = self.engine(b, side)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_dec_decode(h, codes.data_ptr(), img.data_ptr(), u8.data_ptr() if want_u8 else None, b,
-                                                 torch.cuda.current_stream().cuda_stream), "mb_dec_decode")
-        return (img, u8) if want_u8 else img
+        return side
 
-    @torch.no_grad()
-    def decode_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
-        """tokens [b, n] of any numeric dtype (the sampler hands float32, factorization.py:19) -> image."""
-        dev = self._require_cuda("decode_tokens")
-        self._check_codes(tokens)
-        return self._decode_codes(tokens.to(dev).long().contiguous())
+    def _latent_side(self, h: int, w: int) -> int:
+        if h != w or h % 16:
+            raise ValueError(f"decode expects a square latent grid with a side that is a multiple of 16, got {h}x{w}")
+        return h
 
-    def _check_codes(self, tokens: torch.Tensor) -> None:
-        """Host-resident codes of a lookup tokenizer are range-checked (nn.Embedding raises IndexError, quantizer.py:115); device-resident
-        ones are clamped to [0, codebook_size) in the gather kernel, with no host synchronisation."""
-        if self.quantizer_type == "lookup" and tokens.device.type == "cpu" and tokens.numel():
-            t = tokens.long()
-            if int(t.min()) < 0 or int(t.max()) >= self.codebook_size:
-                raise IndexError(f"code outside [0, {self.codebook_size})")
-
-    def saturation_count(self, reset: bool = True) -> int:
-        """Number of 4-channel activation groups the engine clamped at the fp16 range (+-65504) since the last reset, over every conv layer
-        of decode / encode calls on the current engine.  0 for every configuration tested; a checkpoint whose activations need more range
-        shows up here (the activations are stored as fp16) instead of being clipped silently.  Synchronises the current stream."""
-        if self._engine is None:
-            return 0
-        import ctypes as C
-        n = C.c_uint(0)
-        dev = self._require_cuda("saturation_count")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_dec_saturation_count(self._engine, C.byref(n), 1 if reset else 0, torch.cuda.current_stream().cuda_stream),
-                       "mb_dec_saturation_count")
-        return int(n.value)
-
-    @torch.no_grad()
-    def decode_tokens_uint8(self, tokens: torch.Tensor):
-        """-> (image fp32 NCHW, uint8 NHWC = trunc(clamp(x,0,1)*255)) in one pass (eval_maskbit.py:134-135 fused)."""
-        dev = self._require_cuda("decode_tokens")
-        self._check_codes(tokens)
-        return self._decode_codes(tokens.to(dev).long().contiguous(), want_u8=True)
-
-    @torch.no_grad()
-    def decode(self, z_quantized: torch.Tensor) -> torch.Tensor:
-        """z [b, K, h, w] -> image.  Lookup tokenizer: any float latent (ConvDecoder.forward on it, ``mb_dec_decode_latent``).
-        LFQ: z in {-1,+1} only; LFQ latents are exactly the bit pattern of a code, so the latent is re-packed to codes (sign -> bit,
-        LSB first) and decoded through the token path."""
-        dev = self._require_cuda("decode")
-        if z_quantized.dim() != 4 or z_quantized.shape[1] != self.token_size:
-            raise ValueError(f"decode expects [b, {self.token_size}, h, w], got {tuple(z_quantized.shape)}")
-        if self.quantizer_type == "lookup":
-            return self._decode_latent(z_quantized)
-        z = z_quantized.to(dev)
-        if not bool(((z == 1) | (z == -1)).all()):
-            raise ValueError("decode(): the HIP decoder takes quantized LFQ latents (+-1) only")
-        w = (2 ** torch.arange(self.token_size, device=dev)).view(1, -1, 1, 1)
-        codes = ((z > 0).long() * w).sum(1).reshape(z.shape[0], -1)
-        return self._decode_codes(codes.contiguous())
-
-    def _decode_latent(self, z_quantized: torch.Tensor) -> torch.Tensor:
-        dev = self._require_cuda("decode")
-        b, _, hh, ww = z_quantized.shape
-        if hh != ww or hh % 16:
-            raise ValueError(f"decode expects a square latent grid with a side that is a multiple of 16, got {hh}x{ww}")
-        z = z_quantized.to(device=dev, dtype=torch.float32).contiguous()
-        res = hh << (self.num_resolutions - 1)
-        img = torch.empty((b, self.num_channels, res, res), dtype=torch.float32, device=dev)
-        h = self.engine(b, hh)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_dec_decode_latent(h, z.data_ptr(), img.data_ptr(), None, b, torch.cuda.current_stream().cuda_stream),
-                       "mb_dec_decode_latent")
-        return img
-
-    @torch.no_grad()
-    def _encode(self, x: torch.Tensor, want_raw: bool = False, want_dist: bool = False):
-        dev = self._require_cuda("encode")
-        if x.dim() != 4 or x.shape[1] != self.num_channels:
-            raise ValueError(f"encode expects [b, {self.num_channels}, H, W], got {tuple(x.shape)}")
-        b, _, H, W = x.shape
+    def _image_side(self, H: int, W: int) -> int:
         down = 1 << (self.num_resolutions - 1)
         if H != W or H % (16 * down):
             raise ValueError(f"encode expects square images with a side that is a multiple of {16 * down}, got {H}x{W}")
-        side = H // down
-        img = x.to(device=dev, dtype=torch.float32).contiguous()
-        idx = torch.empty((b, side, side), dtype=torch.int64, device=dev)
-        zq = torch.empty((b, self.token_size, side, side), dtype=torch.float32, device=dev)
-        zraw = torch.empty_like(zq) if want_raw else None
-        h = self.engine(b, side)
+        return H // down
+
+    # ---- the LFQ branches ---------------------------------------------------------------------
+    def _decode_latent(self, z_quantized: torch.Tensor) -> torch.Tensor:
+        """Lookup tokenizer: any float latent (ConvDecoder.forward on it, ``mb_dec_decode_latent``).  LFQ: z in {-1,+1} only; LFQ latents are
+        exactly the bit pattern of a code, so the latent is re-packed to codes (sign -> bit, LSB first) and decoded through the token path."""
         if self.quantizer_type == "lookup":
-            dist = torch.empty((b, side, side), dtype=torch.float32, device=dev) if want_dist else None
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().mb_enc_encode_vq(h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), zraw.data_ptr() if want_raw else None,
-                                                        dist.data_ptr() if want_dist else None, b, torch.cuda.current_stream().cuda_stream),
-                           "mb_enc_encode_vq")
-            return (zq, idx, zraw, dist) if want_dist else (zq, idx, zraw)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_enc_encode(h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), zraw.data_ptr() if want_raw else None, b,
-                                                 torch.cuda.current_stream().cuda_stream), "mb_enc_encode")
-        return zq, idx, zraw
+            return super()._decode_latent(z_quantized)
+        z = z_quantized.to(self._require_cuda("decode"))
+        if not bool(((z == 1) | (z == -1)).all()):
+            raise ValueError("decode(): the HIP decoder takes quantized LFQ latents (+-1) only")
+        w = (2 ** torch.arange(self.token_size, device=z.device)).view(1, -1, 1, 1)
+        codes = ((z > 0).long() * w).sum(1).reshape(z.shape[0], -1)
+        return self._decode_codes(codes.contiguous())
+
+    def _encode_call(self, h, img, idx, zq, zraw, dist, b: int) -> None:
+        if self.quantizer_type == "lookup":
+            return super()._encode_call(h, img, idx, zq, zraw, dist, b)
+        self._call("mb_enc_encode", h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), _ptr(zraw), b)
+
+    def _encode(self, x: torch.Tensor, want_raw: bool = False, want_dist: bool = False):
+        """-> (zq, idx, zraw), and (zq, idx, zraw, dist) only for a lookup tokenizer asked for the distances"""
+        want_dist = want_dist and self.quantizer_type == "lookup"
+        out = super()._encode(x, want_raw, want_dist)
+        return out if want_dist else out[:3]
 
     def encode(self, x: torch.Tensor):
-        """ConvVQModel.encode (conv_vqgan.py:70-83): image -> (z_quantized [b,K,h,w] in {-1,+1}, result_dict) with
-        ``min_encoding_indices`` [b,h,w] (lookup_free.py:57-95).  Inference only: the quantizer losses are returned as zeros
-        except the commitment term, which needs the pre-sign latent and is not computed on this path.
-        Lookup tokenizer (SimpleVectorizer.forward, quantizer.py:45-103, eval mode): z_quantized = the selected codebook rows (L2-normalised
-        when configured); codebook_loss = mean((zq - z)^2) from the kernel's per-row squared distances, commitment_loss = commitment_cost *
-        codebook_loss, quantizer_loss their sum; the entropy terms are zero (the reference computes them only in training)."""
+        """ConvVQModel.encode (conv_vqgan.py:70-83): image -> (z_quantized [b,K,h,w], result_dict) with ``min_encoding_indices`` [b,h,w].
+        LFQ (lookup_free.py:57-95): z_quantized in {-1,+1}; inference only: the quantizer losses are returned as zeros except the commitment
+        term, which needs the pre-sign latent and is not computed on this path.  Lookup tokenizer: ``TokenizerModel.encode``."""
         if self.quantizer_type == "lookup":
-            zq, idx, _, dist = self._encode(x, want_dist=True)
-            codebook_loss = (dist.sum() / float(dist.numel() * self.token_size)).reshape(())
-            commitment_loss = self.commitment_cost * codebook_loss
-            zero = torch.zeros((), device=zq.device)
-            return zq, dict(quantizer_loss=commitment_loss + codebook_loss, commitment_loss=commitment_loss, codebook_loss=codebook_loss,
-                            entropy_loss=zero, per_sample_entropy=zero, avg_entropy=zero, min_encoding_indices=idx)
+            return super().encode(x)
         zq, idx, _ = self._encode(x)
         zero = torch.zeros((), device=zq.device)
         return zq, dict(quantizer_loss=zero, commitment_loss=zero, entropy_loss=zero, per_sample_entropy=zero, avg_entropy=zero,
                         min_encoding_indices=idx)
-
-    def forward(self, input: torch.Tensor):
-        """ConvVQModel.forward (conv_vqgan.py:114-127): (decode(encode(x)), result_dict)."""
-        zq, result = self.encode(input)
-        codes = result["min_encoding_indices"].reshape(zq.shape[0], -1)
-        return self._decode_codes(codes.contiguous()), result

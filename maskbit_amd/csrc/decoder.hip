@@ -1,23 +1,19 @@
 // The tokenizer handle of libmaskbit_hip.so (mb_dec_* / mb_enc_*, include/maskbit_hip.h): the conv-VQGAN decoder (ConvDecoder.forward,
 // modeling/modules/autoencoder.py:399-423) and, when built, its encoder (ConvEncoder, :230-286) with the LFQ or the lookup (VQ) quantizer.
-// This file is the layer schedule and the checkpoint ingest; the kernels and their launchers are conv.hip (mb_conv.h) and vq.hip (mb_vq.h).
+// This file is the layer schedule and the entry points; the ResNet block and the checkpoint ingest are shared with the Taming handle (mb_autoenc.h),
+// the kernels and their launchers are conv.hip (mb_conv.h) and vq.hip (mb_vq.h).
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/maskbit_hip.h"
-#include "mb_abi.h"
-#include "mb_conv.h"
+#include "mb_autoenc.h"
 #include "mb_vq.h"
 
 namespace mb {
-struct ResBlock { Norm n1, n2; Conv c1, c2, sc; bool has_sc = false; };
 struct Stage { std::vector<ResBlock> blocks; Conv up; bool has_up = false; };   // `up`: upsample_conv (decoder) / down_conv (encoder)
-// where a checkpoint entry goes (mb_dec_load): a convolution's weight or bias, or the `n` values of a norm's gamma / beta
-struct Param { Conv* conv = nullptr; bool bias = false; float* vec = nullptr; int n = 0; };
 }  // namespace mb
 
-struct mb_dec {
+struct mb_dec : mb::AutoEnc {
   mb_dec_cfg c{};
   int max_batch = 0, out_res = 0;
   mb::Conv conv_in, conv_out;
@@ -30,77 +26,27 @@ struct mb_dec {
   mb::Norm e_norm_out;
   std::vector<mb::ResBlock> e_mid;
   std::vector<mb::Stage> e_down;
-  h16* buf[3] = {nullptr, nullptr, nullptr};
   h16* z = nullptr;              // decoder input latent, [max_batch * latent^2][conv_in.cin_pad]
-  // lookup quantizer (mb_dec_create_vq; SimpleVectorizer, modeling/quantizer/quantizer.py): the prepared codebook and the search buffers
-  bool vq = false, cb_loaded = false;
-  mb::VqCodebook q;
-  float* vq_zT = nullptr;        // [Kp/4][Npad][4] rows of the encoder output (normalised when l2)
-  float* vq_ps = nullptr;        // [VQ_SPLIT_MAX][Npad] per-split best score ...
-  int* vq_pi = nullptr;          // ... and its entry
-  unsigned* sat = nullptr;  // device counter: fp16 clamps in the conv epilogues since the last read
-  mb::GnCtx gn;
-  // checkpoint key -> slot, filled as create_handle names each parameter.  The Conv pointers are into this struct and its vectors, which are sized
-  // before their elements are named and never again.
-  std::unordered_map<std::string, mb::Param> params;
-  mb::DevArena mem;
+  // lookup quantizer (mb_dec_create_vq; SimpleVectorizer, modeling/quantizer/quantizer.py): allocated on a lookup handle only
+  bool lookup = false;
+  mb::VqWorkspace vq;
 };
 
 using namespace mb;
 
 namespace {
 
-void name_conv(mb_dec* d, Conv& c, const std::string& name) {
-  d->params[name + ".weight"] = Param{&c, false};
-  if (c.has_bias) d->params[name + ".bias"] = Param{&c, true};
-}
-void init_conv(mb_dec* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool bias, bool up, bool final_) {
-  c.sat = d->sat;
-  shape_conv(c, cin, cout, ks, bias, up, final_);
-  d->mem.get(&c.w, conv_weight_elems(c));
-  if (bias) d->mem.zeroed(&c.b, (size_t)c.cout_pad);
-  name_conv(d, c, name);
-}
-void init_norm(mb_dec* d, Norm& n, const std::string& name, int c) {
-  n.c = c;
-  d->mem.get(&n.g, (size_t)c);
-  d->mem.get(&n.b, (size_t)c);
-  d->params[name + ".weight"] = Param{nullptr, false, n.g, c};
-  d->params[name + ".bias"] = Param{nullptr, false, n.b, c};
-}
-void init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout) {
-  rb.has_sc = cin != cout;
-  init_norm(d, rb.n1, p + ".norm1", cin);
-  init_conv(d, rb.c1, p + ".conv1", cin, cout, 3, false, false, false);
-  init_norm(d, rb.n2, p + ".norm2", cout);
-  init_conv(d, rb.c2, p + ".conv2", cout, cout, 3, false, false, false);
-  if (rb.has_sc) init_conv(d, rb.sc, p + ".nin_shortcut", cout, cout, 1, false, false, false);
-}
-
-// x (buffer index xi) -> returns the buffer index holding the block output
-int run_block(hipStream_t s, mb_dec* d, const ResBlock& rb, int xi, int B, int H, int W) {
-  const int t1 = (xi + 1) % 3, t2 = (xi + 2) % 3;
-  launch_gn(s, &d->gn, rb.n1, d->buf[xi], B, H * W);
-  launch_conv(s, &d->gn, rb.c1, d->buf[xi], d->gn.ss, nullptr, d->buf[t1], nullptr, nullptr, B, H, W, false);
-  launch_gn(s, &d->gn, rb.n2, d->buf[t1], B, H * W);
-  if (!rb.has_sc) {
-    launch_conv(s, &d->gn, rb.c2, d->buf[t1], d->gn.ss, d->buf[xi], d->buf[t2], nullptr, nullptr, B, H, W, false);
-    return t2;
-  }
-  // shortcut quirk (autoencoder.py:72-73,93-96): out = h + nin_shortcut(h); the block input is dropped
-  launch_conv(s, &d->gn, rb.c2, d->buf[t1], d->gn.ss, nullptr, d->buf[t2], nullptr, nullptr, B, H, W, false, false);   // read by the shortcut conv, not by a GroupNorm
-  launch_conv(s, &d->gn, rb.sc, d->buf[t2], nullptr, d->buf[t2], d->buf[t1], nullptr, nullptr, B, H, W, false);
-  return t1;
-}
+// ResBlock of autoencoder.py:46-96: convolutions without bias, the shortcut on the block's own output (ResBlock::sc_on_input = false)
+void init_block(mb_dec* d, ResBlock& rb, const std::string& p, int cin, int cout) { mb::init_block(*d, rb, p, cin, cout, false, false); }
 
 // ConvDecoder.forward (autoencoder.py:399-423) from the latent in d->z
 void decode_from_z(mb_dec* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s) {
   int res = d->c.latent_size;
   launch_conv(s, &d->gn, d->conv_in, d->z, nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
-  for (auto& rb : d->mid) xi = run_block(s, d, rb, xi, B, res, res);
+  for (auto& rb : d->mid) xi = run_block(s, *d, rb, xi, B, res, res);
   for (auto& st : d->up) {
-    for (auto& rb : st.blocks) xi = run_block(s, d, rb, xi, B, res, res);
+    for (auto& rb : st.blocks) xi = run_block(s, *d, rb, xi, B, res, res);
     if (st.has_up) {
       res *= 2;
       const int t = (xi + 1) % 3;
@@ -120,7 +66,7 @@ int encode_to_z(mb_dec* d, const float* img, int B, hipStream_t s, int* res_out)
   launch_conv(s, &d->gn, d->e_conv_in, d->buf[2], nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
   for (auto& st : d->e_down) {
-    for (auto& rb : st.blocks) xi = run_block(s, d, rb, xi, B, res, res);
+    for (auto& rb : st.blocks) xi = run_block(s, *d, rb, xi, B, res, res);
     if (st.has_up) {
       const int t = (xi + 1) % 3, t2 = (xi + 2) % 3;
       if (!c.sample_with_conv) {                           // F.avg_pool2d(2, 2) (autoencoder.py:182)
@@ -136,7 +82,7 @@ int encode_to_z(mb_dec* d, const float* img, int B, hipStream_t s, int* res_out)
       xi = t2;
     }
   }
-  for (auto& rb : d->e_mid) xi = run_block(s, d, rb, xi, B, res, res);
+  for (auto& rb : d->e_mid) xi = run_block(s, *d, rb, xi, B, res, res);
   launch_gn(s, &d->gn, d->e_norm_out, d->buf[xi], B, res * res);
   const int t = (xi + 1) % 3;
   launch_conv(s, &d->gn, d->e_conv_out, d->buf[xi], d->gn.ss, nullptr, d->buf[t], nullptr, nullptr, B, res, res, false);
@@ -162,7 +108,7 @@ int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int co
   std::vector<int> mult(cfg.channel_mult, cfg.channel_mult + R);
   mult.push_back(cfg.channel_mult[R - 1]);
   const int top = hc * cfg.channel_mult[R - 1];
-  init_conv(d, d->conv_in, "decoder.conv_in", cfg.token_size, top, 3, true, false, false);
+  init_conv(*d, d->conv_in, "decoder.conv_in", cfg.token_size, top, 3, true, false, false);
   d->mid.resize(cfg.num_res_blocks);
   for (int r = 0; r < cfg.num_res_blocks; ++r) init_block(d, d->mid[r], "decoder.mid.res_blocks." + std::to_string(r), top, top);
   d->up.resize(R);
@@ -182,19 +128,19 @@ int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int co
     max_elems = std::max(max_elems, (size_t)res * res * std::max(cin, cout));
     st.has_up = lvl > 0;
     if (st.has_up) {
-      init_conv(d, st.up, "decoder.up." + std::to_string(s) + ".upsample_conv", cout, cout, 3, true, true, false);
+      init_conv(*d, st.up, "decoder.up." + std::to_string(s) + ".upsample_conv", cout, cout, 3, true, true, false);
       res *= 2;
       max_elems = std::max(max_elems, (size_t)res * res * cout);
     }
     last = cout;
   }
-  init_norm(d, d->norm_out, "decoder.norm_out", last);
-  init_conv(d, d->conv_out, "decoder.conv_out", last, cfg.num_channels, 3, true, false, true);
+  init_norm(*d, d->norm_out, "decoder.norm_out", last);
+  init_conv(*d, d->conv_out, "decoder.conv_out", last, cfg.num_channels, 3, true, false, true);
   if (cfg.build_encoder) {                                // ConvEncoder (autoencoder.py:230-262): mirrors the decoder top-down
     const int enrb = cfg.enc_res_blocks > 0 ? cfg.enc_res_blocks : cfg.num_res_blocks;
     std::vector<int> imult{1};
     imult.insert(imult.end(), cfg.channel_mult, cfg.channel_mult + R);
-    init_conv(d, d->e_conv_in, "encoder.conv_in", cfg.num_channels, hc, 3, false, false, false);
+    init_conv(*d, d->e_conv_in, "encoder.conv_in", cfg.num_channels, hc, 3, false, false, false);
     d->e_down.resize(R);
     for (int s = 0; s < R; ++s) {
       const int cin = hc * imult[s], cout = hc * imult[s + 1];
@@ -208,19 +154,16 @@ int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int co
       st.has_up = s < R - 1;                              // a downsampling step follows: down_conv, or avg_pool2d when !sample_with_conv
       st.up.cin = cout;
       if (st.has_up && cfg.sample_with_conv) {            // DownsamplingStage.down_conv: 3x3, stride 2, bias (autoencoder.py:165)
-        Conv& dc = st.up;
-        dc.sat = d->sat;
-        shape_down_conv(dc, cout);
-        m.get(&dc.w, conv_weight_elems(dc));
-        m.zeroed(&dc.b, (size_t)dc.cout_pad);
-        name_conv(d, dc, "encoder.down." + std::to_string(s) + ".down_conv");
+        shape_down_conv(st.up, cout);
+        alloc_conv(*d, st.up);
+        name_conv(*d, st.up, "encoder.down." + std::to_string(s) + ".down_conv");
       }
     }
     d->e_mid.resize(enrb);
     for (int r = 0; r < enrb; ++r) init_block(d, d->e_mid[r], "encoder.mid.res_blocks." + std::to_string(r), top, top);
     const int k4 = (cfg.token_size + 3) / 4 * 4;           // stored channel count of z (8-byte stores)
-    init_norm(d, d->e_norm_out, "encoder.norm_out", top);
-    init_conv(d, d->e_conv_out, "encoder.conv_out", top, k4, 1, true, false, false);
+    init_norm(*d, d->e_norm_out, "encoder.norm_out", top);
+    init_conv(*d, d->e_conv_out, "encoder.conv_out", top, k4, 1, true, false, false);
     d->e_conv_out.cout_w = cfg.token_size;
     d->has_enc = true;
   }
@@ -229,14 +172,8 @@ int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int co
   m.get(&d->z, nlat * d->conv_in.cin_pad);
   m.get(&d->gn.part, gn_part_elems(max_batch, d->out_res, d->out_res));
   m.get(&d->gn.ss, (size_t)max_batch * 4096);
-  if (vq) {
-    VqCodebook& q = d->q;
-    q.C = codebook_size; q.K = cfg.token_size; q.Kp = vq_kp(q.K); q.Cpad = vq_cpad(q.C); q.l2 = l2_normalize ? 1 : 0;
-    const size_t npad = (size_t)vq_npad((int)nlat);
-    m.get(&q.cb, (size_t)q.C * q.K); m.get(&q.cbT, (size_t)q.Kp * q.Cpad); m.get(&q.cbn, (size_t)q.Cpad);
-    m.get(&d->vq_zT, (size_t)q.Kp * npad); m.get(&d->vq_ps, VQ_SPLIT_MAX * npad); m.get(&d->vq_pi, VQ_SPLIT_MAX * npad);
-    d->vq = true;
-  }
+  d->lookup = vq;
+  if (vq) d->vq.alloc(m, codebook_size, cfg.token_size, l2_normalize, nlat);
   if (int rc = m.failed(what)) { delete d; return rc; }
   *out = d;
   return 0;
@@ -246,14 +183,12 @@ int create_handle(const char* what, const mb_dec_cfg& cfg, int max_batch, int co
 int encode_vq(const char* what, mb_dec* d, const float* img, int64_t* indices, float* zq, float* zraw, float* row_dist, int B, hipStream_t s) {
   ProfScope p("encode", s);
   if (!d->has_enc) return fail(-1, "%s: this engine was created without the encoder half (mb_dec_cfg.build_encoder)", what);
-  if (!d->vq) return fail(-1, "%s: not a lookup (VQ) handle", what);
-  if (!d->cb_loaded) return fail(-1, "%s: the codebook (quantize.embedding.weight) is not loaded", what);
+  if (!d->lookup) return fail(-1, "%s: not a lookup (VQ) handle", what);
+  if (!d->vq.loaded) return fail(-1, "%s: the codebook (quantize.embedding.weight) is not loaded", what);
   if (B <= 0 || B > d->max_batch) return fail(-1, "%s: batch outside [1, max_batch]", what);
   int res = 0;
   const int t = encode_to_z(d, img, B, s, &res);
-  const int hw = res * res, N = B * hw;
-  vq_prep_rows(d->q, d->buf[t], d->e_conv_out.cout, nullptr, N, hw, d->vq_zT, zraw, s);
-  vq_search(d->q, d->vq_zT, N, hw, vq_splits(d->q, N, 0), d->vq_ps, d->vq_pi, indices, zq, row_dist, s);
+  d->vq.encode_rows(d->buf[t], d->e_conv_out.cout, B * res * res, res * res, indices, zq, zraw, row_dist, s);
   return launched();
 }
 
@@ -276,31 +211,15 @@ int mb_dec_load(mb_dec* d, const char* name, const float* data, const int64_t* s
   if (!d || !name || !data) return fail(-1, "mb_dec_load: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const std::string n(name);
-  if (d->vq && n == "quantize.embedding.weight") {                               // SimpleVectorizer.embedding [C, K]
-    if (ndim != 2 || shape[0] != d->q.C || shape[1] != d->q.K) return fail(-4, "mb_dec_load: %s: expected [codebook_size, token_size]", name);
-    vq_prep_codebook(d->q, data, s);
-    d->cb_loaded = true;
-    return 0;
+  if (d->lookup && n == "quantize.embedding.weight") {                           // SimpleVectorizer.embedding [C, K]
+    if (!d->vq.load_codebook(shape, ndim, data, s)) return fail(-4, "mb_dec_load: %s: expected [codebook_size, token_size]", name);
+    return launched();
   }
   if (n.rfind("quantize.", 0) == 0) return 0;                                    // derived buffers
   if (n.rfind("encoder.", 0) == 0 && !d->has_enc) return 0;                       // encode half not built in this engine
   size_t numel = 1;
   for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  const auto it = d->params.find(n);
-  if (it == d->params.end()) return fail(-2, "mb_dec_load: unknown checkpoint entry '%s'", name);
-  const Param& p = it->second;
-  if (!p.conv) {
-    if (numel != (size_t)p.n) return fail(-4, "mb_dec_load: %s: wrong norm size", name);
-    HIP_TRY(hipMemcpyAsync(p.vec, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else if (p.bias) {
-    if (numel != (size_t)p.conv->cout_w) return fail(-4, "mb_dec_load: %s: wrong bias size", name);
-    HIP_TRY(hipMemcpyAsync(p.conv->b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else {
-    const Conv& c = *p.conv;                                                     // (down_conv: the checkpoint's 3x3, whatever the taps it runs as)
-    if (numel != (size_t)c.cout_w * c.cin * (c.down ? 9 : c.ks * c.ks)) return fail(-4, "mb_dec_load: %s: wrong weight size", name);
-    launch_repack_conv(s, c, data);
-  }
-  return 0;
+  return load_param("mb_dec_load", *d, name, data, numel, s);
 }
 
 int mb_dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* img_nhwc_u8, int B, mb_stream stream) {
@@ -310,9 +229,9 @@ int mb_dec_decode(mb_dec* d, const int64_t* tokens, float* img_nchw, uint8_t* im
   if (B <= 0 || B > d->max_batch) return fail(-1, "mb_dec_decode: batch outside [1, max_batch]");
   const mb_dec_cfg& c = d->c;
   const size_t npix = (size_t)B * c.latent_size * c.latent_size;
-  if (d->vq) {                                        // SimpleVectorizer.get_codebook_entry (quantizer.py:105-119): codebook rows
-    if (!d->cb_loaded) return fail(-1, "mb_dec_decode: the codebook (quantize.embedding.weight) is not loaded");
-    vq_gather(d->q, tokens, npix, d->z, d->conv_in.cin_pad, d->sat, s);
+  if (d->lookup) {                                    // SimpleVectorizer.get_codebook_entry (quantizer.py:105-119): codebook rows
+    if (!d->vq.loaded) return fail(-1, "mb_dec_decode: the codebook (quantize.embedding.weight) is not loaded");
+    vq_gather(d->vq.q, tokens, npix, d->z, d->conv_in.cin_pad, d->sat, s);
   } else {
     launch_latent(s, tokens, d->z, npix, c.token_size);
   }
@@ -323,7 +242,7 @@ int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_
   if (!d || !z_nchw) return fail(-1, "mb_dec_decode_latent: null argument");
   hipStream_t s = (hipStream_t)stream;
   ProfScope p("decode", s);
-  if (!d->vq) return fail(-1, "mb_dec_decode_latent: decode of a float latent needs a lookup (VQ) handle");
+  if (!d->lookup) return fail(-1, "mb_dec_decode_latent: decode of a float latent needs a lookup (VQ) handle");
   if (B <= 0 || B > d->max_batch) return fail(-1, "mb_dec_decode_latent: batch outside [1, max_batch]");
   const int hw = d->c.latent_size * d->c.latent_size;
   vq_pack_latent(z_nchw, B, d->c.token_size, hw, d->z, d->conv_in.cin_pad, d->sat, s);
@@ -334,18 +253,14 @@ int mb_dec_decode_latent(mb_dec* d, const float* z_nchw, float* img_nchw, uint8_
 // synchronises the stream
 int mb_dec_saturation_count(mb_dec* d, unsigned* count, int reset, mb_stream stream) {
   if (!d || !count) return fail(-1, "mb_dec_saturation_count: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(count, d->sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      (reset && hipMemsetAsync(d->sat, 0, sizeof(unsigned), s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
-    return fail(-10, "mb_dec_saturation_count: copy failed");
-  return 0;
+  return read_counter("mb_dec_saturation_count", d->sat, count, reset, (hipStream_t)stream);
 }
 
 // ConvVQModel.encode (conv_vqgan.py:70-83): image [B,C,H,W] fp32 -> code indices [B, h*w] (+ optional +-1 latent / raw z, fp32 NCHW)
 int mb_enc_encode(mb_dec* d, const float* img_nchw, int64_t* indices, float* zq, float* zraw, int B, mb_stream stream) {
   if (!d || !img_nchw || !indices) return fail(-1, "mb_enc_encode: null argument");
   hipStream_t s = (hipStream_t)stream;
-  if (d->vq) return encode_vq("mb_enc_encode", d, img_nchw, indices, zq, zraw, nullptr, B, s);
+  if (d->lookup) return encode_vq("mb_enc_encode", d, img_nchw, indices, zq, zraw, nullptr, B, s);
   ProfScope p("encode", s);
   if (!d->has_enc) return fail(-1, "mb_enc_encode: this engine was created without the encoder half (mb_dec_cfg.build_encoder)");
   if (B <= 0 || B > d->max_batch) return fail(-1, "mb_enc_encode: batch outside [1, max_batch]");

@@ -669,10 +669,7 @@ int mb_gen_set_walk(mb_gen* g, int mode) {
 
 int mb_gen_saturation_count(mb_gen* g, unsigned* count, int reset, mb_stream stream) {
   if (!g || !count) return fail(-1, "mb_gen_saturation_count: null argument");
-  HIP_TRY(hipMemcpyAsync(count, g->sat, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  if (reset) HIP_TRY(hipMemsetAsync(g->sat, 0, sizeof(unsigned), (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return 0;
+  return mb::read_counter("mb_gen_saturation_count", g->sat, count, reset, (hipStream_t)stream);
 }
 
 int mb_gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits,

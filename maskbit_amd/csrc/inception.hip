@@ -632,11 +632,7 @@ int mb_inception_forward_spatial(mb_inception* h, const uint8_t* u8, int B, int 
 // synchronises the stream
 int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream) {
   if (!h || !count) return fail(-1, "mb_inception_saturation_count: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(count, h->sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      (reset && hipMemsetAsync(h->sat, 0, sizeof(unsigned), s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
-    return fail(-10, "mb_inception_saturation_count: copy failed");
-  return 0;
+  return read_counter("mb_inception_saturation_count", h->sat, count, reset, (hipStream_t)stream);
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----

@@ -314,11 +314,7 @@ int mb_lpips_forward(mb_lpips* h, const float* real, const float* fake, int B, i
 // synchronises the stream
 int mb_lpips_saturation_count(mb_lpips* h, unsigned* count, int reset, mb_stream stream) {
   if (!h || !count) return fail(-1, "mb_lpips_saturation_count: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(count, h->sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      (reset && hipMemsetAsync(h->sat, 0, sizeof(unsigned), s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
-    return fail(-10, "mb_lpips_saturation_count: copy failed");
-  return 0;
+  return read_counter("mb_lpips_saturation_count", h->sat, count, reset, (hipStream_t)stream);
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----

@@ -1,6 +1,6 @@
-// Host-side plumbing of the C ABI, shared by every translation unit that defines an entry point (engine.hip, diag.hip, decoder.hip, lpips.hip, vq.hip, ...):
-// the library's one error path (fail -> mb_last_error), the one owner of device allocations (DevArena), the check after a launch, and the optional
-// per-kernel device timing.
+// Host-side plumbing of the C ABI, shared by every translation unit that defines an entry point (engine.hip, diag.hip, decoder.hip, taming.hip,
+// lpips.hip, inception.hip, vq.hip, ...): the library's one error path (fail -> mb_last_error), the one owner of device allocations (DevArena), the
+// check after a launch, the read of a handle's device counter, and the optional per-kernel device timing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,6 +79,14 @@ struct DevArena {
 inline int launched() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(-11, "kernel launch failed: %s", hipGetErrorString(e));
+}
+
+// the mb_*_saturation_count entries (`what`): *count = the device counter, zeroed afterwards when `reset`.  Synchronises the stream
+inline int read_counter(const char* what, unsigned* dev, unsigned* count, int reset, hipStream_t s) {
+  if (hipMemcpyAsync(count, dev, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      (reset && hipMemsetAsync(dev, 0, sizeof(unsigned), s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess)
+    return fail(-10, "%s: copy failed", what);
+  return 0;
 }
 
 // ---- optional per-kernel device timing with HIP events on the launch stream ------------------

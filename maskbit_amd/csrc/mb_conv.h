@@ -1,5 +1,6 @@
-// The convolution, GroupNorm, pool and repack launchers of conv.hip: what the tokenizer handle (decoder.hip), the VGG16 stack of LPIPS (lpips.hip)
-// and the single-layer diagnostic entries (diag.hip) are made of.  No allocation, no synchronisation, no handle: every buffer is the caller's.
+// The convolution, GroupNorm, pool and repack launchers of conv.hip: what the tokenizer handles (decoder.hip and taming.hip, on the scaffold of
+// mb_autoenc.h), the VGG16 stack of LPIPS (lpips.hip) and the single-layer diagnostic entries (diag.hip) are made of.  No allocation, no
+// synchronisation, no handle: every buffer is the caller's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

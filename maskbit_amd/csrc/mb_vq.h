@@ -1,10 +1,11 @@
 // Lookup (VQ) quantizer kernels (vq.hip): nearest-codeword search fused with its argmin, code -> latent gather and the latent pack of
-// ConvVQModel with quantizer_type = "lookup" (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119).  Used by the tokenizer handle (decoder.hip) and by the
-// diagnostic entry mb_vq_argmin (diag.hip).
+// the lookup tokenizers (SimpleVectorizer, modeling/quantizer/quantizer.py:10-119), and the workspace a handle keeps for them.  Used by the tokenizer
+// handles (decoder.hip, taming.hip) and by the diagnostic entry mb_vq_argmin (diag.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mb_abi.h"
 #include "mb_common.h"
 
 namespace mb {
@@ -40,6 +41,33 @@ void vq_search(const VqCodebook& q, const float* zT, int N, int HW, int splits, 
 void vq_gather(const VqCodebook& q, const int64_t* codes, size_t npix, h16* z, int cin_pad, unsigned* sat, hipStream_t s);
 // fp32 NCHW latent [B][K][HW] -> fp16 NHWC [B*HW][cin_pad], saturating stores counted in *sat
 void vq_pack_latent(const float* z, int B, int K, int HW, h16* out, int cin_pad, unsigned* sat, hipStream_t s);
+
+// The lookup quantizer of a handle: the prepared codebook, the search buffers and whether quantize.embedding.weight has arrived
+struct VqWorkspace {
+  VqCodebook q;
+  float* zT = nullptr;    // [Kp / 4][Npad][4] rows of the encoder output (normalised when l2)
+  float* ps = nullptr;    // [VQ_SPLIT_MAX][Npad] per-split best score ...
+  int* pi = nullptr;      // ... and its entry
+  bool loaded = false;
+  // C entries of K channels, searched for up to nlat rows at a time
+  void alloc(DevArena& m, int C, int K, int l2, size_t nlat) {
+    q.C = C; q.K = K; q.Kp = vq_kp(K); q.Cpad = vq_cpad(C); q.l2 = l2 ? 1 : 0;
+    const size_t npad = (size_t)vq_npad((int)nlat);
+    m.get(&q.cb, (size_t)C * K); m.get(&q.cbT, (size_t)q.Kp * q.Cpad); m.get(&q.cbn, (size_t)q.Cpad);
+    m.get(&zT, (size_t)q.Kp * npad); m.get(&ps, VQ_SPLIT_MAX * npad); m.get(&pi, VQ_SPLIT_MAX * npad);
+  }
+  // quantize.embedding.weight, fp32 [C][K] on the device; false (and nothing done) for any other shape: the message is the handle's
+  bool load_codebook(const int64_t* shape, int ndim, const float* data, hipStream_t s) {
+    if (ndim != 2 || shape[0] != q.C || shape[1] != q.K) return false;
+    vq_prep_codebook(q, data, s);
+    return loaded = true;
+  }
+  // the end of an encode: z rows (fp16, `stride` apart, hw per image) -> idx, zq, zraw, row_dist as vq_prep_rows / vq_search write them
+  void encode_rows(const h16* z16, int stride, int N, int hw, int64_t* idx, float* zq, float* zraw, float* row_dist, hipStream_t s) {
+    vq_prep_rows(q, z16, stride, nullptr, N, hw, zT, zraw, s);
+    vq_search(q, zT, N, hw, vq_splits(q, N, 0), ps, pi, idx, zq, row_dist, s);
+  }
+};
 
 // Diagnostic (mb_vq_argmin): the whole search on caller buffers, z fp32 [N][K], w fp32 [C][K] codebook; temporaries are stream-ordered.
 // 0, or the code of a fail() in that entry's name

@@ -50,7 +50,9 @@ def inception_keys() -> List[str]:
 
 
 class InceptionV3(BaseModel):
-    max_images_per_call = 32               # workspace bound: 5.5 MiB of fp16 activations per image
+    _ABI = "inception"
+    _COUNTS = "4-channel activation groups the convolutions clamped"
+    max_images_per_call = 32              # workspace bound: 5.5 MiB of fp16 activations per image
 
     def __init__(self, features_list: Sequence[str] = DEFAULT_FEATURES):
         super().__init__()
@@ -96,13 +98,6 @@ class InceptionV3(BaseModel):
         h = C.c_void_p()
         _lib.check(_lib.load().mb_inception_create(capacity, C.byref(h)), "mb_inception_create")
         return h
-
-    def _engine_destroy(self, h) -> None:
-        _lib.load().mb_inception_destroy(h)
-
-    def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.load().mb_inception_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_inception_load({key})")
 
     def engine(self, images: int):
         have = self._engine_key[1] if self._engine_key else 0
@@ -153,17 +148,6 @@ class InceptionV3(BaseModel):
                 else:
                     _lib.check(lib.mb_inception_forward(h, src, n, H, W, ptr["2048"], ptr["logits_unbiased"], ptr["logits"], stream), "mb_inception_forward")
         return out
-
-    def saturation_count(self, reset: bool = True) -> int:
-        """4-channel activation groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the current stream."""
-        if self._engine is None:
-            return 0
-        n = C.c_uint(0)
-        dev = self._require_cuda("saturation_count")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_inception_saturation_count(self._engine, C.byref(n), 1 if reset else 0, torch.cuda.current_stream().cuda_stream),
-                       "mb_inception_saturation_count")
-        return int(n.value)
 
 
 def get_inception_model(weights: Optional[StateLike] = None) -> InceptionV3:

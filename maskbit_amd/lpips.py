@@ -49,7 +49,9 @@ def _read(src: StateLike) -> Dict[str, torch.Tensor]:
 
 
 class LPIPS(BaseModel):
-    max_pairs_per_call = 16                # workspace bound at 256 x 256 (two fp16 buffers of 8 MiB per image); scaled down with the image area
+    _ABI = "lpips"
+    _COUNTS = "4-channel activation groups the convolutions clamped (ImageNet VGG16 activations are unnormalised)"
+    max_pairs_per_call = 16               # workspace bound at 256 x 256 (two fp16 buffers of 8 MiB per image); scaled down with the image area
 
     def __init__(self, use_dropout: bool = True):
         super().__init__()
@@ -121,13 +123,6 @@ class LPIPS(BaseModel):
         _lib.check(_lib.load().mb_lpips_create(capacity, self._cap_hw[0], self._cap_hw[1], C.byref(h)), "mb_lpips_create")
         return h
 
-    def _engine_destroy(self, h) -> None:
-        _lib.load().mb_lpips_destroy(h)
-
-    def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.load().mb_lpips_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_lpips_load({key})")
-
     def engine(self, pairs: int, H: int, W: int):
         if H * W > self._cap_hw[0] * self._cap_hw[1]:
             self._drop_engine()
@@ -180,15 +175,3 @@ class LPIPS(BaseModel):
     @torch.no_grad()
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return self._run(input, target, False).to(torch.float32).view(-1, 1, 1, 1)
-
-    def saturation_count(self, reset: bool = True) -> int:
-        """4-channel activation groups the convolutions clamped at the fp16 range since the last reset (ImageNet VGG16 activations are
-        unnormalised: a checkpoint that needs more range shows up here).  Synchronises the current stream."""
-        if self._engine is None:
-            return 0
-        n = C.c_uint(0)
-        dev = self._require_cuda("saturation_count")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_lpips_saturation_count(self._engine, C.byref(n), 1 if reset else 0, torch.cuda.current_stream().cuda_stream),
-                       "mb_lpips_saturation_count")
-        return int(n.value)

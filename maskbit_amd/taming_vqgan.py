@@ -20,7 +20,8 @@ from typing import List, Optional, Union
 import torch
 
 from . import _lib
-from .base_model import BaseModel, ParamSpec
+from .base_model import ParamSpec
+from .tokenizer import TokenizerModel
 
 CH, CH_MULT, NUM_RES_BLOCKS, Z_CHANNELS = 128, (1, 1, 2, 2, 4), 2, 256
 CODEBOOK_SIZE, TOKEN_SIZE, COMMITMENT_COST = 1024, 256, 0.25
@@ -91,7 +92,11 @@ def taming_specs() -> List[ParamSpec]:
     return s
 
 
-class OriginalVQModel(BaseModel):
+class OriginalVQModel(TokenizerModel):
+    """Images in [0, 1] nominally; ``decode`` takes any float latent [b, 256, h, w] (taming_vqgan.py:52-56), ``_encode`` always returns
+    (zq, idx, zraw, dist)."""
+    _ABI, _DECODE, _DECODE_LATENT, _ENCODE = "taming", "mb_taming_decode", "mb_taming_decode_latent", "mb_taming_encode"
+    _COUNTS = "4-channel activation groups clamped: conv outputs (q, k, v among them), attention outputs and latent packs"
     codebook_size = CODEBOOK_SIZE
     token_size = TOKEN_SIZE
     commitment_cost = COMMITMENT_COST
@@ -107,7 +112,6 @@ class OriginalVQModel(BaseModel):
                      torch.empty(CODEBOOK_SIZE, TOKEN_SIZE).uniform_(-1.0 / CODEBOOK_SIZE, 1.0 / CODEBOOK_SIZE))       # quantizer.py:36-37
         for p in ("quant_conv", "post_quant_conv"):
             self._build(_conv(p, TOKEN_SIZE, Z_CHANNELS, 1))
-        self._latent_size = 16
 
     def load_pretrained(self, pretrained_model_path: Union[str, os.PathLike], strict_loading: bool = True,
                         torch_dtype: Optional[torch.dtype] = None) -> None:
@@ -135,134 +139,19 @@ class OriginalVQModel(BaseModel):
         _lib.check(_lib.load().mb_taming_create(capacity, self._latent_size, C.byref(h)), "mb_taming_create")
         return h
 
-    def _engine_destroy(self, h) -> None:
-        _lib.load().mb_taming_destroy(h)
-
-    def _engine_load(self, h, key: str, t: torch.Tensor, stream: int) -> None:
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.load().mb_taming_load(h, key.encode(), t.data_ptr(), shape, t.dim(), stream), f"mb_taming_load({key})")
-
-    def engine(self, min_batch: int, latent_size: int = 16):
-        if latent_size != self._latent_size:
-            self._drop_engine()
-            self._latent_size = latent_size
-        have = self._engine_key[1] if self._engine_key else 0
-        return self._ensure_engine(max(min_batch, have, 8))
-
-    def saturation_count(self, reset: bool = True) -> int:
-        """4-channel activation groups the engine clamped at the fp16 range (+-65504) since the last reset: conv outputs (q, k, v among them),
-        attention outputs and latent packs of the current engine.  Synchronises the current stream."""
-        if self._engine is None:
-            return 0
-        n = C.c_uint(0)
-        dev = self._require_cuda("saturation_count")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_taming_saturation_count(self._engine, C.byref(n), 1 if reset else 0, torch.cuda.current_stream().cuda_stream),
-                       "mb_taming_saturation_count")
-        return int(n.value)
-
     # ---- shapes -----------------------------------------------------------------------------
-    @staticmethod
-    def _latent_side(n: int) -> int:
+    def _grid_side(self, n: int) -> int:
         side = int(math.sqrt(float(n)))
         if side * side != n or side not in (16, 32):
             raise ValueError(f"OriginalVQModel takes 16 x 16 or 32 x 32 token grids (256 x 256 or 512 x 512 images), got {n} tokens")
         return side
 
-    def _check_codes(self, tokens: torch.Tensor) -> None:
-        """Host-resident codes are range-checked (nn.Embedding raises IndexError, quantizer.py:115); device-resident ones are clamped to
-        [0, 1024) in the gather kernel, with no host synchronisation."""
-        if tokens.device.type == "cpu" and tokens.numel():
-            t = tokens.long()
-            if int(t.min()) < 0 or int(t.max()) >= CODEBOOK_SIZE:
-                raise IndexError(f"code outside [0, {CODEBOOK_SIZE})")
+    def _latent_side(self, h: int, w: int) -> int:
+        if h != w or h not in (16, 32):
+            raise ValueError(f"decode expects a 16 x 16 or 32 x 32 latent grid, got {h}x{w}")
+        return h
 
-    # ---- decode -----------------------------------------------------------------------------
-    def _decode_codes(self, codes: torch.Tensor, want_u8: bool = False):
-        if codes.dim() != 2:
-            raise ValueError(f"decode_tokens expects tokens [b, n], got {tuple(codes.shape)}")
-        side = self._latent_side(codes.shape[1])
-        dev = self._require_cuda("decode_tokens")
-        b, res = codes.shape[0], side << (self.num_resolutions - 1)
-        img = torch.empty((b, 3, res, res), dtype=torch.float32, device=dev)
-        u8 = torch.empty((b, res, res, 3), dtype=torch.uint8, device=dev) if want_u8 else None
-        h = self.engine(b, side)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_taming_decode(h, codes.data_ptr(), img.data_ptr(), u8.data_ptr() if want_u8 else None, b,
-                                                    torch.cuda.current_stream().cuda_stream), "mb_taming_decode")
-        return (img, u8) if want_u8 else img
-
-    @torch.no_grad()
-    def decode_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
-        """tokens [b, n] -> image [b, 3, H, W] float32 in [0, 1] nominally, unclamped (taming_vqgan.py:58-64)."""
-        if tokens.dim() == 2:
-            self._latent_side(tokens.shape[1])
-        self._check_codes(tokens)
-        dev = self._require_cuda("decode_tokens")
-        return self._decode_codes(tokens.to(dev).long().contiguous())
-
-    @torch.no_grad()
-    def decode_tokens_uint8(self, tokens: torch.Tensor):
-        """-> (image fp32 NCHW, uint8 NHWC = trunc(clamp(x,0,1)*255)) in one pass."""
-        if tokens.dim() == 2:
-            self._latent_side(tokens.shape[1])
-        self._check_codes(tokens)
-        dev = self._require_cuda("decode_tokens")
-        return self._decode_codes(tokens.to(dev).long().contiguous(), want_u8=True)
-
-    @torch.no_grad()
-    def decode(self, z_quantized: torch.Tensor) -> torch.Tensor:
-        """z [b, 256, h, w], any float latent -> image (taming_vqgan.py:52-56)."""
-        if z_quantized.dim() != 4 or z_quantized.shape[1] != TOKEN_SIZE:
-            raise ValueError(f"decode expects [b, {TOKEN_SIZE}, h, w], got {tuple(z_quantized.shape)}")
-        b, _, hh, ww = z_quantized.shape
-        if hh != ww or hh not in (16, 32):
-            raise ValueError(f"decode expects a 16 x 16 or 32 x 32 latent grid, got {hh}x{ww}")
-        dev = self._require_cuda("decode")
-        z = z_quantized.to(device=dev, dtype=torch.float32).contiguous()
-        res = hh << (self.num_resolutions - 1)
-        img = torch.empty((b, 3, res, res), dtype=torch.float32, device=dev)
-        h = self.engine(b, hh)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_taming_decode_latent(h, z.data_ptr(), img.data_ptr(), None, b, torch.cuda.current_stream().cuda_stream),
-                       "mb_taming_decode_latent")
-        return img
-
-    # ---- encode -----------------------------------------------------------------------------
-    @torch.no_grad()
-    def _encode(self, x: torch.Tensor, want_raw: bool = False, want_dist: bool = False):
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"encode expects [b, 3, H, W], got {tuple(x.shape)}")
-        b, _, H, W = x.shape
+    def _image_side(self, H: int, W: int) -> int:
         if H != W or H not in (256, 512):
             raise ValueError(f"OriginalVQModel takes square images of side 256 or 512, got {H}x{W}")
-        dev = self._require_cuda("encode")
-        side = H >> (self.num_resolutions - 1)
-        img = x.to(device=dev, dtype=torch.float32).contiguous()
-        idx = torch.empty((b, side, side), dtype=torch.int64, device=dev)
-        zq = torch.empty((b, TOKEN_SIZE, side, side), dtype=torch.float32, device=dev)
-        zraw = torch.empty_like(zq) if want_raw else None
-        dist = torch.empty((b, side, side), dtype=torch.float32, device=dev) if want_dist else None
-        h = self.engine(b, side)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().mb_taming_encode(h, img.data_ptr(), idx.data_ptr(), zq.data_ptr(), zraw.data_ptr() if want_raw else None,
-                                                    dist.data_ptr() if want_dist else None, b, torch.cuda.current_stream().cuda_stream),
-                       "mb_taming_encode")
-        return zq, idx, zraw, dist
-
-    def encode(self, x: torch.Tensor):
-        """OriginalVQModel.encode (taming_vqgan.py:45-50; SimpleVectorizer.forward in eval mode, quantizer.py:45-103): z_quantized = the selected
-        codebook rows; codebook_loss = mean((zq - z)^2) from the kernel's per-row squared distances, commitment_loss = 0.25 * codebook_loss,
-        quantizer_loss their sum; the entropy terms are zero, as for the lookup ``ConvVQModel``."""
-        zq, idx, _, dist = self._encode(x, want_dist=True)
-        codebook_loss = (dist.sum() / float(dist.numel() * TOKEN_SIZE)).reshape(())
-        commitment_loss = COMMITMENT_COST * codebook_loss
-        zero = torch.zeros((), device=zq.device)
-        return zq, dict(quantizer_loss=commitment_loss + codebook_loss, commitment_loss=commitment_loss, codebook_loss=codebook_loss,
-                        entropy_loss=zero, per_sample_entropy=zero, avg_entropy=zero, min_encoding_indices=idx)
-
-    def forward(self, input: torch.Tensor):
-        """OriginalVQModel.forward (taming_vqgan.py:66-69): (decode(encode(x)), result_dict)."""
-        zq, result = self.encode(input)
-        codes = result["min_encoding_indices"].reshape(zq.shape[0], -1)
-        return self._decode_codes(codes.contiguous()), result
+        return H >> (self.num_resolutions - 1)
