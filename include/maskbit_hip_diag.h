@@ -1,6 +1,6 @@
 /* libmaskbit_hip.so -- DIAGNOSTIC entry points: single kernels of the engine on caller buffers, for the unit tests (tests/test_hip_gemm.py,
  * test_hip_pair.py, test_hip_conv.py; the row kernels -- mb_layernorm, mb_layernorm_f4_seq, mb_layernorm_pair, mb_pairify, mb_embed_ln, mb_embed_pair --
- * in test_hip_rows.py; the quantizer kernels in test_hip_quantizer.py) and the tools under tools/.  Nothing here is part of the reference's
+ * in test_hip_rows.py; the quantizer kernels in test_hip_quantizer.py; the tokenizers' blocks in test_hip_taming_blocks.py) and the tools under tools/.  Nothing here is part of the reference's
  * surface and no host binding of the product needs it: include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered,
  * 0 / negative return, mb_last_error()).
  */
@@ -200,6 +200,28 @@ int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, co
                   void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
                   float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
                   mb_stream stream);
+/* mb_conv_layer (= flags 0) with the two launch_conv switches the handles use and mb_conv_layer never sets.  flags bit 0: the GroupNorm prologue
+ * WITHOUT SiLU (the q / k / v projection of the Taming AttnBlock; ks 1 with gn_gamma / gn_beta only).  Bit 1: stats = false -- the epilogue writes no
+ * GroupNorm partials and leaves the context without a source: *part_tiles = 0 whatever Cout, and out_scale_shift comes from the sweep.
+ * Refused (-1, nothing launched): bit 0 with ks other than 1 or without a prologue, any other bit. */
+int mb_conv_layer_ex(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
+                     void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
+                     float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up, int final_layer,
+                     int flags, mb_stream stream);
+/* One ResNet block of the conv-autoencoder scaffold (mb_autoenc.h) on a scratch AutoEnc: built with mb::init_block, loaded with mb::load_param under
+ * the checkpoint names norm1 / conv1 / norm2 / conv2 / nin_shortcut (.weight, .bias), run with mb::run_block from buffer 0.  x_h16 fp16
+ * [B, H, W, cin]; the parameters fp32 on the device: n1_g / n1_b [cin], c1_w [cout, cin, 3, 3], n2_g / n2_b [cout], c2_w [cout, cout, 3, 3],
+ * sc_w [cout, cin, 1, 1] (form 1) or [cout, cout, 1, 1] (form 2), the biases [cout] (read with `bias` only).  form 0: cin == cout, no shortcut;
+ * 1: out = nin_shortcut(x) + h (Taming, sc_on_input); 2: out = h + nin_shortcut(h) (conv-VQGAN).  Outputs fp16 NHWC, each required:
+ * out_h16 [.., cout]; h1_h16 = conv1's output (through AutoEnc::h1_tap: in form 2 the buffer rotation overwrites it); mid_h16 = the
+ * shortcut's output (form 1) / conv2's raw output (form 2), not written in form 0 (may be NULL there).  out_scale_shift (optional, with out_gamma /
+ * out_beta [cout]) = [B, cout] (scale, shift) by one further launch_gn on the block's output from whatever the block left in GnCtx.
+ * *saturated (host) as for mb_conv_layer.  Refused (-1, nothing launched): a NULL required pointer, cin / cout no multiple of 64 or beyond 2048,
+ * H % 8, W % 16, a form that does not go with (cin, cout).  Synchronises the stream. */
+int mb_autoenc_block(const void* x_h16, const float* n1_g, const float* n1_b, const float* c1_w, const float* c1_b, const float* n2_g, const float* n2_b,
+                     const float* c2_w, const float* c2_b, const float* sc_w, const float* sc_b, int form, int bias, void* out_h16, void* h1_h16,
+                     void* mid_h16, const float* out_gamma, const float* out_beta, float* out_scale_shift, unsigned* saturated, int B, int H, int W,
+                     int cin, int cout, mb_stream stream);
 /* GroupNorm statistics of x fp16 [B, HW, C] by the sweep (gn_partial_kernel + gn_finalize_kernel): scale_shift [B, C] pairs with
  * scale = gamma * rstd, shift = beta - mean * scale; C % 32 == 0, C <= 2048. */
 int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta, float* scale_shift, int B, int HW, int C, mb_stream stream);
@@ -262,6 +284,21 @@ int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, v
  * encoder.mid.attn_1, 3 = decoder.mid.attn_1, 4 .. 6 = decoder.up.4.attn.{0,1,2}) to out_h16 fp16 [B, N, 512]; NULL removes the tap. */
 int mb_spatial_attention(const void* q, const void* k, const void* v, void* out_h16, unsigned* sat, int B, int N, int ld, int ldo, mb_stream stream);
 int mb_taming_set_tap(mb_taming* h, int block, void* out_h16);
+/* Pieces of the handle's schedule on caller data (tests/test_hip_taming_blocks.py), each through the function the schedule itself calls.
+ * mb_taming_attn_block: run_attn of AttnBlock `block` (numbered as for mb_taming_set_tap) -- x fp16 [B, H, W, 512] is copied into buffer 0 and the
+ * GroupNorm context cleared of its source, then GroupNorm -> the stacked 512 -> 1536 projection (no SiLU) -> spatial attention on its slices ->
+ * proj_out + x.  Outputs fp16, each required: qkv_out [B H W, 1536], attn_out [B H W, 512] (the attention's output), out [B, H, W, 512].
+ * out_scale_shift (optional, with out_gamma / out_beta [512]) = [B, 512] (scale, shift) by one further launch_gn on the block's output from the
+ * state run_attn left.  H % 8 == 0, W % 16 == 0, H W <= latent^2, 1 <= B <= max_batch.  Only that block's parameters need to be loaded.
+ * mb_taming_final: decoder.norm_out + the folded decoder.conv_out as decode runs them, on x fp16 [B, H, W, 128] -> img_nchw fp32 [B, 3, H, W]
+ * and / or img_nhwc_u8 [B, H, W, 3]; H % 8 == 0, W % 16 == 0, H W <= the handle's image, 1 <= B <= max_batch.
+ * mb_taming_pack_image: the encoder's input kernel alone: img_nchw fp32 [B, 3, H, W] -> out_h16 fp16 [B H W, 64], channels 0 .. 2 the saturating
+ * fp16 of x * 2 - 1, 0 beyond; any H, W >= 1, B H W <= 2^24.  No handle.
+ * Refused (-1, nothing launched): a NULL required pointer, a block outside [0, 7), a shape outside the above. */
+int mb_taming_attn_block(mb_taming* h, int block, const void* x_h16, void* qkv_out, void* attn_out, void* out_h16, const float* out_gamma,
+                         const float* out_beta, float* out_scale_shift, int B, int H, int W, mb_stream stream);
+int mb_taming_final(mb_taming* h, const void* x_h16, float* img_nchw, uint8_t* img_nhwc_u8, int B, int H, int W, mb_stream stream);
+int mb_taming_pack_image(const float* img_nchw, void* out_h16, int B, int H, int W, mb_stream stream);
 
 /* ---- the fp32 reference mode's kernels (gemm_f32.hip; mb_gen_cfg.precision = MB_PREC_F32), everything fp32 in device memory.
  * mb_gemm_f32: out = epi(A[M,K] . W[N,K]^T + bias).  Every output element is acc = 0; for k = 0 .. K-1: acc = fmaf(A[m,k], W[n,k], acc) -- one chain,

@@ -149,6 +149,8 @@ SIGNATURES = {
     "mb_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                           C.c_int, C.c_int, C.c_void_p]),
     "mb_conv_layer": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_int), C.POINTER(C.c_uint)] + [C.c_int] * 8 + [C.c_void_p]),
+    "mb_conv_layer_ex": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_int), C.POINTER(C.c_uint)] + [C.c_int] * 9 + [C.c_void_p]),
+    "mb_autoenc_block": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_uint)] + [C.c_int] * 5 + [C.c_void_p]),
     "mb_groupnorm_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_avgpool2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_s2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -199,6 +201,9 @@ SIGNATURES = {
     "mb_taming_decode_latent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mb_taming_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
     "mb_taming_set_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "mb_taming_attn_block": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
+    "mb_taming_final": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "mb_taming_pack_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_spatial_attention": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "mb_gemm_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "mb_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),

@@ -1,6 +1,6 @@
 // Diagnostic entry points (include/maskbit_hip_diag.h): single kernels and single layers on caller buffers, for the tests and the tools.
 // No host binding of the product needs them.  Argument checks, a scratch arena (mb::DevArena) where a layer needs one, and the launchers' own calls
-// only: this file holds no kernel.
+// only: this file holds no kernel of its own (mb_autoenc.h brings the loader's affine_kernel along for mb_autoenc_block).
 // (mb_gen_set_alo, the one entry of that header that needs the generator handle's members, is in engine.hip.)
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
+#include "mb_autoenc.h"
 #include "mb_conv.h"
 #include "mb_image.h"
 #include "mb_kernels.h"
@@ -416,9 +417,19 @@ int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, co
                   void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
                   float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up_, int final_layer,
                   mb_stream stream) {
+  return mb_conv_layer_ex(in_h16, w_oihw, bias, gn_gamma, gn_beta, residual_h16, out_h16, img_nchw, img_nhwc_u8, out_gamma, out_beta, out_scale_shift,
+                          out_gn_part, part_tiles, saturated, B, H, W, Cin, Cout, ks, up_, final_layer, 0, stream);
+}
+// flags: 1 = the prologue without SiLU, 2 = stats off (launch_conv's gn_silu = false / stats = false, which the handles' schedules use)
+int mb_conv_layer_ex(const void* in_h16, const float* w_oihw, const float* bias, const float* gn_gamma, const float* gn_beta, const void* residual_h16,
+                     void* out_h16, float* img_nchw, uint8_t* img_nhwc_u8, const float* out_gamma, const float* out_beta, float* out_scale_shift,
+                     float* out_gn_part, int* part_tiles, unsigned* saturated, int B, int H, int W, int Cin, int Cout, int ks, int up_, int final_layer,
+                     int flags, mb_stream stream) {
   using namespace mb;
   hipStream_t s = (hipStream_t)stream;
-  const bool fin = final_layer != 0, up = up_ != 0;
+  const bool fin = final_layer != 0, up = up_ != 0, no_silu = (flags & 1) != 0, stats = (flags & 2) == 0;
+  if (flags & ~3) return fail(-1, "mb_conv_layer: unknown flag bits");
+  if (no_silu && (ks != 1 || !gn_gamma)) return fail(-1, "mb_conv_layer: the prologue without SiLU goes with ks 1 and gamma / beta");
   if (!in_h16 || !w_oihw || B <= 0 || Cin <= 0 || Cout <= 0) return fail(-1, "mb_conv_layer: null or empty argument");
   if (ks < 1 || ks > 3) return fail(-1, "mb_conv_layer: ks must be 1, 2 or 3");
   if (H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_conv_layer: the output must be whole 8 x 16 pixel tiles");
@@ -461,7 +472,7 @@ int mb_conv_layer(const void* in_h16, const float* w_oihw, const float* bias, co
     launch_gn(s, &gc, n, in, B, Hin * Win);
     gn = gc.ss;
   }
-  launch_conv(s, &gc, c, in, gn, (const h16*)residual_h16, (h16*)out_h16, img_nchw, img_nhwc_u8, B, H, W, fin);
+  launch_conv(s, &gc, c, in, gn, (const h16*)residual_h16, (h16*)out_h16, img_nchw, img_nhwc_u8, B, H, W, fin, stats, !no_silu);
   const int tiles = gc.of == (const void*)out_h16 && !fin ? gc.ntile : 0;      // the epilogue wrote GroupNorm partials of the output
   if (part_tiles) *part_tiles = tiles;
   if (out_gn_part && tiles) ok = hipMemcpyAsync(out_gn_part, gc.part, (size_t)B * tiles * 64 * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess;
@@ -489,6 +500,56 @@ int mb_groupnorm_stats(const void* x_h16, const float* gamma, const float* beta,
   launch_gn(s, &gc, n, (const h16*)x_h16, B, HW);   // gc.of is null: the sweep (gn_partial_kernel) + gn_finalize_kernel
   if (hipMemcpyAsync(scale_shift, gc.ss, (size_t)B * C * sizeof(float2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) return fail(-10, "mb_groupnorm_stats: copy failed");
+  return launched();
+}
+// One ResNet block of the handles' scaffold (mb_autoenc.h) on a scratch AutoEnc: init_block, load_param under checkpoint names, run_block
+int mb_autoenc_block(const void* x_h16, const float* n1_g, const float* n1_b, const float* c1_w, const float* c1_b, const float* n2_g, const float* n2_b,
+                     const float* c2_w, const float* c2_b, const float* sc_w, const float* sc_b, int form, int bias_, void* out_h16, void* h1_h16,
+                     void* mid_h16, const float* out_gamma, const float* out_beta, float* out_scale_shift, unsigned* saturated, int B, int H, int W,
+                     int cin, int cout, mb_stream stream) {
+  using namespace mb;
+  hipStream_t s = (hipStream_t)stream;
+  const bool bias = bias_ != 0;
+  if (!x_h16 || !n1_g || !n1_b || !c1_w || !n2_g || !n2_b || !c2_w || !out_h16 || !h1_h16) return fail(-1, "mb_autoenc_block: null argument");
+  if (form < 0 || form > 2 || (form == 0) != (cin == cout)) return fail(-1, "mb_autoenc_block: form 0 goes with cin == cout, forms 1 and 2 with cin != cout");
+  if (form != 0 && (!sc_w || !mid_h16)) return fail(-1, "mb_autoenc_block: the shortcut's weight and the mid output are required with a shortcut");
+  if (bias && (!c1_b || !c2_b || (form != 0 && !sc_b))) return fail(-1, "mb_autoenc_block: bias on needs every bias");
+  if (B <= 0 || H <= 0 || W <= 0 || H % TH8 || W % TW) return fail(-1, "mb_autoenc_block: whole 8 x 16 pixel tiles required");
+  if (cin <= 0 || cout <= 0 || cin % CK || cout % CK || cin > 2048 || cout > 2048) return fail(-1, "mb_autoenc_block: cin and cout must be multiples of 64 up to 2048");
+  if (out_scale_shift && (!out_gamma || !out_beta)) return fail(-1, "mb_autoenc_block: output statistics need gamma and beta");
+  AutoEnc a;
+  ResBlock rb;
+  const size_t npix = (size_t)B * H * W;
+  a.mem.zeroed(&a.sat, 1);
+  init_block(a, rb, "b", cin, cout, bias, form == 1);
+  for (int i = 0; i < 3; ++i) a.mem.get(&a.buf[i], npix * std::max(cin, cout));
+  a.mem.get(&a.gn.part, gn_part_elems(B, H, W));
+  a.mem.get(&a.gn.ss, (size_t)B * std::max(cin, cout));
+  if (int rc = a.mem.failed("mb_autoenc_block")) return rc;
+  const size_t sc_in = form == 1 ? cin : cout;
+  struct { const char* name; const float* data; size_t numel; } entries[] = {
+      {"b.norm1.weight", n1_g, (size_t)cin}, {"b.norm1.bias", n1_b, (size_t)cin}, {"b.conv1.weight", c1_w, (size_t)cout * cin * 9},
+      {"b.conv1.bias", bias ? c1_b : nullptr, (size_t)cout}, {"b.norm2.weight", n2_g, (size_t)cout}, {"b.norm2.bias", n2_b, (size_t)cout},
+      {"b.conv2.weight", c2_w, (size_t)cout * cout * 9}, {"b.conv2.bias", bias ? c2_b : nullptr, (size_t)cout},
+      {"b.nin_shortcut.weight", form ? sc_w : nullptr, (size_t)cout * sc_in}, {"b.nin_shortcut.bias", form && bias ? sc_b : nullptr, (size_t)cout}};
+  for (const auto& e : entries)
+    if (e.data)
+      if (int rc = load_param("mb_autoenc_block", a, e.name, e.data, e.numel, s)) return rc;
+  HIP_TRY(hipMemcpyAsync(a.buf[0], x_h16, npix * cin * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  a.h1_tap = (h16*)h1_h16;
+  const int oi = run_block(s, a, rb, 0, B, H, W);
+  // where run_block's rotation leaves the middle tensor: buffer 2 in both forms (the shortcut's output / conv2's raw output)
+  if (form) HIP_TRY(hipMemcpyAsync(mid_h16, a.buf[2], npix * cout * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(out_h16, a.buf[oi], npix * cout * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  if (out_scale_shift) {
+    Norm n; n.c = cout; n.g = const_cast<float*>(out_gamma); n.b = const_cast<float*>(out_beta);
+    launch_gn(s, &a.gn, n, a.buf[oi], B, H * W);                               // from whatever state the block left in the context
+    HIP_TRY(hipMemcpyAsync(out_scale_shift, a.gn.ss, (size_t)B * cout * sizeof(float2), hipMemcpyDeviceToDevice, s));
+  }
+  unsigned nsat = 0;
+  HIP_TRY(hipMemcpyAsync(&nsat, a.sat, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (saturated) *saturated = nsat;
   return launched();
 }
 int mb_avgpool2(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) { return pool_entry("mb_avgpool2", mb::launch_avgpool2, x_h16, y_h16, B, H, W, C, stream); }

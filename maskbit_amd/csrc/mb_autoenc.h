@@ -24,6 +24,7 @@ struct AutoEnc {
   float* fold_w = nullptr;       // scratch of the folded convolution's weight x 0.5 before its repack (allocated when one is named)
   unsigned* sat = nullptr;       // device counter: fp16 clamps since the last read
   GnCtx gn;
+  h16* h1_tap = nullptr;         // diagnostic (mb_autoenc_block): where run_block copies conv1's output [B, H, W, cout] to, or null
   // checkpoint key -> slot, filled as the create function names each parameter.  The Conv pointers are into the handle and its vectors, which
   // are sized before their elements are named and never again.
   std::unordered_map<std::string, Param> params;
@@ -74,6 +75,7 @@ inline int run_block(hipStream_t s, AutoEnc& a, const ResBlock& rb, int xi, int 
   const int t1 = (xi + 1) % 3, t2 = (xi + 2) % 3;
   launch_gn(s, &a.gn, rb.n1, a.buf[xi], B, H * W);
   launch_conv(s, &a.gn, rb.c1, a.buf[xi], a.gn.ss, nullptr, a.buf[t1], nullptr, nullptr, B, H, W, false);
+  if (a.h1_tap) (void)hipMemcpyAsync(a.h1_tap, a.buf[t1], (size_t)B * H * W * rb.c1.cout * sizeof(h16), hipMemcpyDeviceToDevice, s);
   launch_gn(s, &a.gn, rb.n2, a.buf[t1], B, H * W);
   if (!rb.has_sc) {
     launch_conv(s, &a.gn, rb.c2, a.buf[t1], a.gn.ss, a.buf[xi], a.buf[t2], nullptr, nullptr, B, H, W, false);

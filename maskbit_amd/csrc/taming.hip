@@ -60,6 +60,11 @@ __global__ void pack_image_pm1_kernel(const float* __restrict__ img, h16* __rest
   }
 }
 
+void launch_pack_image_pm1(hipStream_t s, const float* img, h16* out, int B, int H, int W) {
+  const size_t npix = (size_t)B * H * W;
+  hipLaunchKernelGGL(pack_image_pm1_kernel, dim3((unsigned)std::min<size_t>(4096, (npix * 8 + 255) / 256)), dim3(256), 0, s, img, out, B, 3, H, W);
+}
+
 // Every convolution of this network has a bias
 void init_conv(mb_taming* d, Conv& c, const std::string& name, int cin, int cout, int ks, bool up = false) {
   mb::init_conv(*d, c, name, cin, cout, ks, true, up);
@@ -97,10 +102,7 @@ int run_attn(hipStream_t s, mb_taming* d, const TAttn& at, int xi, int B, int H,
 // Encoder.forward (taming_autoencoder.py:240-267) + quant_conv (taming_vqgan.py:48) -> index of the buffer holding z [B * latent^2][256]
 int encode_to_z(mb_taming* d, const float* img, int B, hipStream_t s) {
   int res = d->res;
-  {
-    const size_t npix = (size_t)B * res * res;
-    hipLaunchKernelGGL(pack_image_pm1_kernel, dim3((unsigned)std::min<size_t>(4096, (npix * 8 + 255) / 256)), dim3(256), 0, s, img, d->buf[2], B, 3, res, res);
-  }
+  launch_pack_image_pm1(s, img, d->buf[2], B, res, res);
   launch_conv(s, &d->gn, d->e_conv_in, d->buf[2], nullptr, nullptr, d->buf[0], nullptr, nullptr, B, res, res, false);
   int xi = 0;
   for (int l = 0; l < T_LEVELS; ++l) {
@@ -127,6 +129,12 @@ int encode_to_z(mb_taming* d, const float* img, int B, hipStream_t s) {
   return t2;
 }
 
+// decoder.norm_out + the folded decoder.conv_out (taming_autoencoder.py:366-369, taming_vqgan.py:55) on x = buf[xi] -> the image
+void final_layer(mb_taming* d, int xi, float* img_nchw, uint8_t* img_nhwc_u8, int B, int H, int W, hipStream_t s) {
+  launch_gn(s, &d->gn, d->d_norm_out, d->buf[xi], B, H * W);
+  launch_conv(s, &d->gn, d->d_conv_out, d->buf[xi], d->gn.ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, H, W, true);
+}
+
 // post_quant_conv + Decoder.forward (taming_vqgan.py:52-56, taming_autoencoder.py:340-370) from the latent in d->z
 void decode_from_z(mb_taming* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, hipStream_t s) {
   int res = d->latent;
@@ -149,8 +157,7 @@ void decode_from_z(mb_taming* d, float* img_nchw, uint8_t* img_nhwc_u8, int B, h
       xi = t;
     }
   }
-  launch_gn(s, &d->gn, d->d_norm_out, d->buf[xi], B, res * res);
-  launch_conv(s, &d->gn, d->d_conv_out, d->buf[xi], d->gn.ss, nullptr, nullptr, img_nchw, img_nhwc_u8, B, res, res, true);
+  final_layer(d, xi, img_nchw, img_nhwc_u8, B, res, res, s);
 }
 
 }  // namespace
@@ -284,5 +291,49 @@ int mb_taming_set_tap(mb_taming* d, int block, void* out_h16) {
   if (!d || block < 0 || block >= T_NATTN) return fail(-1, "mb_taming_set_tap: block outside [0, 7)");
   d->tap[block] = out_h16;
   return 0;
+}
+int mb_taming_attn_block(mb_taming* d, int block, const void* x_h16, void* qkv_out, void* attn_out, void* out_h16, const float* out_gamma,
+                         const float* out_beta, float* out_scale_shift, int B, int H, int W, mb_stream stream) {
+  if (!d || !x_h16 || !qkv_out || !attn_out || !out_h16) return fail(-1, "mb_taming_attn_block: null argument");
+  if (block < 0 || block >= T_NATTN) return fail(-1, "mb_taming_attn_block: block outside [0, 7)");
+  if (out_scale_shift && (!out_gamma || !out_beta)) return fail(-1, "mb_taming_attn_block: output statistics need gamma and beta");
+  if (B <= 0 || B > d->max_batch) return fail(-1, "mb_taming_attn_block: batch outside [1, max_batch]");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW || (int64_t)H * W > (int64_t)d->latent * d->latent)
+    return fail(-1, "mb_taming_attn_block: H a multiple of 8, W of 16, H W <= latent^2 required");
+  hipStream_t s = (hipStream_t)stream;
+  const TAttn& at = block < 2    ? d->e_down[T_LEVELS - 1].attn[block]      // numbered as init_attn's taps
+                    : block == 2 ? d->e_mid_attn
+                    : block == 3 ? d->d_mid_attn
+                                 : d->d_up[T_LEVELS - 1].attn[block - 4];
+  const size_t rows = (size_t)B * H * W;
+  HIP_TRY(hipMemcpyAsync(d->buf[0], x_h16, rows * T_ATT * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  d->gn.of = nullptr;                               // buffer 0 is no convolution's output
+  const int oi = run_attn(s, d, at, 0, B, H, W);
+  HIP_TRY(hipMemcpyAsync(qkv_out, d->qkv, rows * 3 * T_ATT * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(attn_out, d->buf[1], rows * T_ATT * sizeof(h16), hipMemcpyDeviceToDevice, s));   // run_attn's t1 from buffer 0
+  HIP_TRY(hipMemcpyAsync(out_h16, d->buf[oi], rows * T_ATT * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  if (out_scale_shift) {
+    Norm n; n.c = T_ATT; n.g = const_cast<float*>(out_gamma); n.b = const_cast<float*>(out_beta);
+    launch_gn(s, &d->gn, n, d->buf[oi], B, H * W);                             // from the state run_attn left in the context
+    HIP_TRY(hipMemcpyAsync(out_scale_shift, d->gn.ss, (size_t)B * T_ATT * sizeof(float2), hipMemcpyDeviceToDevice, s));
+  }
+  return launched();
+}
+int mb_taming_final(mb_taming* d, const void* x_h16, float* img_nchw, uint8_t* img_nhwc_u8, int B, int H, int W, mb_stream stream) {
+  if (!d || !x_h16 || !(img_nchw || img_nhwc_u8)) return fail(-1, "mb_taming_final: null argument");
+  if (B <= 0 || B > d->max_batch) return fail(-1, "mb_taming_final: batch outside [1, max_batch]");
+  if (H <= 0 || W <= 0 || H % TH8 || W % TW || (int64_t)H * W > (int64_t)d->res * d->res)
+    return fail(-1, "mb_taming_final: H a multiple of 8, W of 16, H W <= the handle's image required");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemcpyAsync(d->buf[0], x_h16, (size_t)B * H * W * T_CH * sizeof(h16), hipMemcpyDeviceToDevice, s));
+  d->gn.of = nullptr;
+  final_layer(d, 0, img_nchw, img_nhwc_u8, B, H, W, s);
+  return launched();
+}
+int mb_taming_pack_image(const float* img_nchw, void* out_h16, int B, int H, int W, mb_stream stream) {
+  if (!img_nchw || !out_h16) return fail(-1, "mb_taming_pack_image: null argument");
+  if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > (1 << 24)) return fail(-1, "mb_taming_pack_image: B, H, W >= 1, B * H * W <= 2^24 required");
+  launch_pack_image_pm1((hipStream_t)stream, img_nchw, (h16*)out_h16, B, H, W);
+  return launched();
 }
 }  // extern "C"

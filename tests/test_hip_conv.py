@@ -25,10 +25,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from taming_blocks_reference import U16, U32, check_scale_shift, h16r, ref_conv, ref_gn
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-U16 = 2.0 ** -11          # unit roundoff of fp16
-U32 = 2.0 ** -24          # ... of fp32
 
 
 def _lib():
@@ -77,55 +77,7 @@ def gn_stats(x, gamma, beta):
 
 
 # ------------------------------------------------------------------------------------------------ fp64 reference
-def h16r(t):
-    """round an fp64 tensor to fp16 (nearest even) and back"""
-    return t.to(torch.float16).double()
-
-
-def ref_conv(x16, w, bias, gamma, beta, res16, ks, up, final, rounded):
-    """-> (y fp64 NCHW, S = sum|w a| per output).  x16 fp16 NHWC (CPU).  rounded: the design's documented roundings applied in fp64."""
-    a = x16.double().permute(0, 3, 1, 2)
-    if gamma is not None:
-        a = F.silu(F.group_norm(a, 32, gamma.double(), beta.double(), 1e-6))
-        if rounded:
-            a = h16r(a)
-    if up:
-        a = F.interpolate(a, scale_factor=2.0, mode="nearest")
-    wq = w.to(torch.float16).double()
-    if ks == 2:                                                # 3x3, stride 2, TF "same": the odd pixel goes to the bottom / right
-        a = F.pad(a, [0, 1, 0, 1])
-        conv = lambda t, ww, bb: F.conv2d(t, ww, bb, stride=2)
-    else:
-        conv = lambda t, ww, bb: F.conv2d(t, ww, bb, padding=(ks - 1) // 2)
-    y = conv(a, wq, bias.double() if bias is not None else None)
-    S = conv(a.abs(), wq.abs(), None)
-    if res16 is not None:
-        y = y + res16.double().permute(0, 3, 1, 2)
-    if rounded and not final:
-        y = h16r(y)
-    return y, S
-
-
-def ref_gn(x16, gamma, beta):
-    """fp64 GroupNorm(32, eps 1e-6) statistics of fp16 values x16 [B, HW, C] -> scale, shift, mean, each [B, C]"""
-    B, HW, Cc = x16.shape
-    cpg = Cc // 32
-    v = x16.double().reshape(B, HW, 32, cpg)
-    mean = v.mean(dim=(1, 3))
-    var = (v - mean[:, None, :, None]).pow(2).mean(dim=(1, 3))
-    rstd = (var + 1e-6).rsqrt()
-    mean, rstd = mean.repeat_interleave(cpg, 1), rstd.repeat_interleave(cpg, 1)
-    scale = rstd * gamma.double()
-    return scale, beta.double() - mean * scale, mean
-
-
-def check_scale_shift(ss, x16, gamma, beta, what):
-    scale, shift, mean = ref_gn(x16, gamma, beta)
-    got = ss.double().cpu()
-    e_sc = ((got[..., 0] - scale).abs() / scale.abs()).max().item()
-    e_sh = ((got[..., 1] - shift).abs() / (beta.double().abs() + (mean * scale).abs())).max().item()
-    print(f"{what}: scale rel err {e_sc / U16:.3f} x 2^-11, shift err {e_sh / U16:.3f} x 2^-11 (|beta| + |mean scale|)")
-    assert e_sc <= U16 and e_sh <= U16, (what, e_sc / U16, e_sh / U16)
+# h16r, ref_conv, ref_gn and check_scale_shift live in tests/taming_blocks_reference.py (imported above), shared with the block tests
 
 
 def check_partials(r, out16, H, W):
