@@ -490,6 +490,28 @@ int mb_inception_forward_spatial(mb_inception* h, const uint8_t* u8, int B, int 
 /* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
 int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream);
 
+/* ---- ResNet-50 perceptual loss: modeling/modules/perceptual_loss.py PerceptualLoss("resnet50") ------------------------------------------------- *
+ * torchvision's resnet50 (v1.5) as written out in DESIGN.md "ResNet-50", inference only, on the convolution of the Inception network with a linear
+ * and a residual epilogue (csrc/resnet.hip).  The handle holds the packed weights and the activation buffers for max_pairs pairs (10.7 MiB of fp16
+ * per image).  Additions, MB_ABI_VERSION unchanged. */
+typedef struct mb_resnet mb_resnet;
+int mb_resnet_create(int max_pairs, mb_resnet** out);
+void mb_resnet_destroy(mb_resnet* h);
+/* One state-dict entry (device fp32) of the reference module: `mean`, `std` (3 values each) and `model.` + torchvision's resnet50 keys (the prefix
+ * may be missing): `conv1.weight` [64, 3, 7, 7], `bn1.*`, `layerL.B.conv{1,2,3}.weight`, `layerL.B.bn{1,2,3}.{weight,bias,running_mean,running_var}`,
+ * `layerL.0.downsample.0.weight`, `layerL.0.downsample.1.*`, `fc.weight` [1000, 2048], `fc.bias`; `*.num_batches_tracked` is accepted and ignored.
+ * -2: unknown name, -4: wrong size. */
+int mb_resnet_load(mb_resnet* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
+/* PerceptualLoss.forward of B pairs real / fake fp32 [B, 3, H, W] (32 <= H, W <= 1024; clamp01 != 0: clamped to [0, 1] on the load): both resized to
+ * 224 x 224 (bilinear, antialiased, half-pixel centres), (x - mean) / std, one batch of 2B images through the network.  per_pair double [B] = the
+ * mean over the 1000 logits of (a - b)^2; on_logits == 0: plus the mean over the 2048 x 7 x 7 layer4 map of the same.  sum (double, may be NULL)
+ * += per_pair[0 .. B) in pair order.  Fixed summation order, no floating-point atomics: a pair's value does not depend on B or on the other pairs.
+ * No synchronisation.  Fails (-1) before any launch when the checkpoint is incomplete ("not complete") or the geometry is not taken. */
+int mb_resnet_forward(mb_resnet* h, const float* real, const float* fake, int B, int H, int W, int clamp01, int on_logits, double* per_pair, double* sum,
+                      mb_stream stream);
+/* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
+int mb_resnet_saturation_count(mb_resnet* h, unsigned* count, int reset, mb_stream stream);
+
 /* ---- Taming VQGAN tokenizer: OriginalVQModel, modeling/taming_vqgan.py:19-69 (Encoder / Decoder of modeling/taming/taming_autoencoder.py) ---- *
  * The fixed network of that class: ch 128, ch_mult (1,1,2,2,4), 2 (decoder: 3) res blocks per level, seven single-head AttnBlocks of 512 channels at
  * the 16-pixel level, quant_conv / post_quant_conv, SimpleVectorizer(1024, 256) without normalisation.  fp16 NHWC activations on the convolution

@@ -273,6 +273,36 @@ int mb_inception_input(const uint8_t* u8, void* out_h16, int B, int H, int W, mb
 int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, void* map0, void* map1, void* map2, void* map3, float* tap64,
                       float* tap192, float* tap768, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
 
+/* ---- the pieces of the ResNet-50 perceptual loss (inception.hip, resnet.hip) on caller buffers.
+ * mb_convbn_layer_ex: mb_convbn_layer with the epilogue chosen: 0 = fp16(relu(v)), v = fma(acc, scale, shift) (mb_convbn_layer itself, the same
+ * bits); 1 = fp16(v), no ReLU, *saturated counts groups with |v| > 65504; 2 = fp16(relu(v + float(identity[p][c]))), the identity read as fp16
+ * from channels [idn_off, idn_off + Cout) of identity_h16 [B, Ho, Wo, idn_cs] (idn_off, idn_cs % 4 == 0) and from nowhere else, the add in fp32.
+ * mb_pool3_ex: mb_pool3 plus mode 3 = max, stride 2, padding 1 over the in-image taps only (Ho = (H - 1) / 2 + 1); mb_pool3 keeps refusing it. */
+int mb_convbn_layer_ex(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
+                       int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
+                       int epilogue, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream);
+int mb_pool3_ex(const void* x_h16, void* y_h16, int B, int H, int W, int C, int mode, int in_off, int in_cs, int out_off, int out_cs, mb_stream stream);
+/* The input path alone: real / fake fp32 [B, 3, H, W] (32 <= H, W <= 1024) -> image_h16 fp16 [2B, 224, 224, 4], real images first: channels 0 .. 2 =
+ * (resize(x) - mean[c]) / std[c], channel 3 = 0; mean_std = fp32 {mean[3], std[3]} on the device.  The resize is F.interpolate(size=224,
+ * mode="bilinear", antialias=True, align_corners=False): per axis scale = n / 224, support = max(scale, 1), c = scale (i + 0.5), taps j in
+ * [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), n)) with weights max(0, 1 - |(j - c + 0.5) / support|) over their sum, computed in
+ * double and stored as fp32; fp32 accumulation rows outer, columns inner, taps ascending, one fma each; IEEE division by std.  cols_h16 (may be
+ * NULL) fp16 [2B, 112, 112, 160]: the stem's im2col of that image, channel ci * 49 + ky * 7 + kx < 147 = pixel (2 oy - 3 + ky, 2 ox - 3 + kx) or 0
+ * outside the image, channels 147 .. 159 = 0.  Synchronises the stream. */
+int mb_resnet_input(const float* real, const float* fake, const float* mean_std, void* image_h16, void* cols_h16, int B, int H, int W, int clamp01,
+                    mb_stream stream);
+/* The stem's im2col alone, at any side: image_h16 fp16 [B, S, S, 4] -> cols_h16 [B, So, So, 160], So = (S - 1) / 2 + 1, channels as above.  conv1 is
+ * then mb_convbn_layer on it with Cin 147, in_cs 160, a 1 x 1 kernel and conv1.weight [64, 3, 7, 7] read as [64, 147, 1, 1].  No synchronisation. */
+int mb_resnet_stem_cols(const void* image_h16, void* cols_h16, int B, int S, mb_stream stream);
+/* The distance alone: logits fp32 [2B, N] (the first B rows against the last B), feat_h16 fp16 [2B, F] or NULL (F % 8 == 0) -> per_pair double [B] =
+ * mean_i (a_i - b_i)^2 over the logits (+ the same over feat); sum (may be NULL) += per_pair in pair order.  No synchronisation. */
+int mb_resnet_distance(const float* logits, const void* feat_h16, int B, int N, long long F, double* per_pair, double* sum, mb_stream stream);
+/* The trunk on a caller's normalised image fp16 [B, S, S, 4] (channel 3 is not read), S % 8 == 0 in [32, 224], B <= 2 max_pairs -- the network is
+ * convolutional up to the spatial mean, so it runs at any side.  Each output may be NULL: layer1 .. layer4 fp16 NHWC [B, s, s, {256, 512, 1024,
+ * 2048}] with s = ceil(S / 4), then halved rounding up three times; pool fp32 [B, 2048]; logits fp32 [B, 1000]. */
+int mb_resnet_taps(mb_resnet* h, const void* image_h16, int B, int S, void* layer1, void* layer2, void* layer3, void* layer4, float* pool, float* logits,
+                   mb_stream stream);
+
 /* ---- the Taming tokenizer (spatial_attention.hip, taming.hip).
  * mb_spatial_attention: the AttnBlock's attention as the handle launches it: one head of 512 channels over the N pixels of each of B images,
  * out[b, i] = sum_j softmax_j(q[b, i] . k[b, j] * 512^-0.5) v[b, j].  q, k, v fp16, pixel (b, i) at element (b N + i) * ld of each (ld >= 512,

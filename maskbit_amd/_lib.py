@@ -193,6 +193,17 @@ SIGNATURES = {
     "mb_pool3": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
     "mb_inception_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mb_inception_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "mb_resnet_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "mb_resnet_destroy": (None, [C.c_void_p]),
+    "mb_resnet_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "mb_resnet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
+    "mb_resnet_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
+    "mb_convbn_layer_ex": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(C.c_uint)] + [C.c_int] * 16 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mb_pool3_ex": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
+    "mb_resnet_input": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "mb_resnet_stem_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mb_resnet_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mb_resnet_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
     "mb_taming_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mb_taming_destroy": (None, [C.c_void_p]),
     "mb_taming_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

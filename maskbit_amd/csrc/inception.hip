@@ -17,7 +17,9 @@
 //   Every output element is a chain of MFMAs over the same K order whatever the tile shape, the pixel's place in its tile or the batch: a
 // pixel's bits do not depend on the variant, on B or on the other images.
 //   Epilogue: v = fma(acc, scale[c], shift[c]) in fp32 (BatchNorm in evaluation mode, eps 1e-3; the scale stays out of the fp16 weights because
-// the checkpoint's variances span decades), ReLU, fp16 store saturating at 65504 and counted.
+// the checkpoint's variances span decades), ReLU, fp16 store saturating at 65504 and counted.  Two more epilogues serve ResNet-50's bottlenecks
+// (resnet.hip): linear (no ReLU; saturation on |v|) and residual (relu(v + identity), the identity an fp16 channel slice, the add in fp32).
+// The epilogue is a template parameter: the ReLU form's instructions are what they were.
 //
 // Two instantiations: <4, 4> (64 pixels x 64 channels a wave: 16 MFMAs per 8 fragment loads) from 512 such tiles up, else <2, 2> (the 8 x 8 maps,
 // and everything at small batches).
@@ -45,7 +47,8 @@ struct ConvBnArgs {
   int Ho, Wo, M, cin_pad, cout_pad, nch, T, ntn, ntiles, tail;
 };
 
-template <int MJ, int NI>
+// EPI: the epilogue (mb_incep.h CONVBN_RELU / CONVBN_LINEAR / CONVBN_RESIDUAL); the K walk is the same for all three
+template <int MJ, int NI, int EPI>
 __global__ __launch_bounds__(IC_THREADS) void convbn_kernel(ConvBnArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
   const int tile = blockIdx.x * (IC_THREADS / 64) + wave;
@@ -127,9 +130,23 @@ __global__ __launch_bounds__(IC_THREADS) void convbn_kernel(ConvBnArgs a) {
       for (int j = 0; j < MJ; ++j) {
         const int p = p0 + j * 16 + l15;
         if (p < a.M) {
-          const float v[4] = {fmaxf(fmaf(acc[i][j][0], sc.x, sh.x), 0.f), fmaxf(fmaf(acc[i][j][1], sc.y, sh.y), 0.f),
-                              fmaxf(fmaf(acc[i][j][2], sc.z, sh.z), 0.f), fmaxf(fmaf(acc[i][j][3], sc.w, sh.w), 0.f)};
-          nsat += fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) > MB_H16_MAX ? 1u : 0u;
+          float v[4];
+          if constexpr (EPI == CONVBN_RELU) {
+            v[0] = fmaxf(fmaf(acc[i][j][0], sc.x, sh.x), 0.f); v[1] = fmaxf(fmaf(acc[i][j][1], sc.y, sh.y), 0.f);
+            v[2] = fmaxf(fmaf(acc[i][j][2], sc.z, sh.z), 0.f); v[3] = fmaxf(fmaf(acc[i][j][3], sc.w, sh.w), 0.f);
+            nsat += fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) > MB_H16_MAX ? 1u : 0u;
+          } else if constexpr (EPI == CONVBN_LINEAR) {             // the downsample branch: no ReLU, saturation on |v|
+            v[0] = fmaf(acc[i][j][0], sc.x, sh.x); v[1] = fmaf(acc[i][j][1], sc.y, sh.y);
+            v[2] = fmaf(acc[i][j][2], sc.z, sh.z); v[3] = fmaf(acc[i][j][3], sc.w, sh.w);
+            nsat += fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) > MB_H16_MAX ? 1u : 0u;
+          } else {                                                 // the end of a bottleneck: + identity in fp32, ReLU, one rounding
+            const h16x4 id = *(const h16x4*)(q.idn + (size_t)p * q.idn_cs + q.idn_off + nl);
+            v[0] = fmaxf(__fadd_rn(fmaf(acc[i][j][0], sc.x, sh.x), (float)id[0]), 0.f);
+            v[1] = fmaxf(__fadd_rn(fmaf(acc[i][j][1], sc.y, sh.y), (float)id[1]), 0.f);
+            v[2] = fmaxf(__fadd_rn(fmaf(acc[i][j][2], sc.z, sh.z), (float)id[2]), 0.f);
+            v[3] = fmaxf(__fadd_rn(fmaf(acc[i][j][3], sc.w, sh.w), (float)id[3]), 0.f);
+            nsat += fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) > MB_H16_MAX ? 1u : 0u;
+          }
           *(h16x4*)(q.out + (size_t)p * q.out_cs + q.out_off + nl) = h16x4{to_h(v[0]), to_h(v[1]), to_h(v[2]), to_h(v[3])};
         }
       }
@@ -146,10 +163,10 @@ __global__ void repack_convbn_kernel(const float* __restrict__ w, h16* __restric
   }
 }
 
-__global__ void bn_fold_kernel(const float* __restrict__ bn, float* __restrict__ scale, float* __restrict__ shift, int cout) {
+__global__ void bn_fold_kernel(const float* __restrict__ bn, float* __restrict__ scale, float* __restrict__ shift, int cout, float eps) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cout) return;
-  const float s = __fdiv_rn(bn[c], __fsqrt_rn(__fadd_rn(bn[3 * cout + c], 1e-3f)));
+  const float s = __fdiv_rn(bn[c], __fsqrt_rn(__fadd_rn(bn[3 * cout + c], eps)));
   scale[c] = s;
   shift[c] = __fsub_rn(bn[cout + c], __fmul_rn(bn[2 * cout + c], s));
 }
@@ -157,7 +174,7 @@ __global__ void bn_fold_kernel(const float* __restrict__ bn, float* __restrict__
 // one thread per (output pixel, 8-channel slot)
 template <int MODE>
 __global__ __launch_bounds__(IC_THREADS) void pool3_kernel(Pool3 q, int Ho, int Wo) {
-  constexpr int ST = MODE == 0 ? 2 : 1, PAD = MODE == 0 ? 0 : 1;
+  constexpr int ST = (MODE == 0 || MODE == 3) ? 2 : 1, PAD = MODE == 0 ? 0 : 1;
   const int ns = q.C / 8;
   const size_t total = (size_t)q.B * Ho * Wo * ns;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -279,6 +296,9 @@ const char* convbn_refusal(const ConvBn& q) {
   if (q.H + 2 * q.ph < q.kh || q.W + 2 * q.pw < q.kw) return "the image is smaller than the kernel";
   if (q.in_off < 0 || q.in_off % 8 || q.in_cs % 8 || q.in_off + (q.cin + 7) / 8 * 8 > q.in_cs)
     return "input slice: offset and stride must be multiples of 8 channels and hold Cin rounded up to 8";
+  if (q.epi < CONVBN_RELU || q.epi > CONVBN_RESIDUAL) return "epilogue must be 0 (ReLU), 1 (linear) or 2 (residual + ReLU)";
+  if (q.epi == CONVBN_RESIDUAL && (!q.idn || q.idn_off < 0 || q.idn_off % 4 || q.idn_cs % 4 || q.idn_off + q.cout > q.idn_cs))
+    return "identity slice: a pointer, and offset and stride multiples of 4 channels that hold Cout";
   if (q.cout % 4 || q.out_off < 0 || q.out_off % 4 || q.out_cs % 4 || q.out_off + q.cout > q.out_cs)
     return "output slice: Cout, offset and stride must be multiples of 4 channels";
   const size_t M = (size_t)q.B * ic_out_size(q.H, q.kh, q.stride, q.ph) * ic_out_size(q.W, q.kw, q.stride, q.pw);
@@ -301,10 +321,16 @@ void launch_convbn(hipStream_t s, const ConvBn& q, int variant) {
   if (variant == 0) variant = big_tiles >= 512 ? 1 : 2;
   if (variant == 1) {
     a.ntn = a.cout_pad / 64; a.ntiles = big_tiles;
-    hipLaunchKernelGGL((convbn_kernel<4, 4>), dim3((a.ntiles + 3) / 4), dim3(IC_THREADS), 0, s, a);
+    const dim3 grid((a.ntiles + 3) / 4), block(IC_THREADS);
+    if (q.epi == CONVBN_RELU) hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_RELU>), grid, block, 0, s, a);
+    else if (q.epi == CONVBN_LINEAR) hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_LINEAR>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_RESIDUAL>), grid, block, 0, s, a);
   } else {
     a.ntn = a.cout_pad / 32; a.ntiles = ((a.M + 31) / 32) * a.ntn;
-    hipLaunchKernelGGL((convbn_kernel<2, 2>), dim3((a.ntiles + 3) / 4), dim3(IC_THREADS), 0, s, a);
+    const dim3 grid((a.ntiles + 3) / 4), block(IC_THREADS);
+    if (q.epi == CONVBN_RELU) hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_RELU>), grid, block, 0, s, a);
+    else if (q.epi == CONVBN_LINEAR) hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_LINEAR>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_RESIDUAL>), grid, block, 0, s, a);
   }
 }
 
@@ -313,13 +339,14 @@ void launch_repack_convbn(hipStream_t s, const float* w_oihw, h16* out, int cout
   hipLaunchKernelGGL(repack_convbn_kernel, dim3(grid_for((size_t)kh * kw * cop * cip)), dim3(IC_THREADS), 0, s, w_oihw, out, cout, cin, kh * kw, cop, cip);
 }
 
-void launch_bn_fold(hipStream_t s, const float* bn, float* scale, float* shift, int cout) {
-  hipLaunchKernelGGL(bn_fold_kernel, dim3((cout + IC_THREADS - 1) / IC_THREADS), dim3(IC_THREADS), 0, s, bn, scale, shift, cout);
+void launch_bn_fold(hipStream_t s, const float* bn, float* scale, float* shift, int cout, float eps) {
+  hipLaunchKernelGGL(bn_fold_kernel, dim3((cout + IC_THREADS - 1) / IC_THREADS), dim3(IC_THREADS), 0, s, bn, scale, shift, cout, eps);
 }
 
 const char* pool3_refusal(const Pool3& q) {
   if (!q.in || !q.out) return "null argument";
-  if (q.mode < 0 || q.mode > 2) return "mode must be 0 (max, stride 2), 1 (max, stride 1, padding 1) or 2 (average, stride 1, padding 1)";
+  if (q.mode < 0 || q.mode > 3)
+    return "mode must be 0 (max, stride 2), 1 (max, stride 1, padding 1), 2 (average, stride 1, padding 1) or 3 (max, stride 2, padding 1)";
   if (q.B < 1 || q.C < 8 || q.C % 8 || q.H < 1 || q.W < 1 || (q.mode == 0 && (q.H < 3 || q.W < 3))) return "empty shape, or C not a multiple of 8";
   if (q.in_off < 0 || q.in_off % 8 || q.in_cs % 8 || q.in_off + q.C > q.in_cs || q.out_off < 0 || q.out_off % 8 || q.out_cs % 8 || q.out_off + q.C > q.out_cs)
     return "slices: offsets and strides must be multiples of 8 channels and hold C";
@@ -327,11 +354,12 @@ const char* pool3_refusal(const Pool3& q) {
 }
 
 void launch_pool3(hipStream_t s, const Pool3& q) {
-  const int Ho = q.mode == 0 ? (q.H - 3) / 2 + 1 : q.H, Wo = q.mode == 0 ? (q.W - 3) / 2 + 1 : q.W;
+  const int Ho = ic_pool_size(q.H, q.mode), Wo = ic_pool_size(q.W, q.mode);
   const dim3 grid(grid_for((size_t)q.B * Ho * Wo * (q.C / 8))), block(IC_THREADS);
   if (q.mode == 0) hipLaunchKernelGGL(pool3_kernel<0>, grid, block, 0, s, q, Ho, Wo);
   else if (q.mode == 1) hipLaunchKernelGGL(pool3_kernel<1>, grid, block, 0, s, q, Ho, Wo);
-  else hipLaunchKernelGGL(pool3_kernel<2>, grid, block, 0, s, q, Ho, Wo);
+  else if (q.mode == 2) hipLaunchKernelGGL(pool3_kernel<2>, grid, block, 0, s, q, Ho, Wo);
+  else hipLaunchKernelGGL(pool3_kernel<3>, grid, block, 0, s, q, Ho, Wo);
 }
 
 void launch_inception_input(hipStream_t s, const uint8_t* u8, h16* out, int B, int H, int W) {
@@ -602,7 +630,7 @@ int mb_inception_load(mb_inception* h, const char* name, const float* data, cons
       if (rest != IC_BN_NAMES[k]) continue;
       if (numel != (size_t)c.cout) return fail(-4, "mb_inception_load: %s: expected %d values", name, c.cout);
       HIP_TRY(hipMemcpyAsync(c.bn + (size_t)k * c.cout, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-      launch_bn_fold(s, c.bn, c.scale, c.shift, c.cout);
+      launch_bn_fold(s, c.bn, c.scale, c.shift, c.cout, IC_BN_EPS);
       h->loaded[l * 5 + 1 + k] = 1;
       return launched();
     }
@@ -636,12 +664,13 @@ int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, m
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----
-int mb_convbn_layer(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
-                    int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
-                    mb_stream stream) {
+int mb_convbn_layer_ex(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
+                       int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
+                       int epilogue, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!w_oihw || variant < 0 || variant > 2) return fail(-1, "mb_convbn_layer: bad arguments");
-  ConvBn q{(const h16*)in_h16, nullptr, scale, shift, (h16*)out_h16, nullptr, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, in_off, in_cs, out_off, out_cs};
+  ConvBn q{(const h16*)in_h16, nullptr, scale, shift, (h16*)out_h16, nullptr, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, in_off, in_cs, out_off, out_cs,
+           epilogue, (const h16*)identity_h16, idn_off, idn_cs};
   if (const char* why = convbn_refusal(q)) return fail(-1, "mb_convbn_layer: %s", why);
   DevArena m;
   h16* w = nullptr;
@@ -659,11 +688,24 @@ int mb_convbn_layer(const void* in_h16, const float* w_oihw, const float* scale,
   return rc;
 }
 
-int mb_pool3(const void* x_h16, void* y_h16, int B, int H, int W, int C, int mode, int in_off, int in_cs, int out_off, int out_cs, mb_stream stream) {
+int mb_convbn_layer(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
+                    int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
+                    mb_stream stream) {
+  return mb_convbn_layer_ex(in_h16, w_oihw, scale, shift, out_h16, saturated, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, in_off, in_cs, out_off, out_cs,
+                            variant, CONVBN_RELU, nullptr, 0, 0, stream);
+}
+
+int mb_pool3_ex(const void* x_h16, void* y_h16, int B, int H, int W, int C, int mode, int in_off, int in_cs, int out_off, int out_cs, mb_stream stream) {
   const Pool3 q{(const h16*)x_h16, (h16*)y_h16, B, H, W, C, mode, in_off, in_cs, out_off, out_cs};
   if (const char* why = pool3_refusal(q)) return fail(-1, "mb_pool3: %s", why);
   launch_pool3((hipStream_t)stream, q);
   return launched();
+}
+
+// the three pools of Inception-v3; mode 3 (ResNet's) is mb_pool3_ex's
+int mb_pool3(const void* x_h16, void* y_h16, int B, int H, int W, int C, int mode, int in_off, int in_cs, int out_off, int out_cs, mb_stream stream) {
+  if (mode == 3) return fail(-1, "mb_pool3: mode must be 0, 1 or 2 (mode 3 is taken by mb_pool3_ex)");
+  return mb_pool3_ex(x_h16, y_h16, B, H, W, C, mode, in_off, in_cs, out_off, out_cs, stream);
 }
 
 int mb_inception_input(const uint8_t* u8, void* out_h16, int B, int H, int W, mb_stream stream) {

@@ -18,6 +18,13 @@ constexpr int IC_INC = 8;                 // channels of the input image buffer 
 inline int ic_cin_pad(int cin) { return (cin + IC_CK - 1) / IC_CK * IC_CK; }
 inline int ic_cout_pad(int cout) { return (cout + IC_BN - 1) / IC_BN * IC_BN; }
 inline int ic_out_size(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+inline int ic_pool_size(int n, int mode) { return mode == 0 ? (n - 3) / 2 + 1 : mode == 3 ? (n - 1) / 2 + 1 : n; }
+constexpr float IC_BN_EPS = 1e-3f;        // Inception's BatchNorm epsilon (ResNet's is 1e-5: mb_resnet.h)
+
+// the epilogues of the convolution, v = fma(acc, scale, shift) in fp32:
+enum { CONVBN_RELU = 0,                   // fp16(relu(v)): BasicConv2d, and the first two convolutions of a bottleneck
+       CONVBN_LINEAR = 1,                 // fp16(v): a bottleneck's downsample branch; saturation is counted on |v|
+       CONVBN_RESIDUAL = 2 };             // fp16(relu(v + float(identity[p][c]))): the add in fp32, one rounding
 
 // One BasicConv2d: out = fp16(relu(scale * conv(in, w) + shift)), see include/maskbit_hip_diag.h mb_convbn_layer for the geometry taken
 struct ConvBn {
@@ -25,6 +32,9 @@ struct ConvBn {
   int B, H, W, cin, cout;
   int kh, kw, stride, ph, pw;
   int in_off, in_cs, out_off, out_cs;
+  int epi = CONVBN_RELU;
+  const h16* idn = nullptr;               // CONVBN_RESIDUAL: channels [idn_off, idn_off + cout) of fp16 [B, Ho, Wo, idn_cs]
+  int idn_off = 0, idn_cs = 0;
 };
 // null, or why the geometry is not taken
 const char* convbn_refusal(const ConvBn& q);
@@ -32,12 +42,12 @@ const char* convbn_refusal(const ConvBn& q);
 void launch_convbn(hipStream_t s, const ConvBn& q, int variant = 0);
 // fp32 OIHW [cout, cin, kh, kw] (device) -> fp16 [kh * kw][ic_cout_pad(cout)][ic_cin_pad(cin)], zero-filled
 void launch_repack_convbn(hipStream_t s, const float* w_oihw, h16* out, int cout, int cin, int kh, int kw);
-// bn fp32 [4][cout] = gamma, beta, running mean, running variance -> scale = gamma / sqrt(var + 1e-3), shift = beta - mean * scale
-void launch_bn_fold(hipStream_t s, const float* bn, float* scale, float* shift, int cout);
+// bn fp32 [4][cout] = gamma, beta, running mean, running variance -> scale = gamma / sqrt(var + eps), shift = beta - mean * scale
+void launch_bn_fold(hipStream_t s, const float* bn, float* scale, float* shift, int cout, float eps);
 
 struct Pool3 {
   const h16* in; h16* out;
-  int B, H, W, C, mode;                   // 0 max s2 valid, 1 max s1 p1, 2 avg s1 p1 (divisor = in-image taps)
+  int B, H, W, C, mode;                   // 0 max s2 valid, 1 max s1 p1, 2 avg s1 p1 (divisor = in-image taps), 3 max s2 p1 (in-image taps only)
   int in_off, in_cs, out_off, out_cs;
 };
 const char* pool3_refusal(const Pool3& q);

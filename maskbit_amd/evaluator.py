@@ -75,6 +75,9 @@ class TokenizerEvaluator:
         self.last_lpips: Optional[torch.Tensor] = None
         self._lpips = None
         self._lpips_sum: Optional[torch.Tensor] = None
+        self.last_perceptual: Optional[torch.Tensor] = None
+        self._perceptual = None
+        self._perceptual_sum: Optional[torch.Tensor] = None
         self._inception = None                                                                # use_inception(): the extractor and its three states
         self._rfid = self._inception_score = False
         self._is_stats = self._rfid_real = self._rfid_fake = None
@@ -99,6 +102,9 @@ class TokenizerEvaluator:
         self.last_lpips = None
         if self._lpips_sum is not None:
             self._lpips_sum.zero_()
+        self.last_perceptual = None
+        if self._perceptual_sum is not None:
+            self._perceptual_sum.zero_()
         for stats in (self._is_stats, self._rfid_real, self._rfid_fake):
             if stats is not None:
                 stats.reset()
@@ -140,6 +146,25 @@ class TokenizerEvaluator:
         if self._lpips_sum is None:
             self._lpips_sum = torch.zeros(1, dtype=torch.float64, device=self._device)
 
+    def use_perceptual(self, model) -> None:
+        """Attaches a loaded ``maskbit_amd.PerceptualLoss`` on the evaluator's device (``None`` detaches): ``update()`` then also adds the batch's
+        per-pair ResNet-50 perceptual distances to a float64 device sum (``last_perceptual`` holds the batch's [B] values) and ``result()`` reports
+        ``"PerceptualLoss"``, their mean -- what the reference's ``PerceptualLoss.forward`` gives over the same pairs.  The reference's evaluator
+        has no such entry; the key is there only while a model is attached.  Attach before the first ``update()`` of a pass, or call
+        ``reset_metrics()``."""
+        if model is None:
+            self._perceptual = None
+            return
+        from .perceptual import PerceptualLoss
+        if not isinstance(model, PerceptualLoss):
+            raise TypeError(f"use_perceptual() takes a maskbit_amd.PerceptualLoss, got {type(model).__name__}")
+        dev = model._require_cuda("use_perceptual")
+        if (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device.index:
+            raise ValueError(f"the PerceptualLoss model is on {dev}, the evaluator on {self._device}")
+        self._perceptual = model
+        if self._perceptual_sum is None:
+            self._perceptual_sum = torch.zeros(1, dtype=torch.float64, device=self._device)
+
     def update(self, real_images: torch.Tensor, fake_images: torch.Tensor, codebook_indices: Optional[torch.Tensor] = None, clamp: bool = False):
         """Adds a batch.  ``real_images`` / ``fake_images``: [B, C, H, W] of any float dtype (cast to contiguous fp32 only when needed), equal
         element counts (``real`` is viewed as ``fake``, evaluator.py:283), H, W >= 6, C == 3 when SSIM is enabled.  ``clamp=True`` clamps both
@@ -163,6 +188,8 @@ class TokenizerEvaluator:
             raise ValueError(f"codebook_indices must be an integer tensor, got {codebook_indices.dtype}")
         if self._lpips is not None:
             self._lpips.check_images(tuple(fake_images.shape), tuple(fake_images.shape))      # sizes the engine does not take: ValueError, no device work
+        if self._perceptual is not None:
+            self._perceptual.check_images(tuple(fake_images.shape), tuple(fake_images.shape))
         lib = _lib.load()
         need = int(lib.mb_eval_workspace_bytes(B, C, H, W)) if self._metrics else 0
         if self._metrics and need == 0:
@@ -195,6 +222,8 @@ class TokenizerEvaluator:
                     self._rfid_fake.add(pool_fake)
             if self._lpips is not None:                                                         # evaluator.py:366-368
                 self.last_lpips = self._lpips._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._lpips_sum)
+            if self._perceptual is not None:
+                self.last_perceptual = self._perceptual._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._perceptual_sum)
             if self._codebook:
                 idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
                 _lib.check(lib.mb_eval_codebook(idx.data_ptr(), idx.numel(), self._num_codebook_entries, self._hist.data_ptr(),
@@ -211,7 +240,10 @@ class TokenizerEvaluator:
         lp = self._lpips is not None
         if lp:
             parts.append(self._lpips_sum)
-        cb = 5 if lp else 4                                                                      # position of the codebook figures
+        pl = self._perceptual is not None
+        if pl:
+            parts.append(self._perceptual_sum)
+        cb = 4 + int(lp) + int(pl)                                                               # position of the codebook figures
         if self._codebook:
             counts = self._hist.double()
             probs = counts / counts.sum()
@@ -248,6 +280,8 @@ class TokenizerEvaluator:
             eval_score["rFID"] = frechet_distance(t_real / n, get_covariance(s_real, t_real, n), t_fake / n, get_covariance(s_fake, t_fake, n))
         if lp:
             eval_score["LPIPS"] = host[4].item() / n                                            # evaluator.py:453-455
+        if pl:
+            eval_score["PerceptualLoss"] = host[cb - 1].item() / n
         if self._enable_codebook_usage_measure:
             eval_score["CodebookUsage"] = float(int(host[cb])) / self._num_codebook_entries
         if self._enable_codebook_entropy_measure:

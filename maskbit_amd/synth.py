@@ -520,3 +520,51 @@ def make_inception_weights(seed: int, style: str = "he") -> StateDict:
     sd["fc.weight"] = torch.randn(n, d, generator=g) / math.sqrt(d)
     sd["fc.bias"] = torch.randn(n, generator=g) * 0.1
     return sd
+
+
+# torchvision's resnet50 (v1.5; DESIGN.md "ResNet-50"): (convolution key, BatchNorm key, Cin, Cout, kernel, stride), in state-dict order
+ResNetConv = Tuple[str, str, int, int, int, int]
+RESNET50_BLOCKS = (3, 4, 6, 3)
+RESNET50_FC = (1000, 2048)
+RESNET50_RESIDUAL_GAIN = 0.3
+
+
+def resnet50_convs() -> List[ResNetConv]:
+    convs: List[ResNetConv] = [("conv1", "bn1", 3, 64, 7, 2)]
+    cin = 64
+    for layer, blocks in enumerate(RESNET50_BLOCKS):
+        width = 64 << layer
+        for b in range(blocks):
+            p = f"layer{layer + 1}.{b}"
+            stride = 2 if (b == 0 and layer > 0) else 1
+            convs += [(p + ".conv1", p + ".bn1", cin, width, 1, 1), (p + ".conv2", p + ".bn2", width, width, 3, stride),
+                      (p + ".conv3", p + ".bn3", width, 4 * width, 1, 1)]
+            if b == 0:
+                convs.append((p + ".downsample.0", p + ".downsample.1", cin, 4 * width, 1, stride))
+            cin = 4 * width
+    return convs
+
+
+def make_resnet50_weights(seed: int) -> StateDict:
+    """Seeded weights of torchvision's resnet50 under its own keys (``conv1.weight``, ``bn1.*``, ``layerL.B.*``, ``fc.*``; the
+    ``num_batches_tracked`` counters included, as 0): 53 convolutions x 6 + 2 = 320 entries, 25 557 032 parameters.  The ImageNet checkpoint is not
+    available here; these stand in for it.
+
+    He-normal convolutions (std = sqrt(2 / fan_in)); BatchNorm gamma in [0.8, 1.2), beta N(0, 0.1), running mean N(0, 0.1), running variance in
+    [0.8, 1.25) -- except the last BatchNorm of every bottleneck (``bn3``), whose gamma is times RESNET50_RESIDUAL_GAIN: sixteen residual adds of
+    unit-variance branches would otherwise grow the stream fourfold, which trained networks do not do.  ``fc``: N(0, 1 / sqrt(2048)) weights and
+    N(0, 0.1) bias: logits of order 1."""
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+    for conv, bn, cin, cout, k, _stride in resnet50_convs():
+        sd[conv + ".weight"] = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
+        gamma = 0.8 + 0.4 * torch.rand(cout, generator=g)
+        if bn.endswith(".bn3"):
+            gamma = gamma * RESNET50_RESIDUAL_GAIN
+        sd[bn + ".weight"], sd[bn + ".bias"] = gamma, torch.randn(cout, generator=g) * 0.1
+        sd[bn + ".running_mean"], sd[bn + ".running_var"] = torch.randn(cout, generator=g) * 0.1, 0.8 + 0.45 * torch.rand(cout, generator=g)
+        sd[bn + ".num_batches_tracked"] = torch.zeros((), dtype=torch.int64)
+    n, d = RESNET50_FC
+    sd["fc.weight"] = torch.randn(n, d, generator=g) / math.sqrt(d)
+    sd["fc.bias"] = torch.randn(n, generator=g) * 0.1
+    return sd
