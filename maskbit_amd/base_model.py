@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Callable, Dict, Iterable, Optional, Tuple, Union
+from typing import Callable, Dict, Iterable, Mapping, Optional, Tuple, Union
 
 import torch
 
@@ -43,6 +43,16 @@ def _init_tensor(shape, kind: str) -> torch.Tensor:
     raise ValueError(kind)
 
 
+StateLike = Union[str, os.PathLike, Mapping[str, torch.Tensor]]
+
+
+def read_state(src: StateLike) -> Dict[str, torch.Tensor]:
+    """a checkpoint path (``torch.load`` onto the CPU) or a state dict -> a dict of its own"""
+    if isinstance(src, (str, os.PathLike)):
+        src = torch.load(os.fspath(src), map_location="cpu")
+    return dict(src)
+
+
 class BaseModel(torch.nn.Module):
     def __init__(self):
         super().__init__()
@@ -62,6 +72,18 @@ class BaseModel(torch.nn.Module):
             mod.register_buffer(parts[-1], tensor)
         else:
             mod.register_parameter(parts[-1], torch.nn.Parameter(tensor))
+
+    def _attach_convbn(self, conv: str, bn: str, shape, counter: bool) -> None:
+        """a bias-free convolution ``conv``.weight [cout, cin, kh, kw] and its BatchNorm ``bn``.* -- weight, bias, the two running statistics
+        and, with ``counter``, torch's ``num_batches_tracked`` buffer -- as zeros"""
+        cout = shape[0]
+        self._attach(conv + ".weight", torch.zeros(*shape))
+        self._attach(bn + ".weight", torch.zeros(cout))
+        self._attach(bn + ".bias", torch.zeros(cout))
+        self._attach(bn + ".running_mean", torch.zeros(cout), buffer=True)
+        self._attach(bn + ".running_var", torch.zeros(cout), buffer=True)
+        if counter:
+            self._attach(bn + ".num_batches_tracked", torch.zeros((), dtype=torch.int64), buffer=True)
 
     def _build(self, specs: Iterable[ParamSpec]) -> None:
         for key, shape, kind in specs:
@@ -200,3 +222,73 @@ class BaseModel(torch.nn.Module):
                 torch.cuda.current_stream().synchronize()          # temporaries in `keep` must outlive the repack
                 self._engine_sig = sig
         return self._engine
+
+
+class PairLoss(BaseModel):
+    """What the image-pair losses (``LPIPS``, ``PerceptualLoss``) share: the shape checks, the run in chunks into a float64 [B] device tensor,
+    ``per_image`` and the grow-only engine.  A subclass states its network (``_INPUT``, for the messages), its size rule (``_size_error``), what
+    to say while it has no weights (``_no_weights``), its chunk size (``_chunk``) and the one ``mb_*_forward`` call (``_forward_chunk``)."""
+    max_pairs_per_call = 16
+    _INPUT = ""
+
+    @staticmethod
+    def _size_error(H: int, W: int) -> Optional[str]:
+        """what the engine takes instead, when it does not take H x W"""
+        raise NotImplementedError
+
+    def _no_weights(self) -> Optional[str]:
+        """which loaders to call first, while weights are missing"""
+        raise NotImplementedError
+
+    def _chunk(self, H: int, W: int) -> int:
+        return int(self.max_pairs_per_call)
+
+    def _forward_chunk(self, h, a: int, b: int, n: int, H: int, W: int, clamp: int, out: int, running_sum: Optional[int], stream: int) -> int:
+        raise NotImplementedError
+
+    def engine(self, pairs: int, H: int = 0, W: int = 0):
+        have = self._engine_key[1] if self._engine_key else 0
+        return self._ensure_engine(max(pairs, have))
+
+    @classmethod
+    def check_images(cls, shape_a, shape_b) -> None:
+        """``ValueError`` for what the engine does not take; no device work."""
+        name = cls.__name__
+        if len(shape_a) != 4 or tuple(shape_a) != tuple(shape_b):
+            raise ValueError(f"{name} expects two [B, 3, H, W] batches of one shape, got {tuple(shape_a)} and {tuple(shape_b)}")
+        B, Cc, H, W = (int(v) for v in shape_a)
+        if B < 1:
+            raise ValueError(f"{name}: empty batch {tuple(shape_a)}")
+        if Cc != 3:
+            raise ValueError(f"{name} takes 3 channels (the {cls._INPUT} input), got {Cc}")
+        why = cls._size_error(H, W)
+        if why:
+            raise ValueError(f"{name}: images of {H} x {W}: the HIP engine takes {why}")
+
+    def _run(self, a: torch.Tensor, b: torch.Tensor, clamp: bool, running_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self.check_images(a.shape, b.shape)
+        why = self._no_weights()
+        if why:
+            raise RuntimeError(f"{type(self).__name__} has no weights yet: call {why} first (nothing is loaded at construction)")
+        dev = self._require_cuda("forward")
+        B, _, H, W = (int(v) for v in a.shape)
+        a = a.to(device=dev, dtype=torch.float32).contiguous()
+        b = b.to(device=dev, dtype=torch.float32).contiguous()
+        chunk = max(1, min(B, self._chunk(H, W)))
+        h = self.engine(chunk, H, W)
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+        total = running_sum.data_ptr() if running_sum is not None else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            for b0 in range(0, B, chunk):
+                n = min(chunk, B - b0)
+                rc = self._forward_chunk(h, a[b0:b0 + n].data_ptr(), b[b0:b0 + n].data_ptr(), n, H, W, 1 if clamp else 0, out[b0:b0 + n].data_ptr(),
+                                         total, stream)
+                _lib.check(rc, f"mb_{self._ABI}_forward")
+        return out
+
+    @torch.no_grad()
+    def per_image(self, input: torch.Tensor, target: torch.Tensor, clamp: bool = False) -> torch.Tensor:
+        """The loss of every pair as float64 [B] on the device (``clamp=True``: both images clamped to [0, 1] inside the input kernel).  Batches
+        beyond the chunk size (``max_pairs_per_call``) are walked in chunks; a pair's value does not depend on the chunking.  No synchronisation."""
+        return self._run(input, target, clamp)

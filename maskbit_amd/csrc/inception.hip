@@ -33,6 +33,7 @@
 #include "../../include/maskbit_hip.h"
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
+#include "mb_convnet.h"
 #include "mb_incep.h"
 
 namespace mb {
@@ -385,19 +386,13 @@ void launch_fc_head(hipStream_t s, const float* pool, const float* w, const floa
 // ---- the network ------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct IcConv {
-  std::string name;
-  int cin = 0, cout = 0, kh = 1, kw = 1, stride = 1, ph = 0, pw = 0;
-  h16* w = nullptr;
-  float *bn = nullptr, *scale = nullptr, *shift = nullptr;     // bn [4][cout]: gamma, beta, running mean, running variance
-};
 struct IcView { int buf, off, cs, H, W, C; };                  // channels [off, off + C) of buffer `buf`, [B, H, W, cs]
 enum { IC_OP_CONV, IC_OP_POOL, IC_OP_MEAN, IC_OP_MAP, IC_OP_SPATIAL };
 struct IcOp { int kind, idx; IcView in, out; std::string scope; };   // idx: the convolution, the pool mode, the fp32 tap (0 .. 2) or the fp16 map (0 .. 3)
 constexpr int IC_NBUF = 5;                                     // 0 / 1: a block's input and output in turn; 2 / 3: a branch's intermediates; 4: the pooled input
 
 struct IcNet {
-  std::vector<IcConv> convs;
+  ConvNet* cn = nullptr;                                       // where conv() puts its records: the handle's
   std::vector<IcOp> ops;
   size_t need[IC_NBUF] = {0, 0, 0, 0, 0};                      // fp16 elements per image
   IcView last{0, 0, 0, 0, 0, 0};
@@ -405,11 +400,9 @@ struct IcNet {
 
   IcView claim(IcView v) { need[v.buf] = std::max(need[v.buf], (size_t)v.H * v.W * v.cs); return v; }
   IcView conv(const std::string& name, IcView in, int cout, int kh, int kw, int stride, int ph, int pw, int obuf, int ooff = 0, int ocs = 0) {
-    IcConv c;
-    c.name = name; c.cin = in.C; c.cout = cout; c.kh = kh; c.kw = kw; c.stride = stride; c.ph = ph; c.pw = pw;
-    convs.push_back(c);
+    const int idx = add_conv(*cn, name + ".conv.weight", name + ".bn", in.C, cout, kh, kw, stride, ph, pw);   // the checkpoint's naming
     const IcView out = claim({obuf, ooff, ocs ? ocs : cout, ic_out_size(in.H, kh, stride, ph), ic_out_size(in.W, kw, stride, pw), cout});
-    ops.push_back({IC_OP_CONV, (int)convs.size() - 1, in, out, "inception_conv." + group});
+    ops.push_back({IC_OP_CONV, idx, in, out, "inception_conv." + group});
     return out;
   }
   IcView c1(const std::string& name, IcView in, int cout, int obuf, int ooff = 0, int ocs = 0) { return conv(name, in, cout, 1, 1, 1, 0, 0, obuf, ooff, ocs); }
@@ -478,7 +471,8 @@ struct IcNet {
     return whole(r, cs);
   }
 
-  void build() {
+  void build(ConvNet& net) {
+    cn = &net;
     IcView x = claim({0, 0, IC_INC, IC_SIDE, IC_SIDE, 3});
     x = conv("Conv2d_1a_3x3", x, 32, 3, 3, 2, 0, 0, 1);
     x = conv("Conv2d_2a_3x3", x, 32, 3, 3, 1, 0, 0, 0);
@@ -511,21 +505,16 @@ struct IcNet {
   }
 };
 
-constexpr int IC_BN_PARTS = 4;
-const char* const IC_BN_NAMES[IC_BN_PARTS] = {".bn.weight", ".bn.bias", ".bn.running_mean", ".bn.running_var"};
-
 }  // namespace
 
 }  // namespace mb
 
 struct mb_inception {
   int max_images = 0;
+  mb::ConvNet cn;                  // the convolutions, the head, the checkpoint table, the arena (mb_convnet.h)
   mb::IcNet net;
   h16* buf[mb::IC_NBUF] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  float *fc_w = nullptr, *fc_b = nullptr, *pool = nullptr;
-  unsigned* sat = nullptr;
-  std::vector<uint8_t> loaded;     // per convolution 5 entries (weight, the four BatchNorm vectors), then fc.weight, fc.bias
-  mb::DevArena mem;
+  float* pool = nullptr;
 };
 
 using namespace mb;
@@ -536,8 +525,7 @@ struct IcOut { void* map[4]; float* tap[3]; float *pool, *unbiased, *biased; flo
 
 int check_inception(const char* what, mb_inception* h, const uint8_t* u8, int B, int H, int W) {
   if (!h || !u8) return fail(-1, "%s: null argument", what);
-  if (std::find(h->loaded.begin(), h->loaded.end(), (uint8_t)0) != h->loaded.end())
-    return fail(-1, "%s: the checkpoint is not complete (%zu entries: <layer>.conv.weight, <layer>.bn.*, fc.*)", what, h->loaded.size());
+  if (int rc = complete(what, h->cn)) return rc;
   if (B < 1 || B > h->max_images) return fail(-1, "%s: batch %d outside [1, %d] images", what, B, h->max_images);
   if (H < 2 || W < 2 || H > 16384 || W > 16384) return fail(-1, "%s: images of %d x %d: H and W must be in [2, 16384]", what, H, W);
   return 0;
@@ -549,9 +537,9 @@ void run_inception(mb_inception* h, const uint8_t* u8, int B, int H, int W, cons
   { ProfScope p("inception_input", s); launch_inception_input(s, u8, h->buf[0], B, H, W); }
   for (const IcOp& op : h->net.ops) {
     if (op.kind == IC_OP_CONV) {
-      const IcConv& c = h->net.convs[op.idx];
+      const CnConv& c = h->cn.convs[op.idx];
       ProfScope p(op.scope.c_str(), s);
-      launch_convbn(s, ConvBn{at(h, op.in), c.w, c.scale, c.shift, at(h, op.out), h->sat, B, op.in.H, op.in.W, c.cin, c.cout, c.kh, c.kw, c.stride, c.ph, c.pw,
+      launch_convbn(s, ConvBn{at(h, op.in), c.w, c.scale, c.shift, at(h, op.out), h->cn.sat, B, op.in.H, op.in.W, c.cin, c.cout, c.kh, c.kw, c.stride, c.ph, c.pw,
                               op.in.off, op.in.cs, op.out.off, op.out.cs});
     } else if (op.kind == IC_OP_POOL) {
       ProfScope p(op.scope.c_str(), s);
@@ -572,7 +560,7 @@ void run_inception(mb_inception* h, const uint8_t* u8, int B, int H, int W, cons
   { ProfScope p("inception_head", s);
     launch_spatial_mean(s, at(h, f), h->pool, B, f.H * f.W, f.C);
     if (o.pool) (void)hipMemcpyAsync(o.pool, h->pool, (size_t)B * IC_FEAT * sizeof(float), hipMemcpyDeviceToDevice, s);
-    if (o.unbiased || o.biased) launch_fc_head(s, h->pool, h->fc_w, h->fc_b, o.unbiased, o.biased, B, IC_FEAT, IC_NCLASS); }
+    if (o.unbiased || o.biased) launch_fc_head(s, h->pool, h->cn.fc_w, h->cn.fc_b, o.unbiased, o.biased, B, IC_FEAT, IC_NCLASS); }
 }
 
 }  // namespace
@@ -583,17 +571,13 @@ int mb_inception_create(int max_images, mb_inception** out) {
   if (!out || max_images < 1 || max_images > 4096) return fail(-1, "mb_inception_create: bad arguments");
   mb_inception* h = new mb_inception();
   h->max_images = max_images;
-  h->net.build();
-  DevArena& m = h->mem;
-  m.zeroed(&h->sat, 1);
-  for (IcConv& c : h->net.convs) {
-    m.get(&c.w, (size_t)c.kh * c.kw * ic_cout_pad(c.cout) * ic_cin_pad(c.cin));
-    m.zeroed(&c.bn, (size_t)IC_BN_PARTS * c.cout); m.zeroed(&c.scale, (size_t)c.cout); m.zeroed(&c.shift, (size_t)c.cout);
-  }
-  m.get(&h->fc_w, (size_t)IC_NCLASS * IC_FEAT); m.get(&h->fc_b, (size_t)IC_NCLASS); m.get(&h->pool, (size_t)max_images * IC_FEAT);
+  h->cn.bn_eps = IC_BN_EPS;
+  h->net.build(h->cn);
+  add_head(h->cn, "", IC_FEAT, IC_NCLASS);
+  DevArena& m = h->cn.mem;
+  m.get(&h->pool, (size_t)max_images * IC_FEAT);
   for (int i = 0; i < IC_NBUF; ++i) m.get(&h->buf[i], (size_t)max_images * h->net.need[i]);
   if (int rc = m.failed("mb_inception_create")) { delete h; return rc; }
-  h->loaded.assign(h->net.convs.size() * 5 + 2, 0);
   *out = h;
   return 0;
 }
@@ -602,40 +586,7 @@ void mb_inception_destroy(mb_inception* h) { delete h; }
 
 int mb_inception_load(mb_inception* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
   if (!h || !name || !data || !shape || ndim < 0) return fail(-1, "mb_inception_load: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const std::string n(name);
-  size_t numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  const size_t nconv = h->net.convs.size();
-  if (n == "fc.weight" || n == "fc.bias") {
-    const bool isw = n == "fc.weight";
-    if (numel != (isw ? (size_t)IC_NCLASS * IC_FEAT : (size_t)IC_NCLASS)) return fail(-4, "mb_inception_load: %s: wrong size", name);
-    HIP_TRY(hipMemcpyAsync(isw ? h->fc_w : h->fc_b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    h->loaded[nconv * 5 + (isw ? 0 : 1)] = 1;
-    return 0;
-  }
-  for (size_t l = 0; l < nconv; ++l) {
-    const IcConv& c = h->net.convs[l];
-    if (n.compare(0, c.name.size(), c.name) != 0 || n.size() <= c.name.size() || n[c.name.size()] != '.') continue;
-    const std::string rest = n.substr(c.name.size());
-    if (rest == ".bn.num_batches_tracked") return 0;
-    if (rest == ".conv.weight") {
-      if (ndim != 4 || shape[0] != c.cout || shape[1] != c.cin || shape[2] != c.kh || shape[3] != c.kw)
-        return fail(-4, "mb_inception_load: %s: expected [%d, %d, %d, %d]", name, c.cout, c.cin, c.kh, c.kw);
-      launch_repack_convbn(s, data, c.w, c.cout, c.cin, c.kh, c.kw);
-      h->loaded[l * 5] = 1;
-      return launched();
-    }
-    for (int k = 0; k < IC_BN_PARTS; ++k) {
-      if (rest != IC_BN_NAMES[k]) continue;
-      if (numel != (size_t)c.cout) return fail(-4, "mb_inception_load: %s: expected %d values", name, c.cout);
-      HIP_TRY(hipMemcpyAsync(c.bn + (size_t)k * c.cout, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-      launch_bn_fold(s, c.bn, c.scale, c.shift, c.cout, IC_BN_EPS);
-      h->loaded[l * 5 + 1 + k] = 1;
-      return launched();
-    }
-  }
-  return fail(-2, "mb_inception_load: unknown checkpoint entry '%s'", name);
+  return load_entry("mb_inception_load", h->cn, name, name, data, shape, ndim, (hipStream_t)stream);
 }
 
 int mb_inception_forward(mb_inception* h, const uint8_t* u8, int B, int H, int W, float* pool, float* logits_unbiased, float* logits, mb_stream stream) {
@@ -660,7 +611,7 @@ int mb_inception_forward_spatial(mb_inception* h, const uint8_t* u8, int B, int 
 // synchronises the stream
 int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, mb_stream stream) {
   if (!h || !count) return fail(-1, "mb_inception_saturation_count: null argument");
-  return read_counter("mb_inception_saturation_count", h->sat, count, reset, (hipStream_t)stream);
+  return read_counter("mb_inception_saturation_count", h->cn.sat, count, reset, (hipStream_t)stream);
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----

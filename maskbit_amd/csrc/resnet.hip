@@ -26,6 +26,7 @@
 #include "../../include/maskbit_hip.h"
 #include "../../include/maskbit_hip_diag.h"
 #include "mb_abi.h"
+#include "mb_convnet.h"
 #include "mb_incep.h"
 #include "mb_resnet.h"
 
@@ -191,31 +192,20 @@ namespace {
 
 constexpr int RN_LAYERS = 4;
 constexpr int RN_BLOCKS[RN_LAYERS] = {3, 4, 6, 3};
-constexpr int RN_BN_PARTS = 4;
-const char* const RN_BN_NAMES[RN_BN_PARTS] = {".weight", ".bias", ".running_mean", ".running_var"};
+const char* const RN_PREFIX = "model.";                           // the reference module holds torchvision's network under this name
 enum { RN_A, RN_B, RN_T1, RN_T2, RN_D, RN_COLS, RN_IMG, RN_NBUF };     // A / B: a block's input and output in turn; T1 / T2: its two inner maps; D: downsample
 
-struct RnConv {
-  std::string name, bn;                                          // checkpoint names of the convolution and of its BatchNorm
-  int cin = 0, cout = 0, k = 1, stride = 1, pad = 0;             // as the kernel runs it (conv1: 147 -> 64, 1x1)
-  int64_t shape[4] = {0, 0, 0, 0};                               // of the checkpoint's weight
-  h16* w = nullptr;
-  float *bnv = nullptr, *scale = nullptr, *shift = nullptr;      // bnv [4][cout]: gamma, beta, running mean, running variance
-};
-
 struct RnNet {
-  std::vector<RnConv> convs;                                     // conv1, then per block conv1, conv2, conv3 (, downsample.0)
   size_t need[RN_NBUF] = {0, 0, 0, 0, 0, 0, 0};                  // fp16 elements per image at 224 x 224
 
-  void add(const std::string& name, const std::string& bn, int cin, int cout, int k, int stride) {
-    RnConv c;
-    c.name = name; c.bn = bn; c.cin = cin; c.cout = cout; c.k = k; c.stride = stride; c.pad = k / 2;
-    c.shape[0] = cout; c.shape[1] = cin; c.shape[2] = c.shape[3] = k;
-    convs.push_back(c);
-  }
-  void build() {
-    add("conv1", "bn1", RN_STEM_K, 64, 1, 1);
-    convs[0].pad = 0; convs[0].shape[1] = 3; convs[0].shape[2] = convs[0].shape[3] = 7;
+  // cn.convs: conv1, then per block conv1, conv2, conv3 (, downsample.0)
+  void build(ConvNet& cn) {
+    // the checkpoint's naming, in the reference's layout: model.<conv>.weight with model.<bn>.*
+    auto add = [&cn](const std::string& conv, const std::string& bn, int cin, int cout, int k, int stride) {
+      return add_conv(cn, RN_PREFIX + conv + ".weight", RN_PREFIX + bn, cin, cout, k, k, stride, k / 2, k / 2);
+    };
+    CnConv& stem = cn.convs[add("conv1", "bn1", RN_STEM_K, 64, 1, 1)];
+    stem.shape[1] = 3; stem.shape[2] = stem.shape[3] = 7;
     int cin = 64;
     for (int L = 0; L < RN_LAYERS; ++L) {
       const int width = 64 << L;
@@ -243,13 +233,11 @@ struct RnNet {
 
 struct mb_resnet {
   int max_pairs = 0;
+  mb::ConvNet cn;                  // the convolutions, the head, the checkpoint table, the arena (mb_convnet.h)
   mb::RnNet net;
   h16* buf[mb::RN_NBUF] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float *fc_w = nullptr, *fc_b = nullptr, *pool = nullptr, *logits = nullptr, *mean_std = nullptr, *rw = nullptr;
+  float *pool = nullptr, *logits = nullptr, *mean_std = nullptr, *rw = nullptr;
   int* rspan = nullptr;
-  unsigned* sat = nullptr;
-  std::vector<uint8_t> loaded;     // per convolution 5 entries (weight, the four BatchNorm vectors), then fc.weight, fc.bias, mean, std
-  mb::DevArena mem;
 };
 
 using namespace mb;
@@ -263,8 +251,8 @@ const h16* run_trunk(mb_resnet* h, const h16* img, int N, int S, const RnOut& o,
   int hw = rn_stem_size(S);
   { ProfScope p("resnet_stem", s);
     launch_stem_cols(s, img, h->buf[RN_COLS], N, S);
-    const RnConv& c = h->net.convs[0];
-    launch_convbn(s, ConvBn{h->buf[RN_COLS], c.w, c.scale, c.shift, h->buf[RN_A], h->sat, N, hw, hw, c.cin, c.cout, 1, 1, 1, 0, 0, 0, RN_STEM_C, 0, c.cout}); }
+    const CnConv& c = h->cn.convs[0];
+    launch_convbn(s, ConvBn{h->buf[RN_COLS], c.w, c.scale, c.shift, h->buf[RN_A], h->cn.sat, N, hw, hw, c.cin, c.cout, 1, 1, 1, 0, 0, 0, RN_STEM_C, 0, c.cout}); }
   { ProfScope p("resnet_pool", s);
     launch_pool3(s, Pool3{h->buf[RN_A], h->buf[RN_B], N, hw, hw, 64, 3, 0, 64, 0, 64}); }
   hw = rn_stem_size(hw);
@@ -275,18 +263,18 @@ const h16* run_trunk(mb_resnet* h, const h16* img, int N, int S, const RnOut& o,
     const std::string scope = "resnet_conv.layer" + std::to_string(L + 1);
     for (int b = 0; b < RN_BLOCKS[L]; ++b) {
       ProfScope p(scope.c_str(), s);
-      const RnConv &c1 = h->net.convs[ci], &c2 = h->net.convs[ci + 1], &c3 = h->net.convs[ci + 2];
+      const CnConv &c1 = h->cn.convs[ci], &c2 = h->cn.convs[ci + 1], &c3 = h->cn.convs[ci + 2];
       const int yi = xi == RN_A ? RN_B : RN_A, ho = ic_out_size(hw, 3, c2.stride, 1);
       const h16* x = h->buf[xi];
-      launch_convbn(s, ConvBn{x, c1.w, c1.scale, c1.shift, h->buf[RN_T1], h->sat, N, hw, hw, cin, width, 1, 1, 1, 0, 0, 0, cin, 0, width});
-      launch_convbn(s, ConvBn{h->buf[RN_T1], c2.w, c2.scale, c2.shift, h->buf[RN_T2], h->sat, N, hw, hw, width, width, 3, 3, c2.stride, 1, 1, 0, width, 0, width});
+      launch_convbn(s, ConvBn{x, c1.w, c1.scale, c1.shift, h->buf[RN_T1], h->cn.sat, N, hw, hw, cin, width, 1, 1, 1, 0, 0, 0, cin, 0, width});
+      launch_convbn(s, ConvBn{h->buf[RN_T1], c2.w, c2.scale, c2.shift, h->buf[RN_T2], h->cn.sat, N, hw, hw, width, width, 3, 3, c2.stride, 1, 1, 0, width, 0, width});
       const h16* idn = x;
       if (b == 0) {
-        const RnConv& d = h->net.convs[ci + 3];
-        launch_convbn(s, ConvBn{x, d.w, d.scale, d.shift, h->buf[RN_D], h->sat, N, hw, hw, cin, cout, 1, 1, d.stride, 0, 0, 0, cin, 0, cout, CONVBN_LINEAR});
+        const CnConv& d = h->cn.convs[ci + 3];
+        launch_convbn(s, ConvBn{x, d.w, d.scale, d.shift, h->buf[RN_D], h->cn.sat, N, hw, hw, cin, cout, 1, 1, d.stride, 0, 0, 0, cin, 0, cout, CONVBN_LINEAR});
         idn = h->buf[RN_D];
       }
-      launch_convbn(s, ConvBn{h->buf[RN_T2], c3.w, c3.scale, c3.shift, h->buf[yi], h->sat, N, ho, ho, width, cout, 1, 1, 1, 0, 0, 0, width, 0, cout,
+      launch_convbn(s, ConvBn{h->buf[RN_T2], c3.w, c3.scale, c3.shift, h->buf[yi], h->cn.sat, N, ho, ho, width, cout, 1, 1, 1, 0, 0, 0, width, 0, cout,
                               CONVBN_RESIDUAL, idn, 0, cout});
       ci += b == 0 ? 4 : 3;
       xi = yi; hw = ho; cin = cout;
@@ -295,17 +283,11 @@ const h16* run_trunk(mb_resnet* h, const h16* img, int N, int S, const RnOut& o,
   }
   { ProfScope p("resnet_head", s);
     launch_spatial_mean(s, h->buf[xi], h->pool, N, hw * hw, RN_FEAT);
-    launch_fc_head(s, h->pool, h->fc_w, h->fc_b, nullptr, h->logits, N, RN_FEAT, RN_NCLASS); }
+    launch_fc_head(s, h->pool, h->cn.fc_w, h->cn.fc_b, nullptr, h->logits, N, RN_FEAT, RN_NCLASS); }
   if (o.pool) (void)hipMemcpyAsync(o.pool, h->pool, (size_t)N * RN_FEAT * sizeof(float), hipMemcpyDeviceToDevice, s);
   if (o.logits) (void)hipMemcpyAsync(o.logits, h->logits, (size_t)N * RN_NCLASS * sizeof(float), hipMemcpyDeviceToDevice, s);
   *HWout = hw * hw;
   return h->buf[xi];
-}
-
-int check_complete(const char* what, mb_resnet* h) {
-  if (std::find(h->loaded.begin(), h->loaded.end(), (uint8_t)0) != h->loaded.end())
-    return fail(-1, "%s: the checkpoint is not complete (%zu entries: conv / bn of every layer, fc.*, mean, std)", what, h->loaded.size());
-  return 0;
 }
 
 }  // namespace
@@ -316,20 +298,17 @@ int mb_resnet_create(int max_pairs, mb_resnet** out) {
   if (!out || max_pairs < 1 || max_pairs > 2048) return fail(-1, "mb_resnet_create: bad arguments");
   mb_resnet* h = new mb_resnet();
   h->max_pairs = max_pairs;
-  h->net.build();
-  DevArena& m = h->mem;
+  h->cn.bn_eps = RN_BN_EPS;
+  h->net.build(h->cn);
+  add_head(h->cn, RN_PREFIX, RN_FEAT, RN_NCLASS);
+  DevArena& m = h->cn.mem;
   const size_t N = (size_t)2 * max_pairs;
-  m.zeroed(&h->sat, 1);
-  for (RnConv& c : h->net.convs) {
-    m.get(&c.w, (size_t)c.k * c.k * ic_cout_pad(c.cout) * ic_cin_pad(c.cin));
-    m.zeroed(&c.bnv, (size_t)RN_BN_PARTS * c.cout); m.zeroed(&c.scale, (size_t)c.cout); m.zeroed(&c.shift, (size_t)c.cout);
-  }
-  m.get(&h->fc_w, (size_t)RN_NCLASS * RN_FEAT); m.get(&h->fc_b, (size_t)RN_NCLASS);
   m.get(&h->pool, N * RN_FEAT); m.get(&h->logits, N * RN_NCLASS);
   m.get(&h->mean_std, 6); m.get(&h->rw, (size_t)2 * RN_SIDE * RN_MAXT); m.get(&h->rspan, (size_t)4 * RN_SIDE);
+  add_vec(h->cn, "mean", h->mean_std, 3);                        // the module's own buffers: outside `model.`
+  add_vec(h->cn, "std", h->mean_std + 3, 3);
   for (int i = 0; i < RN_NBUF; ++i) m.get(&h->buf[i], N * h->net.need[i]);
   if (int rc = m.failed("mb_resnet_create")) { delete h; return rc; }
-  h->loaded.assign(h->net.convs.size() * 5 + 4, 0);
   *out = h;
   return 0;
 }
@@ -338,55 +317,17 @@ void mb_resnet_destroy(mb_resnet* h) { delete h; }
 
 int mb_resnet_load(mb_resnet* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream) {
   if (!h || !name || !data || !shape || ndim < 0) return fail(-1, "mb_resnet_load: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  std::string n(name);
-  size_t numel = 1;
-  for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
-  const size_t nconv = h->net.convs.size();
-  if (n == "mean" || n == "std") {
-    const int which = n == "std";
-    if (numel != 3) return fail(-4, "mb_resnet_load: %s: expected 3 values", name);
-    HIP_TRY(hipMemcpyAsync(h->mean_std + 3 * which, data, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    h->loaded[nconv * 5 + 2 + which] = 1;
-    return 0;
-  }
-  if (n.compare(0, 6, "model.") == 0) n = n.substr(6);           // the reference's layout; torchvision's has no prefix
-  if (n == "fc.weight" || n == "fc.bias") {
-    const bool isw = n == "fc.weight";
-    if (numel != (isw ? (size_t)RN_NCLASS * RN_FEAT : (size_t)RN_NCLASS)) return fail(-4, "mb_resnet_load: %s: wrong size", name);
-    HIP_TRY(hipMemcpyAsync(isw ? h->fc_w : h->fc_b, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    h->loaded[nconv * 5 + (isw ? 0 : 1)] = 1;
-    return 0;
-  }
-  for (size_t l = 0; l < nconv; ++l) {
-    const RnConv& c = h->net.convs[l];
-    if (n == c.name + ".weight") {
-      if (ndim != 4 || shape[0] != c.shape[0] || shape[1] != c.shape[1] || shape[2] != c.shape[2] || shape[3] != c.shape[3])
-        return fail(-4, "mb_resnet_load: %s: expected [%d, %d, %d, %d]", name, (int)c.shape[0], (int)c.shape[1], (int)c.shape[2], (int)c.shape[3]);
-      // conv1 [64, 3, 7, 7] is read as [64, 147, 1, 1]: the same memory, input channel ci * 49 + ky * 7 + kx
-      launch_repack_convbn(s, data, c.w, c.cout, c.cin, c.k, c.k);
-      h->loaded[l * 5] = 1;
-      return launched();
-    }
-    if (n.compare(0, c.bn.size(), c.bn) != 0 || n.size() <= c.bn.size() || n[c.bn.size()] != '.') continue;
-    const std::string rest = n.substr(c.bn.size());
-    if (rest == ".num_batches_tracked") return 0;
-    for (int k = 0; k < RN_BN_PARTS; ++k) {
-      if (rest != RN_BN_NAMES[k]) continue;
-      if (numel != (size_t)c.cout) return fail(-4, "mb_resnet_load: %s: expected %d values", name, c.cout);
-      HIP_TRY(hipMemcpyAsync(c.bnv + (size_t)k * c.cout, data, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-      launch_bn_fold(s, c.bnv, c.scale, c.shift, c.cout, RN_BN_EPS);
-      h->loaded[l * 5 + 1 + k] = 1;
-      return launched();
-    }
-  }
-  return fail(-2, "mb_resnet_load: unknown checkpoint entry '%s'", name);
+  // the table is in the reference's layout (mean, std, model.<torchvision's key>); torchvision's own has no prefix.  Accepted are the names
+  // that stripping one leading `model.` -- after mean / std have been tried -- turns into a torchvision key: `model.mean` is none
+  std::string key(name);
+  if (!h->cn.table.count(key)) key = RN_PREFIX + key;
+  return load_entry("mb_resnet_load", h->cn, name, key, data, shape, ndim, (hipStream_t)stream);
 }
 
 int mb_resnet_forward(mb_resnet* h, const float* real, const float* fake, int B, int H, int W, int clamp01, int on_logits, double* per_pair, double* sum,
                       mb_stream stream) {
   if (!h || !real || !fake || !per_pair) return fail(-1, "mb_resnet_forward: null argument");
-  if (int rc = check_complete("mb_resnet_forward", h)) return rc;
+  if (int rc = complete("mb_resnet_forward", h->cn)) return rc;
   if (B < 1 || B > h->max_pairs) return fail(-1, "mb_resnet_forward: batch %d outside [1, %d] pairs", B, h->max_pairs);
   if (H < RN_MIN_HW || W < RN_MIN_HW || H > RN_MAX_HW || W > RN_MAX_HW)
     return fail(-1, "mb_resnet_forward: images of %d x %d: H and W must be in [%d, %d]", H, W, RN_MIN_HW, RN_MAX_HW);
@@ -405,7 +346,7 @@ int mb_resnet_forward(mb_resnet* h, const float* real, const float* fake, int B,
 // synchronises the stream
 int mb_resnet_saturation_count(mb_resnet* h, unsigned* count, int reset, mb_stream stream) {
   if (!h || !count) return fail(-1, "mb_resnet_saturation_count: null argument");
-  return read_counter("mb_resnet_saturation_count", h->sat, count, reset, (hipStream_t)stream);
+  return read_counter("mb_resnet_saturation_count", h->cn.sat, count, reset, (hipStream_t)stream);
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----
@@ -444,7 +385,7 @@ int mb_resnet_distance(const float* logits, const void* feat_h16, int B, int N, 
 int mb_resnet_taps(mb_resnet* h, const void* image_h16, int B, int S, void* layer1, void* layer2, void* layer3, void* layer4, float* pool, float* logits,
                    mb_stream stream) {
   if (!h || !image_h16) return fail(-1, "mb_resnet_taps: null argument");
-  if (int rc = check_complete("mb_resnet_taps", h)) return rc;
+  if (int rc = complete("mb_resnet_taps", h->cn)) return rc;
   if (B < 1 || B > 2 * h->max_pairs) return fail(-1, "mb_resnet_taps: batch %d outside [1, %d] images", B, 2 * h->max_pairs);
   if (S < RN_MIN_HW || S > RN_SIDE || S % 8) return fail(-1, "mb_resnet_taps: side %d: a multiple of 8 in [%d, %d]", S, RN_MIN_HW, RN_SIDE);
   int HW = 0;

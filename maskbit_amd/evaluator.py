@@ -17,6 +17,7 @@ forms -- runs here (``generator_evaluator.py``, which also holds ``GeneratorEval
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Mapping, Optional, Text
 
 import torch
@@ -72,12 +73,8 @@ class TokenizerEvaluator:
         self._hist: Optional[torch.Tensor] = None
         self._out_of_range: Optional[torch.Tensor] = None
         self.last_per_image: Optional[torch.Tensor] = None
-        self.last_lpips: Optional[torch.Tensor] = None
-        self._lpips = None
-        self._lpips_sum: Optional[torch.Tensor] = None
-        self.last_perceptual: Optional[torch.Tensor] = None
-        self._perceptual = None
-        self._perceptual_sum: Optional[torch.Tensor] = None
+        # the attached pair losses in the order of result(): the result key, the model (None: detached), the float64 device sum, the last batch's [B] values
+        self._pair_losses = [SimpleNamespace(key=key, model=None, sum=None, last=None) for key in ("LPIPS", "PerceptualLoss")]
         self._inception = None                                                                # use_inception(): the extractor and its three states
         self._rfid = self._inception_score = False
         self._is_stats = self._rfid_real = self._rfid_fake = None
@@ -99,12 +96,10 @@ class TokenizerEvaluator:
             self._hist.zero_()
             self._out_of_range.zero_()
         self.last_per_image = None
-        self.last_lpips = None
-        if self._lpips_sum is not None:
-            self._lpips_sum.zero_()
-        self.last_perceptual = None
-        if self._perceptual_sum is not None:
-            self._perceptual_sum.zero_()
+        for row in self._pair_losses:
+            row.last = None
+            if row.sum is not None:
+                row.sum.zero_()
         for stats in (self._is_stats, self._rfid_real, self._rfid_fake):
             if stats is not None:
                 stats.reset()
@@ -133,18 +128,8 @@ class TokenizerEvaluator:
         values to a float64 device sum (``last_lpips`` holds the batch's [B] values) and ``result()`` reports ``"LPIPS"``.  Takes the place of
         the reference's ``enable_lpips_score`` (evaluator.py:223-226,366-368,453-455), whose weights cannot be fetched here.  Attach before the
         first ``update()`` of a pass, or call ``reset_metrics()``: the mean is over all examples counted."""
-        if model is None:
-            self._lpips = None
-            return
         from .lpips import LPIPS
-        if not isinstance(model, LPIPS):
-            raise TypeError(f"use_lpips() takes a maskbit_amd.LPIPS, got {type(model).__name__}")
-        dev = model._require_cuda("use_lpips")
-        if (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device.index:
-            raise ValueError(f"the LPIPS model is on {dev}, the evaluator on {self._device}")
-        self._lpips = model
-        if self._lpips_sum is None:
-            self._lpips_sum = torch.zeros(1, dtype=torch.float64, device=self._device)
+        self._use_pair_loss(self._pair_losses[0], model, LPIPS, "use_lpips")
 
     def use_perceptual(self, model) -> None:
         """Attaches a loaded ``maskbit_amd.PerceptualLoss`` on the evaluator's device (``None`` detaches): ``update()`` then also adds the batch's
@@ -152,18 +137,25 @@ class TokenizerEvaluator:
         ``"PerceptualLoss"``, their mean -- what the reference's ``PerceptualLoss.forward`` gives over the same pairs.  The reference's evaluator
         has no such entry; the key is there only while a model is attached.  Attach before the first ``update()`` of a pass, or call
         ``reset_metrics()``."""
-        if model is None:
-            self._perceptual = None
-            return
         from .perceptual import PerceptualLoss
-        if not isinstance(model, PerceptualLoss):
-            raise TypeError(f"use_perceptual() takes a maskbit_amd.PerceptualLoss, got {type(model).__name__}")
-        dev = model._require_cuda("use_perceptual")
+        self._use_pair_loss(self._pair_losses[1], model, PerceptualLoss, "use_perceptual")
+
+    def _use_pair_loss(self, row, model, cls, who: str) -> None:
+        if model is None:
+            row.model = None
+            return
+        if not isinstance(model, cls):
+            raise TypeError(f"{who}() takes a maskbit_amd.{cls.__name__}, got {type(model).__name__}")
+        dev = model._require_cuda(who)
         if (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device.index:
-            raise ValueError(f"the PerceptualLoss model is on {dev}, the evaluator on {self._device}")
-        self._perceptual = model
-        if self._perceptual_sum is None:
-            self._perceptual_sum = torch.zeros(1, dtype=torch.float64, device=self._device)
+            raise ValueError(f"the {cls.__name__} model is on {dev}, the evaluator on {self._device}")
+        row.model = model
+        if row.sum is None:
+            row.sum = torch.zeros(1, dtype=torch.float64, device=self._device)
+
+    last_lpips = property(lambda self: self._pair_losses[0].last)
+    last_perceptual = property(lambda self: self._pair_losses[1].last)
+    _lpips_sum = property(lambda self: self._pair_losses[0].sum)                                # (read by tests/test_hip_lpips.py)
 
     def update(self, real_images: torch.Tensor, fake_images: torch.Tensor, codebook_indices: Optional[torch.Tensor] = None, clamp: bool = False):
         """Adds a batch.  ``real_images`` / ``fake_images``: [B, C, H, W] of any float dtype (cast to contiguous fp32 only when needed), equal
@@ -186,10 +178,9 @@ class TokenizerEvaluator:
             raise ValueError("codebook_indices is required when a codebook metric is enabled")
         if self._codebook and (codebook_indices.is_floating_point() or codebook_indices.is_complex()):
             raise ValueError(f"codebook_indices must be an integer tensor, got {codebook_indices.dtype}")
-        if self._lpips is not None:
-            self._lpips.check_images(tuple(fake_images.shape), tuple(fake_images.shape))      # sizes the engine does not take: ValueError, no device work
-        if self._perceptual is not None:
-            self._perceptual.check_images(tuple(fake_images.shape), tuple(fake_images.shape))
+        attached = [row for row in self._pair_losses if row.model is not None]
+        for row in attached:
+            row.model.check_images(tuple(fake_images.shape), tuple(fake_images.shape))         # sizes the engine does not take: ValueError, no device work
         lib = _lib.load()
         need = int(lib.mb_eval_workspace_bytes(B, C, H, W)) if self._metrics else 0
         if self._metrics and need == 0:
@@ -220,10 +211,8 @@ class TokenizerEvaluator:
                         raise ValueError(f"features of the real images {tuple(pool_real.shape)} and of the fake ones {tuple(pool_fake.shape)} differ")
                     self._rfid_real.add(pool_real)
                     self._rfid_fake.add(pool_fake)
-            if self._lpips is not None:                                                         # evaluator.py:366-368
-                self.last_lpips = self._lpips._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._lpips_sum)
-            if self._perceptual is not None:
-                self.last_perceptual = self._perceptual._run(real_images.reshape(fake_images.shape), fake_images, clamp, self._perceptual_sum)
+            for row in attached:                                                                # evaluator.py:366-368
+                row.last = row.model._run(real_images.reshape(fake_images.shape), fake_images, clamp, row.sum)
             if self._codebook:
                 idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
                 _lib.check(lib.mb_eval_codebook(idx.data_ptr(), idx.numel(), self._num_codebook_entries, self._hist.data_ptr(),
@@ -236,14 +225,9 @@ class TokenizerEvaluator:
         if self._num_examples < 1:
             raise ValueError("No examples to evaluate.")
         entropy = None
-        parts = [self._sums]
-        lp = self._lpips is not None
-        if lp:
-            parts.append(self._lpips_sum)
-        pl = self._perceptual is not None
-        if pl:
-            parts.append(self._perceptual_sum)
-        cb = 4 + int(lp) + int(pl)                                                               # position of the codebook figures
+        attached = [row for row in self._pair_losses if row.model is not None]
+        parts = [self._sums] + [row.sum for row in attached]
+        cb = 4 + len(attached)                                                                  # position of the codebook figures
         if self._codebook:
             counts = self._hist.double()
             probs = counts / counts.sum()
@@ -278,10 +262,8 @@ class TokenizerEvaluator:
             D = self._rfid_real.width
             (t_real, s_real), (t_fake, s_fake) = ((host[o:o + D], host[o + D:o + D + D * D].reshape(D, D)) for o in (at, at + D + D * D))
             eval_score["rFID"] = frechet_distance(t_real / n, get_covariance(s_real, t_real, n), t_fake / n, get_covariance(s_fake, t_fake, n))
-        if lp:
-            eval_score["LPIPS"] = host[4].item() / n                                            # evaluator.py:453-455
-        if pl:
-            eval_score["PerceptualLoss"] = host[cb - 1].item() / n
+        for i, row in enumerate(attached):
+            eval_score[row.key] = host[4 + i].item() / n                                        # evaluator.py:453-455
         if self._enable_codebook_usage_measure:
             eval_score["CodebookUsage"] = float(int(host[cb])) / self._num_codebook_entries
         if self._enable_codebook_entropy_measure:

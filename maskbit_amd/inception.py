@@ -21,12 +21,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Mapping, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from . import _lib
-from .base_model import BaseModel
+from .base_model import BaseModel, StateLike, read_state
 from .synth import INCEPTION_FC, inception_convs
 
 WEIGHTS_FILE = "pt_inception-2015-12-05-6726825d.pth"
@@ -36,7 +36,6 @@ SPATIAL_WIDTH = 17 * 17 * 7              # the sFID tap: Mixed_6d.branch1x1[...,
 FEATURE_WIDTH = {"64": 64, "192": 192, "768": 768, "2048": 2048, "logits_unbiased": INCEPTION_FC[0], "logits": INCEPTION_FC[0],
                  "spatial": SPATIAL_WIDTH}
 DEFAULT_FEATURES = ("2048", "logits_unbiased")
-StateLike = Union[str, os.PathLike, Mapping[str, torch.Tensor]]
 _BN = ("weight", "bias", "running_mean", "running_var")
 
 
@@ -61,11 +60,7 @@ class InceptionV3(BaseModel):
         if bad or not self.features_list:
             raise ValueError(f"InceptionV3: unknown features {bad}; supported: {list(FEATURE_KEYS)}")
         for name, cin, cout, (kh, kw), _stride, _pad in inception_convs():
-            self._attach(f"{name}.conv.weight", torch.zeros(cout, cin, kh, kw))
-            self._attach(f"{name}.bn.weight", torch.zeros(cout))
-            self._attach(f"{name}.bn.bias", torch.zeros(cout))
-            self._attach(f"{name}.bn.running_mean", torch.zeros(cout), buffer=True)
-            self._attach(f"{name}.bn.running_var", torch.zeros(cout), buffer=True)
+            self._attach_convbn(name + ".conv", name + ".bn", (cout, cin, kh, kw), counter=False)
         self._attach("fc.weight", torch.zeros(*INCEPTION_FC))
         self._attach("fc.bias", torch.zeros(INCEPTION_FC[0]))
         for p in self.parameters():
@@ -83,10 +78,7 @@ class InceptionV3(BaseModel):
     def load_weights(self, path_or_state_dict: StateLike) -> None:
         """The checkpoint from a path or a state dict with the keys of ``pt_inception-2015-12-05-6726825d.pth``.  All 472 entries must be there;
         ``num_batches_tracked`` and entries the network does not read (the auxiliary classifier's) are ignored."""
-        src = path_or_state_dict
-        if isinstance(src, (str, os.PathLike)):
-            src = torch.load(os.fspath(src), map_location="cpu")
-        src = dict(src)
+        src = read_state(path_or_state_dict)
         missing = [k for k in inception_keys() if k not in src]
         if missing:
             raise KeyError(f"load_weights: {len(missing)} entries missing, e.g. {missing[:3]}")

@@ -19,18 +19,16 @@ H % 128 == 0 and W % 256 == 0 (256^2, 512^2, ...).  There is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Dict, List, Mapping, Optional, Union
+from typing import List, Optional
 
 import torch
 
 from . import _lib
-from .base_model import BaseModel
+from .base_model import PairLoss, StateLike, read_state
 from .synth import VGG16_CONVS
 
 _SLICE_END = (4, 9, 16, 23, 30)            # lpips.py:94-103: features [0, 4) -> slice1, [4, 9) -> slice2, ...
 _TAP_CHANNELS = (64, 128, 256, 512, 512)
-StateLike = Union[str, os.PathLike, Mapping[str, torch.Tensor]]
 
 
 def _slice_of(idx: int) -> int:
@@ -42,14 +40,9 @@ def vgg16_keys() -> List[str]:
     return [f"net.slice{_slice_of(i)}.{i}.{p}" for i, _cin, _cout in VGG16_CONVS for p in ("weight", "bias")]
 
 
-def _read(src: StateLike) -> Dict[str, torch.Tensor]:
-    if isinstance(src, (str, os.PathLike)):
-        src = torch.load(os.fspath(src), map_location="cpu")
-    return dict(src)
-
-
-class LPIPS(BaseModel):
+class LPIPS(PairLoss):
     _ABI = "lpips"
+    _INPUT = "VGG16"
     _COUNTS = "4-channel activation groups the convolutions clamped (ImageNet VGG16 activations are unnormalised)"
     max_pairs_per_call = 16               # workspace bound at 256 x 256 (two fp16 buffers of 8 MiB per image); scaled down with the image area
 
@@ -87,7 +80,7 @@ class LPIPS(BaseModel):
     def load_vgg16(self, path_or_state_dict: StateLike) -> None:
         """The thirteen convolutions from a checkpoint path or state dict in the reference layout (``net.sliceK.N.*``), torchvision's
         (``features.N.*``; its ``classifier.*`` entries are ignored) or a bare ``N.*``.  All 26 entries must be there."""
-        src = _read(path_or_state_dict)
+        src = read_state(path_or_state_dict)
         sd = {}
         for idx, _cin, _cout in VGG16_CONVS:
             for p in ("weight", "bias"):
@@ -104,7 +97,7 @@ class LPIPS(BaseModel):
     def load_linear(self, path_or_state_dict: StateLike) -> None:
         """The five 1x1 weight vectors (and the scaling buffers, when present) from the reference's ``pretrained/vgg_lpips.pth``; non-strict, as
         the reference loads it (lpips.py:37).  Either lin index (``model.1`` / ``model.0``) is accepted."""
-        src = _read(path_or_state_dict)
+        src = read_state(path_or_state_dict)
         sd = {k: v for k, v in src.items() if k.startswith("scaling_layer.")}
         for k in range(5):
             for j in (1, 0):
@@ -127,50 +120,23 @@ class LPIPS(BaseModel):
         if H * W > self._cap_hw[0] * self._cap_hw[1]:
             self._drop_engine()
             self._cap_hw = (H, W)
-        have = self._engine_key[1] if self._engine_key else 0
-        return self._ensure_engine(max(pairs, have))
+        return super().engine(pairs)
 
     # ---- forward ----------------------------------------------------------------------------------
     @staticmethod
-    def check_images(shape_a, shape_b) -> None:
-        """``ValueError`` for what the engine does not take; no device work."""
-        if len(shape_a) != 4 or tuple(shape_a) != tuple(shape_b):
-            raise ValueError(f"LPIPS expects two [B, 3, H, W] batches of one shape, got {tuple(shape_a)} and {tuple(shape_b)}")
-        B, Cc, H, W = (int(v) for v in shape_a)
-        if B < 1:
-            raise ValueError(f"LPIPS: empty batch {tuple(shape_a)}")
-        if Cc != 3:
-            raise ValueError(f"LPIPS takes 3 channels (the VGG16 input), got {Cc}")
+    def _size_error(H: int, W: int) -> Optional[str]:
         if H < 128 or W < 256 or H % 128 or W % 256:
-            raise ValueError(f"LPIPS: images of {H} x {W}: the HIP engine takes H % 128 == 0 and W % 256 == 0 (whole 8 x 16-pixel convolution "
-                             "tiles at 1/16 resolution), e.g. 256 x 256 or 512 x 512")
+            return "H % 128 == 0 and W % 256 == 0 (whole 8 x 16-pixel convolution tiles at 1/16 resolution), e.g. 256 x 256 or 512 x 512"
+        return None
 
-    def _run(self, a: torch.Tensor, b: torch.Tensor, clamp: bool, running_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
-        dev = self._require_cuda("forward")
-        self.check_images(a.shape, b.shape)
-        if not (self._vgg_loaded and self._lin_loaded):
-            missing = [n for n, ok in (("load_vgg16", self._vgg_loaded), ("load_linear", self._lin_loaded)) if not ok]
-            raise RuntimeError(f"LPIPS has no weights yet: call {' and '.join(missing)} first (nothing is loaded at construction)")
-        B, _, H, W = (int(v) for v in a.shape)
-        a = a.to(device=dev, dtype=torch.float32).contiguous()
-        b = b.to(device=dev, dtype=torch.float32).contiguous()
-        chunk = max(1, min(B, int(self.max_pairs_per_call) * 65536 // (H * W)))
-        h = self.engine(chunk, H, W)
-        out = torch.empty(B, dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            for b0 in range(0, B, chunk):
-                n = min(chunk, B - b0)
-                _lib.check(lib.mb_lpips_forward(h, a[b0:b0 + n].data_ptr(), b[b0:b0 + n].data_ptr(), n, H, W, 1 if clamp else 0, out[b0:b0 + n].data_ptr(),
-                                                running_sum.data_ptr() if running_sum is not None else None, stream), "mb_lpips_forward")
-        return out
+    def _no_weights(self) -> Optional[str]:
+        return " and ".join(n for n, ok in (("load_vgg16", self._vgg_loaded), ("load_linear", self._lin_loaded)) if not ok) or None
 
-    @torch.no_grad()
-    def per_image(self, input: torch.Tensor, target: torch.Tensor, clamp: bool = False) -> torch.Tensor:
-        """LPIPS of every pair as float64 [B] on the device (``clamp=True``: both images clamped to [0, 1] inside the input kernel).  Batches
-        beyond ``max_pairs_per_call`` are walked in chunks; a pair's value does not depend on the chunking.  No synchronisation."""
-        return self._run(input, target, clamp)
+    def _chunk(self, H: int, W: int) -> int:
+        return int(self.max_pairs_per_call) * 65536 // (H * W)
+
+    def _forward_chunk(self, h, a, b, n, H, W, clamp, out, running_sum, stream) -> int:
+        return _lib.load().mb_lpips_forward(h, a, b, n, H, W, clamp, out, running_sum, stream)
 
     @torch.no_grad()
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

@@ -21,16 +21,14 @@ or with the reference module: tests hold it to a float64 restatement of that spe
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Dict, List, Mapping, Optional, Union
+from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib
-from .base_model import BaseModel
+from .base_model import PairLoss, StateLike, read_state
 from .synth import RESNET50_FC, resnet50_convs
 
-StateLike = Union[str, os.PathLike, Mapping[str, torch.Tensor]]
 _BN = ("weight", "bias", "running_mean", "running_var")
 MIN_SIDE, MAX_SIDE = 32, 1024
 WEIGHTS_FILE = "resnet50-0676ba61.pth"
@@ -52,8 +50,9 @@ def perceptual_keys() -> List[str]:
     return ["mean", "std"] + ["model." + k for k in resnet50_keys()]
 
 
-class PerceptualLoss(BaseModel):
+class PerceptualLoss(PairLoss):
     _ABI = "resnet"
+    _INPUT = "ResNet-50"
     _COUNTS = "4-channel activation groups the convolutions clamped"
     max_pairs_per_call = 16               # workspace bound: 10.7 MiB of fp16 activations per image, two images per pair
 
@@ -69,12 +68,7 @@ class PerceptualLoss(BaseModel):
         self._attach("mean", torch.tensor([0.485, 0.456, 0.406])[None, :, None, None], buffer=True)        # perceptual_loss.py:33-34
         self._attach("std", torch.tensor([0.229, 0.224, 0.225])[None, :, None, None], buffer=True)
         for conv, bn, cin, cout, k, _stride in resnet50_convs():
-            self._attach(f"model.{conv}.weight", torch.zeros(cout, cin, k, k))
-            self._attach(f"model.{bn}.weight", torch.zeros(cout))
-            self._attach(f"model.{bn}.bias", torch.zeros(cout))
-            self._attach(f"model.{bn}.running_mean", torch.zeros(cout), buffer=True)
-            self._attach(f"model.{bn}.running_var", torch.zeros(cout), buffer=True)
-            self._attach(f"model.{bn}.num_batches_tracked", torch.zeros((), dtype=torch.int64), buffer=True)
+            self._attach_convbn("model." + conv, "model." + bn, (cout, cin, k, k), counter=True)
         self._attach("model.fc.weight", torch.zeros(*RESNET50_FC))
         self._attach("model.fc.bias", torch.zeros(RESNET50_FC[0]))
         for p in self.parameters():
@@ -93,10 +87,7 @@ class PerceptualLoss(BaseModel):
         """The network from a checkpoint path or a state dict in torchvision's layout (``conv1.weight``, ...) or the reference's
         (``model.conv1.weight``, ...).  All 267 weight and BatchNorm entries must be there; the ``num_batches_tracked`` counters and the
         ``mean`` / ``std`` buffers are taken when present."""
-        src = path_or_state_dict
-        if isinstance(src, (str, os.PathLike)):
-            src = torch.load(os.fspath(src), map_location="cpu")
-        src = dict(src)
+        src = read_state(path_or_state_dict)
         sd: Dict[str, torch.Tensor] = {}
         missing = []
         for k in resnet50_keys():
@@ -119,51 +110,16 @@ class PerceptualLoss(BaseModel):
         _lib.check(_lib.load().mb_resnet_create(capacity, C.byref(h)), "mb_resnet_create")
         return h
 
-    def engine(self, pairs: int):
-        have = self._engine_key[1] if self._engine_key else 0
-        return self._ensure_engine(max(pairs, have))
-
     # ---- forward ----------------------------------------------------------------------------------
     @staticmethod
-    def check_images(shape_a, shape_b) -> None:
-        """``ValueError`` for what the engine does not take; no device work."""
-        if len(shape_a) != 4 or tuple(shape_a) != tuple(shape_b):
-            raise ValueError(f"PerceptualLoss expects two [B, 3, H, W] batches of one shape, got {tuple(shape_a)} and {tuple(shape_b)}")
-        B, Cc, H, W = (int(v) for v in shape_a)
-        if B < 1:
-            raise ValueError(f"PerceptualLoss: empty batch {tuple(shape_a)}")
-        if Cc != 3:
-            raise ValueError(f"PerceptualLoss takes 3 channels (the ResNet-50 input), got {Cc}")
-        if not (MIN_SIDE <= H <= MAX_SIDE and MIN_SIDE <= W <= MAX_SIDE):
-            raise ValueError(f"PerceptualLoss: images of {H} x {W}: the HIP engine takes {MIN_SIDE} <= H, W <= {MAX_SIDE}")
+    def _size_error(H: int, W: int) -> Optional[str]:
+        return None if MIN_SIDE <= H <= MAX_SIDE and MIN_SIDE <= W <= MAX_SIDE else f"{MIN_SIDE} <= H, W <= {MAX_SIDE}"
 
-    def _run(self, a: torch.Tensor, b: torch.Tensor, clamp: bool, running_sum: Optional[torch.Tensor] = None) -> torch.Tensor:
-        self.check_images(a.shape, b.shape)
-        if not self._loaded:
-            raise RuntimeError(f"PerceptualLoss has no weights yet: call load_resnet50(path to torchvision's {WEIGHTS_FILE}) first "
-                               "(nothing is loaded at construction)")
-        dev = self._require_cuda("forward")
-        B, _, H, W = (int(v) for v in a.shape)
-        a = a.to(device=dev, dtype=torch.float32).contiguous()
-        b = b.to(device=dev, dtype=torch.float32).contiguous()
-        chunk = max(1, min(B, int(self.max_pairs_per_call)))
-        h = self.engine(chunk)
-        out = torch.empty(B, dtype=torch.float64, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            for b0 in range(0, B, chunk):
-                n = min(chunk, B - b0)
-                _lib.check(lib.mb_resnet_forward(h, a[b0:b0 + n].data_ptr(), b[b0:b0 + n].data_ptr(), n, H, W, 1 if clamp else 0,
-                                                 1 if self.compute_perceptual_loss_on_logits else 0, out[b0:b0 + n].data_ptr(),
-                                                 running_sum.data_ptr() if running_sum is not None else None, stream), "mb_resnet_forward")
-        return out
+    def _no_weights(self) -> Optional[str]:
+        return None if self._loaded else f"load_resnet50(path to torchvision's {WEIGHTS_FILE})"
 
-    @torch.no_grad()
-    def per_image(self, input: torch.Tensor, target: torch.Tensor, clamp: bool = False) -> torch.Tensor:
-        """The loss of every pair as float64 [B] on the device (``clamp=True``: both images clamped to [0, 1] inside the input kernel).  Batches
-        beyond ``max_pairs_per_call`` are walked in chunks; a pair's value does not depend on the chunking.  No synchronisation."""
-        return self._run(input, target, clamp)
+    def _forward_chunk(self, h, a, b, n, H, W, clamp, out, running_sum, stream) -> int:
+        return _lib.load().mb_resnet_forward(h, a, b, n, H, W, clamp, 1 if self.compute_perceptual_loss_on_logits else 0, out, running_sum, stream)
 
     @torch.no_grad()
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

@@ -14,6 +14,8 @@ import functools
 import torch
 import torch.nn.functional as F
 
+import convnet_reference
+from convnet_reference import h16r  # noqa: F401  (part of this module's surface)
 from maskbit_amd.synth import make_eval_images, make_inception_weights
 
 SIDE = 299
@@ -47,11 +49,6 @@ CONV_CASES = {
 }
 
 
-def h16r(t):
-    """fp64 -> fp16 (nearest even, saturating at the fp16 range as the engine's stores do) -> fp64"""
-    return t.clamp(-65504.0, 65504.0).to(torch.float16).double()
-
-
 def resize64(u8, out=SIDE, dtype=torch.float64):
     """uint8 [B, C, H, W] -> float64 [B, C, out, out]: i0 = floor(dst * in / out), i1 = min(i0 + 1, in - 1), t = dst * in / out - i0 (from the
     integers), v = a0 + (a1 - a0) * t along x for both rows, then along y"""
@@ -78,30 +75,14 @@ def input64(u8, dtype=torch.float64):
     return (resize64(u8, SIDE, dtype) - 128.0) / 128.0
 
 
-def bn_scale_shift(sd, name, dtype=torch.float64):
-    g, b = sd[name + ".bn.weight"].to(dtype), sd[name + ".bn.bias"].to(dtype)
-    m, v = sd[name + ".bn.running_mean"].to(dtype), sd[name + ".bn.running_var"].to(dtype)
-    scale = g / torch.sqrt(v + BN_EPS)
-    return scale, b - m * scale
-
-
-class Net:
-    """one forward: the layers as methods on the state dict, `model` = with the engine's roundings"""
-
+class Net(convnet_reference.Net):
     def __init__(self, sd, model, dtype=torch.float64):
-        self.sd, self.model, self.dtype = sd, model, dtype
+        super().__init__(sd, model, BN_EPS, dtype)
         self.used = []
 
-    def store(self, t):
-        return h16r(t) if self.model else t
-
     def conv(self, x, name, stride=1, padding=0):
-        w = self.sd[name + ".conv.weight"]
-        w = w.to(torch.float16).to(self.dtype) if self.model else w.to(self.dtype)
-        scale, shift = bn_scale_shift(self.sd, name, self.dtype)
         self.used.append(name)
-        y = F.conv2d(x, w, None, stride, padding) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
-        return self.store(F.relu(y))
+        return self.store(F.relu(self.convbn(x, name + ".conv", name + ".bn", stride, padding)))
 
     def avg(self, x):
         return self.store(F.avg_pool2d(x, 3, 1, 1, count_include_pad=False))

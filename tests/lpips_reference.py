@@ -14,6 +14,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from convnet_reference import h16r
 from maskbit_amd.synth import VGG16_CONVS, make_eval_images, make_vgg16_weights
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lpips.npz")
@@ -37,11 +38,6 @@ for _s, _style in enumerate(("he", "grown")):
         for _k, _sig in enumerate((0.003, 0.05)):
             ENGINE_CASES[f"{_style}_{_H}x{_W}_{'lo' if _k == 0 else 'hi'}"] = ("noise", _sig, _B, _H, _W, 4300 + 100 * _s + 10 * _j + _k, _style)
 CASES = {**RESTATEMENT_CASES, **ENGINE_CASES}
-
-
-def h16r(t):
-    """fp64 -> fp16 (nearest even, saturating at the fp16 range as the engine's stores do) -> fp64"""
-    return t.clamp(-65504.0, 65504.0).to(torch.float16).double()
 
 
 def scaling_buffers():

@@ -15,6 +15,8 @@ import functools
 import torch
 import torch.nn.functional as F
 
+import convnet_reference
+from convnet_reference import h16r
 from maskbit_amd.synth import make_resnet50_weights
 
 SIDE = 224
@@ -43,11 +45,6 @@ CONV_CASES = {
     "residual 512->2048 k1 7x7": (2, 7, 7, 512, 2048, 1, 1, 0, EPI_RESIDUAL),
 }
 STEM_SIDE = 32                            # the stem case: conv1 in its folded form on a 32 x 32 image
-
-
-def h16r(t):
-    """fp64 -> fp16 (nearest even, saturating at the fp16 range as the engine's stores do) -> fp64"""
-    return t.clamp(-65504.0, 65504.0).to(torch.float16).double()
 
 
 # ---- the written-out key list (independent of maskbit_amd.perceptual) ---------------------------------------------------------------------
@@ -120,25 +117,9 @@ def stem_cols64(img):
 
 
 # ---- the network ------------------------------------------------------------------------------------------------------------------------------
-def bn_scale_shift(sd, name):
-    g, b = sd[name + ".weight"].double(), sd[name + ".bias"].double()
-    m, v = sd[name + ".running_mean"].double(), sd[name + ".running_var"].double()
-    scale = g / torch.sqrt(v + BN_EPS)
-    return scale, b - m * scale
-
-
-class Net:
+class Net(convnet_reference.Net):
     def __init__(self, sd, model):
-        self.sd, self.model = sd, model
-
-    def store(self, t):
-        return h16r(t) if self.model else t
-
-    def convbn(self, x, conv, bn, stride=1, padding=0):
-        w = self.sd[conv + ".weight"]
-        w = w.to(torch.float16).double() if self.model else w.double()
-        scale, shift = bn_scale_shift(self.sd, bn)
-        return F.conv2d(x, w, None, stride, padding) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        super().__init__(sd, model, BN_EPS)
 
     def bottleneck(self, x, p, stride, downsample):
         t = self.store(F.relu(self.convbn(x, p + ".conv1", p + ".bn1")))

@@ -22,56 +22,13 @@ import torch
 import torch.nn.functional as F
 
 import inception_reference as R
+from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-U16 = 2.0 ** -11
-U32 = 2.0 ** -24
-
-
-def _lib():
-    from maskbit_amd import _lib
-    return _lib, _lib.load()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 # ------------------------------------------------------------------------------------------------ convolution + BatchNorm + ReLU
-def run_convbn(xbuf, w, scale, shift, stride, pad, in_off=0, out=None, out_off=0, variant=0):
-    """mb_convbn_layer: xbuf fp16 [B, H, W, in_cs] (CPU) of which channels [in_off, in_off + Cin) are read, w fp32 OIHW; `out` (CPU, optional) is
-    the pre-filled output buffer -> (the output buffer on the CPU, saturation count)"""
-    L, lib = _lib()
-    B, H, W, in_cs = xbuf.shape
-    cout, cin, kh, kw = w.shape
-    Ho, Wo = (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
-    if out is None:
-        out = torch.full((B, Ho, Wo, cout), float("nan"), dtype=torch.float16)
-    assert tuple(out.shape[:3]) == (B, Ho, Wo)
-    xd, wd, od = xbuf.to(DEV).contiguous(), w.float().to(DEV).contiguous(), out.to(DEV).contiguous()
-    sc, sh = scale.float().to(DEV).contiguous(), shift.float().to(DEV).contiguous()
-    sat = C.c_uint(0)
-    L.check(lib.mb_convbn_layer(xd.data_ptr(), wd.data_ptr(), sc.data_ptr(), sh.data_ptr(), od.data_ptr(), C.byref(sat), B, H, W, cin, cout, kh, kw, stride,
-                                pad[0], pad[1], in_off, in_cs, out_off, out.shape[3], variant, _stream()), "mb_convbn_layer")
-    torch.cuda.synchronize()
-    return od.cpu(), int(sat.value)
-
-
-def ref_convbn(x16, w, scale, shift, stride, pad):
-    """-> (exact float64 NCHW with fp16 weights, the magnitude sum S of the bound)"""
-    a = x16.double().permute(0, 3, 1, 2)
-    wq = w.to(torch.float16).double()
-    sc, sh = scale.float().double().view(1, -1, 1, 1), shift.float().double().view(1, -1, 1, 1)
-    y = F.relu(F.conv2d(a, wq, None, stride, pad) * sc + sh)
-    S = F.conv2d(a.abs(), wq.abs(), None, stride, pad) * sc.abs() + sh.abs()
-    return y, S
-
-
+# run_convbn, ref_convbn, check_against_fp64 and integer_case live in tests/convnet_helpers.py (imported above), shared with the ResNet tests
 def pad_channels(x16, fill=float("nan")):
     """the 3-channel image as the engine holds it: in 8-channel pixels; the pad channels hold `fill`, which must never be read into a product"""
     B, H, W, cin = x16.shape
@@ -88,32 +45,9 @@ def test_convbn_layer_vs_fp64(name):
     B, H, W, cin, cout, k, stride, pad = R.CONV_CASES[name]
     x16, w, scale, shift = R.conv_case(name, seed=4500 + cin + cout)
     got16, sat = run_convbn(pad_channels(x16), w, scale, shift, stride, pad)
-    got = got16.double().permute(0, 3, 1, 2)
     exact, S = ref_convbn(x16, w, scale, shift, stride, pad)
-    model = R.h16r(exact)
-    assert got.shape == exact.shape and bool(torch.isfinite(got).all()) and bool((got >= 0).all())
-    K = cin * k[0] * k[1]
-    bound = U16 * exact.abs() + K * U32 * S
-    err = (got - exact).abs()
-    worst = (err / bound.clamp(min=1e-300)).max().item()
-    e_kernel, e_model = err.pow(2).mean().sqrt().item(), (model - exact).pow(2).mean().sqrt().item()
-    print(f"convbn {name} B {B}: max err / bound {worst:.3f}; rms err {e_kernel:.3e}, E_model {e_model:.3e}, ratio {e_kernel / e_model:.3f}; "
-          f"zeros {float((exact == 0).double().mean()):.2f}")
-    assert worst <= 1.0
-    assert e_model > 0.0 and e_kernel <= 1.25 * e_model
-    assert bool((got[exact == 0] == 0).all())                  # what ReLU cuts is exactly 0
+    check_against_fp64(f"{name} B {B}", got16, exact, S, cin * k[0] * k[1])        # K 2^-24 S: the K products' accumulation
     assert sat == 0
-
-
-def integer_case(name, seed):
-    """operands whose every partial sum is an integer below 2^24 (exact in fp32), scale a power of two, shift a multiple of 1/2"""
-    B, H, W, cin, cout, (kh, kw), stride, pad = R.CONV_CASES[name]
-    g = torch.Generator().manual_seed(seed)
-    x16 = torch.randint(0, 4, (B, H, W, cin), generator=g).to(torch.float16)
-    w = torch.randint(-2, 3, (cout, cin, kh, kw), generator=g).float()
-    scale = torch.pow(2.0, torch.randint(-3, 1, (cout,), generator=g).float())
-    shift = torch.randint(-8, 9, (cout,), generator=g).float() * 0.5
-    return x16, w, scale, shift
 
 
 @pytest.mark.parametrize("variant", [1, 2])
@@ -121,7 +55,7 @@ def integer_case(name, seed):
 def test_convbn_layer_integer_operands_are_bit_exact(name, variant):
     """every kernel shape, both wave tiles: the tile walk, the tap geometry and the K tail decide every bit here"""
     B, H, W, cin, cout, k, stride, pad = R.CONV_CASES[name]
-    x16, w, scale, shift = integer_case(name, 4600 + cin)
+    x16, w, scale, shift, _ = integer_case(4600 + cin, B, H, W, cin, cout, k)
     exact, _ = ref_convbn(x16, w, scale, shift, stride, pad)
     assert float(exact.max()) > 0 and cin * k[0] * k[1] * 6 < 2 ** 24
     got16, sat = run_convbn(pad_channels(x16), w, scale, shift, stride, pad, variant=variant)
@@ -221,18 +155,6 @@ def test_convbn_refuses_what_it_does_not_take():
 
 
 # ------------------------------------------------------------------------------------------------ pools
-def run_pool(x16, mode, out=None, out_off=0):
-    L, lib = _lib()
-    B, H, W, C_ = x16.shape
-    Ho, Wo = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == 0 else (H, W)
-    if out is None:
-        out = torch.full((B, Ho, Wo, C_), float("nan"), dtype=torch.float16)
-    xd, od = x16.to(DEV).contiguous(), out.to(DEV).contiguous()
-    L.check(lib.mb_pool3(xd.data_ptr(), od.data_ptr(), B, H, W, C_, mode, 0, C_, out_off, out.shape[3], _stream()), "mb_pool3")
-    torch.cuda.synchronize()
-    return od.cpu()
-
-
 def ref_avgpool(x16):
     """the stated fp32 expression: the in-image taps added one after the other in row-major order, divided by their number, rounded once"""
     x = x16.float().permute(0, 3, 1, 2)

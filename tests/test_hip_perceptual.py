@@ -24,24 +24,9 @@ import torch
 import torch.nn.functional as F
 
 import resnet_reference as R
+from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-U16 = 2.0 ** -11
-U32 = 2.0 ** -24
-
-
-def _lib():
-    from maskbit_amd import _lib
-    return _lib, _lib.load()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 # ------------------------------------------------------------------------------------------------ input kernel
@@ -100,93 +85,27 @@ def test_input_kernel_clamps():
 
 
 # ------------------------------------------------------------------------------------------------ the epilogues, per launch
-def run_convbn_ex(xbuf, w, scale, shift, stride, pad, epi, idn=None, idn_off=0, variant=0, old_entry=False):
-    """mb_convbn_layer_ex (old_entry: mb_convbn_layer): xbuf fp16 [B, H, W, in_cs] of which the first Cin channels are read, w fp32 OIHW, idn fp16
-    [B, Ho, Wo, idn_cs] of which channels [idn_off, idn_off + Cout) are the identity -> (the output on the CPU, saturation count)"""
-    L, lib = _lib()
-    B, H, W, in_cs = xbuf.shape
-    cout, cin, kh, kw = w.shape
-    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-    out = torch.full((B, Ho, Wo, cout), float("nan"), dtype=torch.float16, device=DEV)
-    xd, wd = xbuf.to(DEV).contiguous(), w.float().to(DEV).contiguous()
-    sc, sh = scale.float().to(DEV).contiguous(), shift.float().to(DEV).contiguous()
-    idd = idn.to(DEV).contiguous() if idn is not None else None
-    sat = C.c_uint(0)
-    geo = (B, H, W, cin, cout, kh, kw, stride, pad, pad, 0, in_cs, 0, cout, variant)
-    if old_entry:
-        L.check(lib.mb_convbn_layer(xd.data_ptr(), wd.data_ptr(), sc.data_ptr(), sh.data_ptr(), out.data_ptr(), C.byref(sat), *geo, _stream()), "mb_convbn_layer")
-    else:
-        L.check(lib.mb_convbn_layer_ex(xd.data_ptr(), wd.data_ptr(), sc.data_ptr(), sh.data_ptr(), out.data_ptr(), C.byref(sat), *geo, epi,
-                                       idd.data_ptr() if idd is not None else None, idn_off, idn.shape[3] if idn is not None else 0, _stream()),
-                "mb_convbn_layer_ex")
-    torch.cuda.synchronize()
-    return out.cpu(), int(sat.value)
-
-
-def ref_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn16=None):
-    """-> (exact float64 NCHW with fp16 weights, the magnitude sum S of the bound)"""
-    a = x16.double().permute(0, 3, 1, 2)
-    wq = w.to(torch.float16).double()
-    sc, sh = scale.float().double().view(1, -1, 1, 1), shift.float().double().view(1, -1, 1, 1)
-    y = F.conv2d(a, wq, None, stride, pad) * sc + sh
-    S = F.conv2d(a.abs(), wq.abs(), None, stride, pad) * sc.abs() + sh.abs()
-    if epi == R.EPI_RESIDUAL:
-        i = idn16.double().permute(0, 3, 1, 2)
-        y, S = y + i, S + i.abs()
-    return (y if epi == R.EPI_LINEAR else F.relu(y)), S
-
-
-def check_against_fp64(tag, got16, exact, S, K, epi):
-    got = got16.double().permute(0, 3, 1, 2)
-    model = R.h16r(exact)
-    assert got.shape == exact.shape and bool(torch.isfinite(got).all())
-    bound = U16 * exact.abs() + (K + 1) * U32 * S
-    err = (got - exact).abs()
-    worst = (err / bound.clamp(min=1e-300)).max().item()
-    e_kernel, e_model = err.pow(2).mean().sqrt().item(), (model - exact).pow(2).mean().sqrt().item()
-    print(f"convbn {tag}: max err / bound {worst:.3f}; rms err {e_kernel:.3e}, E_model {e_model:.3e}, ratio {e_kernel / e_model:.3f}; "
-          f"zeros {float((exact == 0).double().mean()):.2f}, negative {float((exact < 0).double().mean()):.2f}")
-    assert worst <= 1.0
-    assert e_model > 0.0 and e_kernel <= 1.25 * e_model
-    if epi == R.EPI_LINEAR:
-        assert bool((got < 0).any())
-    else:
-        assert bool((got >= 0).all()) and bool((got[exact == 0] == 0).all())       # what ReLU cuts is exactly 0
-
-
+# run_convbn, ref_convbn, check_against_fp64 and integer_case live in tests/convnet_helpers.py (imported above), shared with the Inception tests
 @pytest.mark.parametrize("name", list(R.CONV_CASES))
 def test_epilogue_layer_vs_fp64(name):
     B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
     x16, w, scale, shift, idn = R.conv_case(name, seed=5300 + cin + cout)
-    got16, sat = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn)
-    exact, S = ref_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn)
-    check_against_fp64(name, got16, exact, S, cin * k * k, epi)
+    got16, sat = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=idn)
+    exact, S = ref_convbn(x16, w, scale, shift, stride, pad, epi, idn)
+    check_against_fp64(name, got16, exact, S, cin * k * k + 1, epi)             # (K + 1) 2^-24 S: the K products and the epilogue
     assert sat == 0
-
-
-def integer_case(name, seed):
-    """operands whose every partial sum is an integer below 2^24 (exact in fp32), scale a power of two, shift and identity multiples of 1/2"""
-    B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
-    g = torch.Generator().manual_seed(seed)
-    x16 = torch.randint(0, 4, (B, H, W, cin), generator=g).to(torch.float16)
-    w = torch.randint(-2, 3, (cout, cin, k, k), generator=g).float()
-    scale = torch.pow(2.0, torch.randint(-3, 1, (cout,), generator=g).float())
-    shift = torch.randint(-8, 9, (cout,), generator=g).float() * 0.5
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    idn = (torch.randint(0, 64, (B, Ho, Wo, cout), generator=g).float() * 0.5).to(torch.float16) if epi == R.EPI_RESIDUAL else None
-    return x16, w, scale, shift, idn
 
 
 @pytest.mark.parametrize("variant", [1, 2])
 @pytest.mark.parametrize("name", list(R.CONV_CASES))
 def test_epilogue_integer_operands_are_bit_exact(name, variant):
     B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
-    x16, w, scale, shift, idn = integer_case(name, 5400 + cin)
-    exact, _ = ref_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn)
+    x16, w, scale, shift, idn = integer_case(5400 + cin, B, H, W, cin, cout, k, stride, pad, epi == R.EPI_RESIDUAL)
+    exact, _ = ref_convbn(x16, w, scale, shift, stride, pad, epi, idn)
     assert float(exact.max()) > 0 and cin * k * k * 6 < 2 ** 24
     if epi == R.EPI_LINEAR:
         assert float(exact.min()) < -4
-    got16, sat = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn, variant=variant)
+    got16, sat = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=idn, variant=variant)
     want16 = R.h16r(exact).permute(0, 2, 3, 1).to(torch.float16)
     assert torch.equal(bits(got16), bits(want16)) and sat == 0
 
@@ -195,10 +114,10 @@ def test_epilogue_integer_operands_are_bit_exact(name, variant):
 def test_epilogue_tile_shapes_give_the_same_bits(name):
     B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
     x16, w, scale, shift, idn = R.conv_case(name, seed=5500)
-    a, _ = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn, variant=1)
-    b, _ = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn, variant=2)
+    a, _ = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=idn, variant=1)
+    b, _ = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=idn, variant=2)
     assert torch.equal(bits(a), bits(b))
-    one, _ = run_convbn_ex(x16[1:2], w, scale, shift, stride, pad, epi, idn[1:2] if idn is not None else None)
+    one, _ = run_convbn(x16[1:2], w, scale, shift, stride, pad, epi=epi, idn=idn[1:2] if idn is not None else None)
     assert torch.equal(bits(one), bits(a[1:2]))                  # an image alone: a pixel's bits do not depend on its tile or the batch
 
 
@@ -207,8 +126,8 @@ def test_relu_epilogue_through_the_new_entry_is_the_old_one(name):
     B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
     x16, w, scale, shift, _ = R.conv_case(name, seed=5600)
     for variant in (1, 2):
-        new, s1 = run_convbn_ex(x16, w, scale, shift, stride, pad, R.EPI_RELU, variant=variant)
-        old, s0 = run_convbn_ex(x16, w, scale, shift, stride, pad, R.EPI_RELU, variant=variant, old_entry=True)
+        new, s1 = run_convbn(x16, w, scale, shift, stride, pad, epi=R.EPI_RELU, variant=variant)
+        old, s0 = run_convbn(x16, w, scale, shift, stride, pad, epi=None, variant=variant)
         assert torch.equal(bits(new), bits(old)) and s0 == s1 == 0
 
 
@@ -216,7 +135,7 @@ def test_identity_is_read_only_inside_its_slice():
     name = "residual 64->256 k1 14x14"
     B, H, W, cin, cout, k, stride, pad, epi = R.CONV_CASES[name]
     x16, w, scale, shift, idn = R.conv_case(name, seed=5700)
-    dense, _ = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, idn)
+    dense, _ = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=idn)
     assert bool(torch.isfinite(dense).all())
     wide = torch.full((B, H, W, 64 + cout + 32), float("nan"), dtype=torch.float16)          # NaN on both sides
     wide[..., 64:64 + cout] = idn
@@ -224,7 +143,7 @@ def test_identity_is_read_only_inside_its_slice():
     tight[..., 64:] = idn
     for variant in (1, 2):
         for buf in (wide, tight):
-            got, sat = run_convbn_ex(x16, w, scale, shift, stride, pad, epi, buf, idn_off=64, variant=variant)
+            got, sat = run_convbn(x16, w, scale, shift, stride, pad, epi=epi, idn=buf, idn_off=64, variant=variant)
             assert torch.equal(bits(got), bits(dense)) and sat == 0
 
 
@@ -244,15 +163,15 @@ def test_saturation_is_counted_on_both_signs():
         w[c, 0] = v
     one, zero = torch.ones(cout), torch.zeros(cout)
     for variant in (1, 2):
-        out, sat = run_convbn_ex(x16, w, one, zero, 1, 0, R.EPI_LINEAR, variant=variant)
+        out, sat = run_convbn(x16, w, one, zero, 1, 0, epi=R.EPI_LINEAR, variant=variant)
         assert sat == 2 * len(pix) * 4                            # groups 0, 1, 31 positive and 16 negative
-        exact, _ = ref_convbn_ex(x16, w, one, zero, 1, 0, R.EPI_LINEAR)
+        exact, _ = ref_convbn(x16, w, one, zero, 1, 0, R.EPI_LINEAR)
         assert torch.equal(out.double().permute(0, 3, 1, 2), exact.clamp(-65504.0, 65504.0))
         assert float(out[0, 0, 0, 64]) == -65504.0 and float(out[0, 0, 0, 0]) == 65504.0
         w1 = w / 2                                                # the convolution gives +-60000, the identity adds 60000 to channels 0 and 5
-        out, sat = run_convbn_ex(x16, w1, one, zero, 1, 0, R.EPI_RESIDUAL, idn, variant=variant)
+        out, sat = run_convbn(x16, w1, one, zero, 1, 0, epi=R.EPI_RESIDUAL, idn=idn, variant=variant)
         assert sat == 2 * len(pix) * 2                            # groups 0 and 1 reach 120000; group 31 stays at 60000; -60000 is cut
-        exact, _ = ref_convbn_ex(x16, w1, one, zero, 1, 0, R.EPI_RESIDUAL, idn)
+        exact, _ = ref_convbn(x16, w1, one, zero, 1, 0, R.EPI_RESIDUAL, idn)
         assert torch.equal(out.double().permute(0, 3, 1, 2), exact.clamp(max=65504.0))
         assert float(out[0, 0, 0, 64]) == 0.0 and float(out[0, 0, 0, 127]) == 60000.0 and float(out[0, 0, 0, 5]) == 65504.0
 
@@ -275,29 +194,17 @@ def test_stem_in_its_folded_form():
     assert torch.equal(cols[..., :147].double(), R.stem_cols64(img[..., :3].double().permute(0, 3, 1, 2)))
     assert torch.equal(cols[..., 147:], torch.zeros_like(cols[..., 147:]))
     cols[..., 147:] = float("nan")                                 # the convolution's K tail must mask the pad channels itself
-    exact, Smag = ref_convbn_ex(img[..., :3], w, scale, shift, 2, 3, R.EPI_RELU)
+    exact, Smag = ref_convbn(img[..., :3], w, scale, shift, 2, 3, R.EPI_RELU)
     outs = []
     for variant in (1, 2):
-        got16, sat = run_convbn_ex(cols, w.reshape(64, 147, 1, 1), scale, shift, 1, 0, R.EPI_RELU, variant=variant)
+        got16, sat = run_convbn(cols, w.reshape(64, 147, 1, 1), scale, shift, 1, 0, epi=R.EPI_RELU, variant=variant)
         assert sat == 0
         outs.append(got16)
-    check_against_fp64("stem 3->64 k7 s2 p3 32x32 folded", outs[0], exact, Smag, 147, R.EPI_RELU)
+    check_against_fp64("stem 3->64 k7 s2 p3 32x32 folded", outs[0], exact, Smag, 147 + 1, R.EPI_RELU)
     assert torch.equal(bits(outs[0]), bits(outs[1]))
 
 
 # ------------------------------------------------------------------------------------------------ pool
-def run_pool(x16, mode, out=None, out_off=0):
-    L, lib = _lib()
-    B, H, W, C_ = x16.shape
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if out is None:
-        out = torch.full((B, Ho, Wo, C_), float("nan"), dtype=torch.float16)
-    xd, od = x16.to(DEV).contiguous(), out.to(DEV).contiguous()
-    L.check(lib.mb_pool3_ex(xd.data_ptr(), od.data_ptr(), B, H, W, C_, mode, 0, C_, out_off, out.shape[3], _stream()), "mb_pool3_ex")
-    torch.cuda.synchronize()
-    return od.cpu()
-
-
 @pytest.mark.parametrize("H,W", [(14, 14), (9, 9)])
 def test_padded_stride2_pool_bit_equal(H, W):
     g = torch.Generator().manual_seed(H * W)
@@ -305,10 +212,10 @@ def test_padded_stride2_pool_bit_equal(H, W):
     x16[..., 1] = -x16[..., 1].abs() - 1.0                        # an all-negative channel: a padded border must not win with 0
     x16[0, 0, 0, 0], x16[0, 0, 1, 0] = 65504.0, -65504.0
     want = F.max_pool2d(x16.float().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).to(torch.float16)
-    got = run_pool(x16, 3)
+    got = run_pool(x16, 3, ex=True)
     assert got.shape == want.shape and torch.equal(bits(got), bits(want)) and bool((got[..., 1] < 0).all())
     sentinel = torch.full((2, got.shape[1], got.shape[2], 64 + 72), -1234.0, dtype=torch.float16)
-    out = run_pool(x16, 3, out=sentinel.clone(), out_off=40)
+    out = run_pool(x16, 3, out=sentinel.clone(), out_off=40, ex=True)
     assert torch.equal(bits(out[..., 40:104]), bits(want)) and bool((out[..., :40] == -1234.0).all()) and bool((out[..., 104:] == -1234.0).all())
 
 
