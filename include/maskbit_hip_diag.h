@@ -1,6 +1,6 @@
 /* libmaskbit_hip.so -- DIAGNOSTIC entry points: single kernels of the engine on caller buffers, for the unit tests (tests/test_hip_gemm.py,
  * test_hip_pair.py, test_hip_conv.py; the row kernels -- mb_layernorm, mb_layernorm_f4_seq, mb_layernorm_pair, mb_pairify, mb_embed_ln, mb_embed_pair --
- * in test_hip_rows.py; the quantizer kernels in test_hip_quantizer.py; the tokenizers' blocks in test_hip_taming_blocks.py) and the tools under tools/.  Nothing here is part of the reference's
+ * in test_hip_rows.py; the quantizer kernels in test_hip_quantizer.py; the tokenizers' blocks in test_hip_taming_blocks.py; the feature networks' tail in test_hip_convnet_tail.py) and the tools under tools/.  Nothing here is part of the reference's
  * surface and no host binding of the product needs it: include/maskbit_hip.h is the ABI.  Same conventions (device pointers, stream-ordered,
  * 0 / negative return, mb_last_error()).
  */
@@ -272,6 +272,28 @@ int mb_inception_input(const uint8_t* u8, void* out_h16, int B, int H, int W, mb
  * and Mixed_6e; pool, logits_unbiased, logits as in mb_inception_forward. */
 int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, void* map0, void* map1, void* map2, void* map3, float* tap64,
                       float* tap192, float* tap768, float* pool, float* logits_unbiased, float* logits, mb_stream stream);
+
+/* ---- the tail the Conv+BatchNorm networks share (inception.hip; mb_inception and mb_resnet both run it): the BatchNorm fold of the loaders, the
+ * spatial mean, the head and the channel tap, each through the product's own launcher on caller buffers (tests/test_hip_convnet_tail.py).  Every
+ * refusal is -1 with nothing launched.  No synchronisation.
+ * mb_bn_fold (launch_bn_fold): bn fp32 [4][cout] = gamma, beta, running mean, running variance -> scale[c] = gamma / sqrt(var + eps),
+ * shift[c] = beta - mean * scale: five fp32 operations, each rounded to nearest.  Refused: a NULL pointer, cout < 1, eps < 0 or NaN.
+ * mb_spatial_mean (launch_spatial_mean): x fp16 [B, HW, C] dense -> mean fp32 [B, C]: thread t of 256 adds pixels t, t + 256, .. in sequence from
+ * +0, then red[i] += red[i + o] for o = 128 .. 1, then one division by float(HW).  Refused: a NULL pointer, B < 1, HW < 1, C < 8 or C % 8.
+ * mb_fc_head (launch_fc_head): pool fp32 [B, D], w fp32 [N, D], bias fp32 [N] or NULL (read as 0) -> unbiased [B, N] = pool . w^T and / or
+ * biased = unbiased + bias (one fp32 add); a lane's fma chain over its D / 64 values, then six butterfly levels.  Refused: pool or w NULL, both
+ * outputs NULL, D not a multiple of 256 or beyond 2048 (the kernel would drop the tail), B < 1 or beyond 8 * 65535, N < 1.
+ * mb_channel_tap (launch_channel_tap): out fp32 [B, HW, C] = channels [off, off + C) of x fp16 [B, HW, cs], widened.  Refused: a NULL pointer, an
+ * empty shape, off < 0, off + C > cs.
+ * mb_inception_folded_bn / mb_resnet_folded_bn: the handle's folded scale and shift [cout] of the BatchNorm `bn_prefix` (its checkpoint entries
+ * without `.weight` ..; resolved as the handle's loader resolves an entry, so ResNet takes it with and without `model.`) copied to the caller's
+ * device buffers.  -2: the prefix names no BatchNorm of the handle; -4: cout is not its channel count (the loaders' codes). */
+int mb_bn_fold(const float* bn, float* scale, float* shift, int cout, float eps, mb_stream stream);
+int mb_spatial_mean(const void* x_h16, float* mean_f32, int B, int HW, int C, mb_stream stream);
+int mb_fc_head(const float* pool, const float* w, const float* bias, float* unbiased, float* biased, int B, int D, int N, mb_stream stream);
+int mb_channel_tap(const void* x_h16, float* out_f32, int B, int HW, int C, int off, int cs, mb_stream stream);
+int mb_inception_folded_bn(mb_inception* h, const char* bn_prefix, float* scale_out, float* shift_out, int cout, mb_stream stream);
+int mb_resnet_folded_bn(mb_resnet* h, const char* bn_prefix, float* scale_out, float* shift_out, int cout, mb_stream stream);
 
 /* ---- the pieces of the ResNet-50 perceptual loss (inception.hip, resnet.hip) on caller buffers.
  * mb_convbn_layer_ex: mb_convbn_layer with the epilogue chosen: 0 = fp16(relu(v)), v = fma(acc, scale, shift) (mb_convbn_layer itself, the same

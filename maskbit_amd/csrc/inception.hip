@@ -165,11 +165,17 @@ __global__ void repack_convbn_kernel(const float* __restrict__ w, h16* __restric
 }
 
 __global__ void bn_fold_kernel(const float* __restrict__ bn, float* __restrict__ scale, float* __restrict__ shift, int cout, float eps) {
+  // five fp32 operations, each rounded to nearest: plain operators under the pragma.  The __f*_rn functions are plain operators inside the HIP
+  // headers, out of the pragma's reach: the shift's product and difference written with them contract to one fma; and __fsqrt_rn is the bare
+  // v_sqrt_f32 approximation (1 ulp), where sqrtf is the correctly rounded root
+#pragma clang fp contract(off)
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cout) return;
-  const float s = __fdiv_rn(bn[c], __fsqrt_rn(__fadd_rn(bn[3 * cout + c], eps)));
+  const float a = bn[3 * cout + c] + eps;
+  const float s = bn[c] / sqrtf(a);
+  const float t = bn[2 * cout + c] * s;
   scale[c] = s;
-  shift[c] = __fsub_rn(bn[cout + c], __fmul_rn(bn[2 * cout + c], s));
+  shift[c] = bn[cout + c] - t;
 }
 
 // one thread per (output pixel, 8-channel slot)
@@ -670,6 +676,44 @@ int mb_inception_taps(mb_inception* h, const uint8_t* u8, int B, int H, int W, v
   if (int rc = check_inception("mb_inception_taps", h, u8, B, H, W)) return rc;
   run_inception(h, u8, B, H, W, IcOut{{map0, map1, map2, map3}, {tap64, tap192, tap768}, pool, logits_unbiased, logits}, (hipStream_t)stream);
   return launched();
+}
+
+// the tail kernels both networks share, each through its launcher (tests/test_hip_convnet_tail.py)
+int mb_bn_fold(const float* bn, float* scale, float* shift, int cout, float eps, mb_stream stream) {
+  if (!bn || !scale || !shift) return fail(-1, "mb_bn_fold: null argument");
+  if (cout < 1 || !(eps >= 0.f)) return fail(-1, "mb_bn_fold: cout %d, eps %g: cout >= 1 and eps >= 0", cout, (double)eps);
+  launch_bn_fold((hipStream_t)stream, bn, scale, shift, cout, eps);
+  return launched();
+}
+
+int mb_spatial_mean(const void* x_h16, float* mean_f32, int B, int HW, int C, mb_stream stream) {
+  if (!x_h16 || !mean_f32) return fail(-1, "mb_spatial_mean: null argument");
+  if (B < 1 || HW < 1 || C < 8 || C % 8) return fail(-1, "mb_spatial_mean: [%d, %d, %d]: B >= 1, HW >= 1, C a multiple of 8", B, HW, C);
+  launch_spatial_mean((hipStream_t)stream, (const h16*)x_h16, mean_f32, B, HW, C);
+  return launched();
+}
+
+int mb_fc_head(const float* pool, const float* w, const float* bias, float* unbiased, float* biased, int B, int D, int N, mb_stream stream) {
+  if (!pool || !w) return fail(-1, "mb_fc_head: null argument");
+  if (!unbiased && !biased) return fail(-1, "mb_fc_head: no output: unbiased and biased are both null");
+  // a lane holds D / 256 pieces of 4 values, 8 at the most: another D would lose its tail without a word
+  if (D < 256 || D % 256 || D > 2048) return fail(-1, "mb_fc_head: D %d: a multiple of 256 up to 2048", D);
+  if (B < 1 || B > 8 * 65535 || N < 1) return fail(-1, "mb_fc_head: B %d, N %d: 1 <= B <= %d, N >= 1", B, N, 8 * 65535);
+  launch_fc_head((hipStream_t)stream, pool, w, bias, unbiased, biased, B, D, N);
+  return launched();
+}
+
+int mb_channel_tap(const void* x_h16, float* out_f32, int B, int HW, int C, int off, int cs, mb_stream stream) {
+  if (!x_h16 || !out_f32) return fail(-1, "mb_channel_tap: null argument");
+  if (B < 1 || HW < 1 || C < 1) return fail(-1, "mb_channel_tap: empty shape [%d, %d, %d]", B, HW, C);
+  if (off < 0 || cs < 1 || (long long)off + C > cs) return fail(-1, "mb_channel_tap: channels [%d, %d + %d) are not inside a pixel of %d", off, off, C, cs);
+  launch_channel_tap((hipStream_t)stream, (const h16*)x_h16, out_f32, B, HW, C, off, cs);
+  return launched();
+}
+
+int mb_inception_folded_bn(mb_inception* h, const char* bn_prefix, float* scale_out, float* shift_out, int cout, mb_stream stream) {
+  if (!h || !bn_prefix || !scale_out || !shift_out) return fail(-1, "mb_inception_folded_bn: null argument");
+  return folded_bn("mb_inception_folded_bn", h->cn, bn_prefix, std::string(bn_prefix) + CN_BN_NAMES[0], scale_out, shift_out, cout, (hipStream_t)stream);
 }
 
 }  // extern "C"

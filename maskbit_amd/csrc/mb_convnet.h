@@ -103,6 +103,20 @@ inline int load_entry(const char* what, ConvNet& n, const char* name, const std:
   return rc;
 }
 
+// the diagnostic entries mb_*_folded_bn (`what`; `name`: the BatchNorm's prefix as the caller gave it, `key`: its `.weight` entry as the table has
+// it): the folded scale and shift, as the convolution's epilogue reads them, copied to the caller's device buffers.  0, -2 for a prefix that
+// names no BatchNorm of the handle, -4 for a wrong channel count -- the loader's codes
+inline int folded_bn(const char* what, const ConvNet& n, const char* name, const std::string& key, float* scale_out, float* shift_out, int cout,
+                     hipStream_t s) {
+  const auto it = n.table.find(key);
+  if (it == n.table.end() || it->second.kind != CN_BN) return fail(-2, "%s: unknown BatchNorm '%s'", what, name);
+  const CnConv& c = n.convs[it->second.conv];
+  if (cout != c.cout) return fail(-4, "%s: %s: expected %d values", what, name, c.cout);
+  HIP_TRY(hipMemcpyAsync(scale_out, c.scale, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(shift_out, c.shift, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
 // 0, or -1 with the name of an entry that is still to be loaded
 inline int complete(const char* what, const ConvNet& n) {
   if (!n.missing) return 0;

@@ -290,6 +290,9 @@ const h16* run_trunk(mb_resnet* h, const h16* img, int N, int S, const RnOut& o,
   return h->buf[xi];
 }
 
+// a checkpoint entry's name as the table has it
+std::string table_key(const mb_resnet* h, const std::string& name) { return h->cn.table.count(name) ? name : RN_PREFIX + name; }
+
 }  // namespace
 
 extern "C" {
@@ -319,9 +322,7 @@ int mb_resnet_load(mb_resnet* h, const char* name, const float* data, const int6
   if (!h || !name || !data || !shape || ndim < 0) return fail(-1, "mb_resnet_load: bad arguments");
   // the table is in the reference's layout (mean, std, model.<torchvision's key>); torchvision's own has no prefix.  Accepted are the names
   // that stripping one leading `model.` -- after mean / std have been tried -- turns into a torchvision key: `model.mean` is none
-  std::string key(name);
-  if (!h->cn.table.count(key)) key = RN_PREFIX + key;
-  return load_entry("mb_resnet_load", h->cn, name, key, data, shape, ndim, (hipStream_t)stream);
+  return load_entry("mb_resnet_load", h->cn, name, table_key(h, name), data, shape, ndim, (hipStream_t)stream);
 }
 
 int mb_resnet_forward(mb_resnet* h, const float* real, const float* fake, int B, int H, int W, int clamp01, int on_logits, double* per_pair, double* sum,
@@ -391,6 +392,12 @@ int mb_resnet_taps(mb_resnet* h, const void* image_h16, int B, int S, void* laye
   int HW = 0;
   run_trunk(h, (const h16*)image_h16, B, S, RnOut{{layer1, layer2, layer3, layer4}, pool, logits}, &HW, (hipStream_t)stream);
   return launched();
+}
+
+int mb_resnet_folded_bn(mb_resnet* h, const char* bn_prefix, float* scale_out, float* shift_out, int cout, mb_stream stream) {
+  if (!h || !bn_prefix || !scale_out || !shift_out) return fail(-1, "mb_resnet_folded_bn: null argument");
+  return folded_bn("mb_resnet_folded_bn", h->cn, bn_prefix, table_key(h, std::string(bn_prefix) + CN_BN_NAMES[0]), scale_out, shift_out, cout,
+                   (hipStream_t)stream);
 }
 
 }  // extern "C"

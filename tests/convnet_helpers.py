@@ -1,6 +1,7 @@
 """What the per-launch GPU tests of the Conv+BatchNorm networks (test_hip_inception.py, test_hip_perceptual.py) share: the library handle, one
 runner of the convolution's two diagnostic entries, its float64 reference with the magnitude sum of the bound, the error criterion, the
-integer-operand case maker and the pool runner."""
+integer-operand case maker and the pool runner; and the runners of the fp32 tail's entries (mb_bn_fold, mb_spatial_mean, mb_fc_head,
+mb_channel_tap, mb_*_folded_bn), each on a window of a NaN-filled buffer (tests/test_hip_convnet_tail.py)."""
 import ctypes as C
 
 import torch
@@ -104,6 +105,100 @@ def integer_case(seed, B, H, W, cin, cout, k, stride=1, pad=0, residual=False):
     Ho, Wo = (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
     idn = (torch.randint(0, 64, (B, Ho, Wo, cout), generator=g).float() * 0.5).to(torch.float16) if residual else None
     return x16, w, scale, shift, idn
+
+
+# ---- the networks' tail (tests/test_hip_convnet_tail.py and the network tests): every runner hands the entry a window of a larger buffer filled
+# with NaN and returns (the window, whether everything outside it still holds the sentinel), both on the CPU
+GUARD = 64
+
+
+def bits32(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _guarded(n):
+    return torch.full((n + 2 * GUARD,), float("nan"), dtype=torch.float32, device=DEV)
+
+
+def _window(buf, n):
+    host = buf.cpu()
+    return host[GUARD:GUARD + n].clone(), bool(torch.isnan(host[:GUARD]).all()) and bool(torch.isnan(host[GUARD + n:]).all())
+
+
+def run_bn_fold(bn, eps):
+    """mb_bn_fold on bn fp32 [4, cout] -> (scale, shift, untouched)"""
+    L, lib = _lib()
+    cout = bn.shape[1]
+    bd = bn.float().to(DEV).contiguous()
+    sc, sh = _guarded(cout), _guarded(cout)
+    L.check(lib.mb_bn_fold(bd.data_ptr(), sc[GUARD:].data_ptr(), sh[GUARD:].data_ptr(), cout, eps, _stream()), "mb_bn_fold")
+    torch.cuda.synchronize()
+    (s, ok_s), (t, ok_t) = _window(sc, cout), _window(sh, cout)
+    return s, t, ok_s and ok_t
+
+
+def run_spatial_mean(x16):
+    """mb_spatial_mean on x16 fp16 [B, HW, C] -> (mean fp32 [B, C], untouched)"""
+    L, lib = _lib()
+    B, HW, C_ = x16.shape
+    xd = x16.to(DEV).contiguous()
+    out = _guarded(B * C_)
+    L.check(lib.mb_spatial_mean(xd.data_ptr(), out[GUARD:].data_ptr(), B, HW, C_, _stream()), "mb_spatial_mean")
+    torch.cuda.synchronize()
+    got, ok = _window(out, B * C_)
+    return got.view(B, C_), ok
+
+
+def run_fc_head(pool, w, bias=None, unbiased=True, biased=True):
+    """mb_fc_head -> (unbiased or None, biased or None, untouched); pool [B, D], w [N, D], bias [N] or None"""
+    L, lib = _lib()
+    (B, D), N = pool.shape, w.shape[0]
+    pd, wd = pool.float().to(DEV).contiguous(), w.float().to(DEV).contiguous()
+    bd = bias.float().to(DEV).contiguous() if bias is not None else None
+    ou, ob = (_guarded(B * N) if unbiased else None), (_guarded(B * N) if biased else None)
+    ptr = lambda t: t[GUARD:].data_ptr() if t is not None else None
+    L.check(lib.mb_fc_head(pd.data_ptr(), wd.data_ptr(), bd.data_ptr() if bd is not None else None, ptr(ou), ptr(ob), B, D, N, _stream()), "mb_fc_head")
+    torch.cuda.synchronize()
+    got, ok = [], True
+    for t in (ou, ob):
+        if t is None:
+            got.append(None)
+        else:
+            v, fine = _window(t, B * N)
+            got.append(v.view(B, N))
+            ok = ok and fine
+    return got[0], got[1], ok
+
+
+def run_channel_tap(buf16, C_, off):
+    """mb_channel_tap on channels [off, off + C_) of buf16 fp16 [B, HW, cs] -> (out fp32 [B, HW, C_], untouched)"""
+    L, lib = _lib()
+    B, HW, cs = buf16.shape
+    xd = buf16.to(DEV).contiguous()
+    n = B * HW * C_
+    out = _guarded(n)
+    L.check(lib.mb_channel_tap(xd.data_ptr(), out[GUARD:].data_ptr(), B, HW, C_, off, cs, _stream()), "mb_channel_tap")
+    torch.cuda.synchronize()
+    got, ok = _window(out, n)
+    return got.view(B, HW, C_), ok
+
+
+def folded_bns(abi, h, layers):
+    """mb_{abi}_folded_bn of every (BatchNorm prefix, cout) in `layers` on handle h -> {prefix: (scale, shift)} fp32 on the CPU"""
+    L, lib = _lib()
+    entry = getattr(lib, f"mb_{abi}_folded_bn")
+    total = sum(c for _p, c in layers)
+    buf = torch.full((2, total), float("nan"), dtype=torch.float32, device=DEV)
+    at = 0
+    for prefix, cout in layers:
+        L.check(entry(h, prefix.encode(), buf[0, at:].data_ptr(), buf[1, at:].data_ptr(), cout, _stream()), f"mb_{abi}_folded_bn({prefix})")
+        at += cout
+    torch.cuda.synchronize()
+    host, out, at = buf.cpu(), {}, 0
+    for prefix, cout in layers:
+        out[prefix] = (host[0, at:at + cout].clone(), host[1, at:at + cout].clone())
+        at += cout
+    return out
 
 
 def run_pool(x16, mode, out=None, out_off=0, ex=False):

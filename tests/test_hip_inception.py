@@ -1,6 +1,8 @@
-"""The Inception-v3 feature extractor on the HIP path (maskbit_amd/csrc/inception.hip): every kernel alone on its smallest shapes through the
-diagnostic entries of include/maskbit_hip_diag.h, the whole network against the float64 restatement of the specification
-(tests/inception_reference.py) on seeded weights, and the product surface (``InceptionV3``, the evaluators' ``use_inception``).
+"""The Inception-v3 feature extractor on the HIP path (maskbit_amd/csrc/inception.hip): the convolution, pool and input kernels alone on their
+smallest shapes through the diagnostic entries of include/maskbit_hip_diag.h (``repack_convbn_kernel`` runs inside ``mb_convbn_layer``; the fp32
+tail -- ``bn_fold_kernel``, ``spatial_mean_kernel``, ``fc_head_kernel``, ``channel_tap_kernel`` -- has its per-launch tests in
+tests/test_hip_convnet_tail.py), the whole network against the float64 restatement of the specification (tests/inception_reference.py) on
+seeded weights, and the product surface (``InceptionV3``, the evaluators' ``use_inception``).
 
 Tolerances are derived, none is tuned to what the kernels give:
 
@@ -13,6 +15,9 @@ Tolerances are derived, none is tuned to what the kernels give:
 * input kernel: 2^-11 |exact| (the fp16 store) + 8 x 2^-24 (the fp32 evaluation of two nested interpolations of values up to 255, over 128).
 * whole network: the four fp16 maps have error rms <= 1.5 x and max <= 2 x the model's (`model` = the float64 restatement with fp16 weights
   and fp16 stored activations); every fp32 output is within 2 E of exact, E = max |model - exact|.  The weights are seeded, not the checkpoint.
+* the network's fp32 tail, on the same run's buffers: ``192``, ``768`` and ``2048`` are bit-equal to the stated fp32 mean
+  (convnet_reference.spatial_mean32) of the run's own fp16 maps; both logits are within (2048 / 64 + 7) 2^-24 (sum |p w| + |bias|) of the float64
+  head of the run's own fp32 pooled features; ``logits`` is ``logits_unbiased`` plus the bias in one fp32 add.
 """
 import ctypes as C
 import functools
@@ -21,8 +26,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convnet_reference as CR
 import inception_reference as R
-from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
+from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, bits32, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
 
 pytestmark = pytest.mark.gpu
 
@@ -281,6 +287,20 @@ def test_network_maps_and_features(name):
         print(f"{name} {k}: E {E:.3e}, |hip - exact| / E {d / E:.3f}")
         assert got.shape == exact[k].shape and E > 0 and d <= 2 * E
     assert sat == 0
+    # the fp32 tail on the run's own buffers, in its own unit: the taps and the pooled features are the stated fp32 mean of the fp16 maps the same
+    # run handed out (map 0: the 192-channel pool, 2: Mixed_6e, 3: Mixed_7c), the logits the head of the run's own fp32 pooled features
+    nhwc16 = lambda m: m.permute(0, 2, 3, 1).reshape(m.shape[0], -1, m.shape[1]).to(torch.float16)
+    for key, k in (("192", 0), ("768", 2), ("2048", 3)):
+        assert torch.equal(bits32(outs[key].float()), bits32(CR.spatial_mean32(nhwc16(maps[k])))), key
+    sd = R.weights(R.CASES[name][4])
+    pool32 = outs["2048"].float()
+    head_u, head_b, S = CR.fc_head64(pool32, sd["fc.weight"], sd["fc.bias"])
+    bound = CR.head_bound(2048, S)
+    for key, want in (("logits_unbiased", head_u), ("logits", head_b)):
+        err = (outs[key] - want).abs()
+        print(f"{name} {key} against the float64 head of its own pool: worst err / bound {float((err / bound).max()):.3f}")
+        assert bool((err <= bound).all())
+    assert torch.equal(bits32(outs["logits"].float()), bits32(outs["logits_unbiased"].float() + sd["fc.bias"].float()))
 
 
 # ------------------------------------------------------------------------------------------------ the product

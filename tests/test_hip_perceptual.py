@@ -1,5 +1,7 @@
-"""The ResNet-50 perceptual loss on the HIP path (maskbit_amd/csrc/resnet.hip and the epilogues of csrc/inception.hip): every new kernel alone on
-its smallest shapes through the diagnostic entries of include/maskbit_hip_diag.h, the trunk against the float64 restatement of the specification
+"""The ResNet-50 perceptual loss on the HIP path (maskbit_amd/csrc/resnet.hip and the epilogues of csrc/inception.hip): every kernel resnet.hip
+adds and every new epilogue alone on its smallest shapes through the diagnostic entries of include/maskbit_hip_diag.h (the fp32 tail it shares
+with Inception-v3 -- ``bn_fold_kernel`` at eps 1e-5, ``spatial_mean_kernel``, ``fc_head_kernel`` -- has its per-launch tests, and the fold of
+each of the 53 BatchNorms, in tests/test_hip_convnet_tail.py), the trunk against the float64 restatement of the specification
 (tests/resnet_reference.py) on seeded weights at two small sides, the whole path at two image sizes, and the product surface (``PerceptualLoss``,
 ``TokenizerEvaluator.use_perceptual``).
 
@@ -13,6 +15,8 @@ Tolerances are derived, none is tuned to what the kernels give:
 * pool: the maximum of fp16 values is exact: bit-equal.
 * trunk: the four fp16 layer maps have error rms <= 1.5 x and max <= 2 x the model's (`model` = the float64 restatement with fp16 weights and
   fp16 stored activations); pooled features and logits within 2 E of exact, E = max |model - exact|.
+* the trunk's fp32 tail, on the same run's buffers: the pooled features are bit-equal to the stated fp32 mean (convnet_reference.spatial_mean32)
+  of the run's own layer4 map; the logits are within (2048 / 64 + 7) 2^-24 (sum |p w| + |bias|) of the float64 head of the run's own pool.
 * whole path: each logit within 2 E, so each difference within 4 E: |loss - exact| <= mean(2 |a - b| 4 E + (4 E)^2), and the same with the layer4
   model error for the features term.
 """
@@ -23,8 +27,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convnet_reference as CR
 import resnet_reference as R
-from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
+from convnet_helpers import DEV, U16, U32, _lib, _stream, bits, bits32, check_against_fp64, integer_case, ref_convbn, run_convbn, run_pool
 
 pytestmark = pytest.mark.gpu
 
@@ -302,6 +307,16 @@ def test_trunk_maps_and_features(name):
         print(f"{name} {key}: E {E:.3e}, |hip - exact| / E {d / E:.3f}")
         assert got.shape == exact[key].shape and E > 0 and d <= 2 * E
     assert sat == 0
+    # the fp32 tail on the run's own buffers, in its own unit: the pooled features are the stated fp32 mean of the layer4 map the same run handed
+    # out, the logits the head of the run's own fp32 pooled features
+    l4 = maps[3]
+    l4_16 = l4.permute(0, 2, 3, 1).reshape(l4.shape[0], -1, l4.shape[1]).to(torch.float16)
+    assert torch.equal(bits32(pool.float()), bits32(CR.spatial_mean32(l4_16)))
+    sd = R.weights()
+    _unbiased, want, Smag = CR.fc_head64(pool.float(), sd["fc.weight"], sd["fc.bias"])
+    err, bound = (logits - want).abs(), CR.head_bound(2048, Smag)
+    print(f"{name} logits against the float64 head of its own pool: worst err / bound {float((err / bound).max()):.3f}")
+    assert bool((err <= bound).all())
 
 
 # ------------------------------------------------------------------------------------------------ whole path

@@ -245,7 +245,8 @@ def test_c_entries_are_declared_and_bound():
     diag = open(os.path.join(ROOT, "include", "maskbit_hip_diag.h")).read()
     for name in ("mb_inception_create", "mb_inception_destroy", "mb_inception_load", "mb_inception_forward", "mb_inception_saturation_count"):
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, abi)
-    for name in ("mb_convbn_layer", "mb_pool3", "mb_inception_input", "mb_inception_taps"):
+    for name in ("mb_convbn_layer", "mb_pool3", "mb_inception_input", "mb_inception_taps", "mb_bn_fold", "mb_spatial_mean", "mb_fc_head",
+                 "mb_channel_tap", "mb_inception_folded_bn"):
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, diag) and not re.search(r"\b%s\s*\(" % name, abi)
     assert "#define MB_ABI_VERSION 8" in abi and _lib.ABI_VERSION == 8          # additions only
     assert "inception.hip" in build.SOURCES

@@ -150,7 +150,8 @@ def test_c_entries_are_declared_and_bound():
     diag = open(os.path.join(ROOT, "include", "maskbit_hip_diag.h")).read()
     for name in ("mb_resnet_create", "mb_resnet_destroy", "mb_resnet_load", "mb_resnet_forward", "mb_resnet_saturation_count"):
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, abi)
-    for name in ("mb_convbn_layer_ex", "mb_pool3_ex", "mb_resnet_input", "mb_resnet_stem_cols", "mb_resnet_distance", "mb_resnet_taps"):
+    for name in ("mb_convbn_layer_ex", "mb_pool3_ex", "mb_resnet_input", "mb_resnet_stem_cols", "mb_resnet_distance", "mb_resnet_taps",
+                 "mb_resnet_folded_bn"):
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, diag) and not re.search(r"\b%s\s*\(" % name, abi)
     assert "#define MB_ABI_VERSION 8" in abi and _lib.ABI_VERSION == 8          # additions only
     assert "resnet.hip" in build.SOURCES
@@ -193,3 +194,14 @@ def test_argument_refusals_need_no_device():
     assert lib.mb_resnet_distance(p, None, 0, 1000, 0, p, None, None) != 0
     assert lib.mb_resnet_distance(p, p, 1, 1000, 12, p, None, None) != 0
     assert lib.mb_resnet_distance(None, None, 1, 1000, 0, p, None, None) != 0
+    # the tail both networks share (include/maskbit_hip_diag.h): each -1
+    assert lib.mb_bn_fold(p, p, p, 0, 1e-5, None) == -1 and lib.mb_bn_fold(p, p, p, 8, -1.0, None) == -1 and lib.mb_bn_fold(None, p, p, 8, 1e-5, None) == -1
+    for B, HW, C_ in ((1, 4, 12), (1, 0, 8), (0, 4, 8), (1, 4, 0)):
+        assert lib.mb_spatial_mean(p, p, B, HW, C_, None) == -1
+    for B, D, N in ((1, 2047, 4), (1, 2304, 4), (1, 0, 4), (0, 256, 4), (1, 256, 0)):
+        assert lib.mb_fc_head(p, p, p, p, p, B, D, N, None) == -1, (B, D, N)
+    assert lib.mb_fc_head(p, p, p, None, None, 1, 256, 4, None) == -1 and lib.mb_fc_head(None, p, p, p, None, 1, 256, 4, None) == -1
+    for B, HW, C_, off, cs in ((1, 4, 8, 17, 24), (1, 4, 8, -8, 24), (1, 4, 0, 0, 24), (0, 4, 8, 0, 24), (1, 0, 8, 0, 24)):
+        assert lib.mb_channel_tap(p, p, B, HW, C_, off, cs, None) == -1
+    assert lib.mb_resnet_folded_bn(None, b"bn1", p, p, 64, None) == -1 and lib.mb_inception_folded_bn(None, b"Conv2d_1a_3x3.bn", p, p, 32, None) == -1
+    assert b"mb_inception_folded_bn" in lib.mb_last_error()
