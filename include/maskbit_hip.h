@@ -512,6 +512,29 @@ int mb_resnet_forward(mb_resnet* h, const float* real, const float* fake, int B,
 /* 4-channel output groups the convolutions clamped at the fp16 range since the last reset.  Synchronises the stream. */
 int mb_resnet_saturation_count(mb_resnet* h, unsigned* count, int reset, mb_stream stream);
 
+/* ---- VQGAN+ discriminator: modeling/modules/discriminator.py NLayerDiscriminatorv2 -------------------------------------------------------------- *
+ * The graph of DESIGN.md "Discriminator", inference only (csrc/discriminator.hip): block_in (5 x 5 + LeakyReLU 0.1), `stages` stages of 3 x 3
+ * convolution, downsample (blur_kernel 3, 4, 5: BlurBlock; 0: AvgPool2d(2)), GroupNorm(32, eps 1e-5) and LeakyReLU, AdaptiveMaxPool2d(16), to_logits.
+ * hidden a multiple of 32; 1 .. 4 stages; at most 2048 channels in the last stage.  fp16 NHWC activations, fp32 accumulation.  The workspace holds
+ * max_images images of 256 x 256 (at least one of 512 x 512): a batch is walked in chunks of as many images as fit, 4 max_images at the most.
+ * Additions, MB_ABI_VERSION unchanged. */
+typedef struct mb_disc mb_disc;
+int mb_disc_create(int max_images, int hidden, int stages, int blur_kernel, mb_disc** out);
+void mb_disc_destroy(mb_disc* h);
+/* One state-dict entry (device fp32) of the reference module: `block_in.0.{weight,bias}` [hidden, 3, 5, 5], `blocks.I.0.{weight,bias}`,
+ * `blocks.I.2.{weight,bias}` (GroupNorm), `to_logits.0.{weight,bias}`, `to_logits.2.{weight,bias}` [1, c, 5, 5]; with a blur, `blocks.I.1.kernel`
+ * [1, 1, k, k] must EQUAL the binomial kernel the handle computes itself (that entry synchronises the stream).  -2: unknown name, -4: wrong
+ * size, or a blur kernel that is not the binomial one. */
+int mb_disc_load(mb_disc* h, const char* name, const float* data, const int64_t* shape, int ndim, mb_stream stream);
+/* images fp32 [B, 3, H, W], H and W multiples of 16 in [32, 512] (clamp01 != 0: clamped to [0, 1] on the load).  Each output may be NULL:
+ * logits fp32 [B, 256] (the 16 x 16 map, row-major); stats double [B, 5] = per image the sums over its 256 logits l of l, relu(1 - l), relu(1 + l),
+ * softplus(-l), softplus(l) (softplus as max(x, 0) + log1p(exp(-|x|)) in double); sum double [5] += those sums in image order.  Fixed summation
+ * order, no floating-point atomics: an image's logits and sums do not depend on B, on the chunking or on its place in the batch, bit for bit.
+ * No synchronisation.  Fails (-1) before any launch when the checkpoint is incomplete ("not complete") or the geometry is not taken. */
+int mb_disc_forward(mb_disc* h, const float* images, int B, int H, int W, int clamp01, float* logits, double* stats, double* sum, mb_stream stream);
+/* output groups (4 channels of a convolution, 8 of a GroupNorm) clamped at the fp16 range since the last reset.  Synchronises the stream. */
+int mb_disc_saturation_count(mb_disc* h, unsigned* count, int reset, mb_stream stream);
+
 /* ---- Taming VQGAN tokenizer: OriginalVQModel, modeling/taming_vqgan.py:19-69 (Encoder / Decoder of modeling/taming/taming_autoencoder.py) ---- *
  * The fixed network of that class: ch 128, ch_mult (1,1,2,2,4), 2 (decoder: 3) res blocks per level, seven single-head AttnBlocks of 512 channels at
  * the 16-pixel level, quant_conv / post_quant_conv, SimpleVectorizer(1024, 256) without normalisation.  fp16 NHWC activations on the convolution

@@ -325,6 +325,31 @@ int mb_resnet_distance(const float* logits, const void* feat_h16, int B, int N, 
 int mb_resnet_taps(mb_resnet* h, const void* image_h16, int B, int S, void* layer1, void* layer2, void* layer3, void* layer4, float* pool, float* logits,
                    mb_stream stream);
 
+/* ---- the pieces of the VQGAN+ discriminator (discriminator.hip; the LeakyReLU epilogue in inception.hip) on caller buffers, one launcher each.
+ * mb_convbn_layer_leaky: mb_convbn_layer_ex plus epilogue 3 = fp16(v >= 0 ? v : v * slope), v = fma(acc, scale, shift), 0 <= slope <= 1,
+ * *saturated counts groups with |v| > 65504; mb_convbn_layer_ex keeps refusing 3.  Synchronises the stream.
+ * mb_disc_cols: images fp32 [B, 3, H, W] -> block_in's im2col fp16 [B, H, W, 96]: channel ci * 25 + ky * 5 + kx < 75 = pixel (y - 2 + ky,
+ * x - 2 + kx) of channel ci or 0 outside the image, channels 75 .. 95 = 0.
+ * mb_disc_downsample: x fp16 [B, H, W, C] (C % 8 == 0, C <= 2048; H, W >= 2) -> y fp16 [B, Ho, Wo, C]; K = 3, 4, 5: the binomial blur with stride 2
+ * and BlurBlock's padding (per axis pad = max((ceil(n / 2) - 1) 2 + K - n, 0), pad / 2 in front), Ho = ceil(H / 2); K = 0: AvgPool2d(2), Ho =
+ * floor(H / 2).  part (may be NULL; needs C % 32 == 0) float [B][nchunk][32][2], nchunk = mb_disc_down_chunks(Ho, Wo, C): per image, chunk of
+ * ceil(Ho Wo / nchunk) consecutive output pixels and GroupNorm group the sum and the sum of squares of the fp32 values before rounding.
+ * mb_disc_groupnorm: GroupNorm(32, C, eps 1e-5) + affine + LeakyReLU(slope) in place on x fp16 [B, HW, C] (C % 32 == 0, C <= 2048) with the
+ * statistics taken from part [B][nchunk][32][2] (1 <= nchunk); *saturated (may be NULL) = the 8-channel groups clamped.  Synchronises the stream.
+ * mb_disc_pool: AdaptiveMaxPool2d((16, 16)) x fp16 [B, H, W, C] -> y fp16 [B, 16, 16, C] (C % 8 == 0; any H, W >= 1).
+ * mb_disc_logits: x fp16 [B, 16, 16, C] (C % 8 == 0), w_oihw fp32 [1, C, 5, 5], bias fp32 [1] -> logits / stats / sum as mb_disc_forward leaves them
+ * (each may be NULL; sum needs stats).  Synchronises the stream. */
+int mb_convbn_layer_leaky(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B,
+                          int H, int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs,
+                          int variant, int epilogue, float slope, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream);
+int mb_disc_cols(const float* images, void* cols_h16, int B, int H, int W, int clamp01, mb_stream stream);
+int mb_disc_down_chunks(int Ho, int Wo, int C);
+int mb_disc_downsample(const void* x_h16, void* y_h16, float* part, int B, int H, int W, int C, int K, mb_stream stream);
+int mb_disc_groupnorm(void* x_h16, const float* part, int nchunk, const float* gamma, const float* beta, unsigned* saturated, int B, int HW, int C,
+                      float slope, mb_stream stream);
+int mb_disc_pool(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream);
+int mb_disc_logits(const void* x_h16, const float* w_oihw, const float* bias, float* logits, double* stats, double* sum, int B, int C, mb_stream stream);
+
 /* ---- the Taming tokenizer (spatial_attention.hip, taming.hip).
  * mb_spatial_attention: the AttnBlock's attention as the handle launches it: one head of 512 channels over the N pixels of each of B images,
  * out[b, i] = sum_j softmax_j(q[b, i] . k[b, j] * 512^-0.5) v[b, j].  q, k, v fp16, pixel (b, i) at element (b N + i) * ld of each (ld >= 512,

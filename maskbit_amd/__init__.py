@@ -13,6 +13,7 @@ from .generator_evaluator import GeneratorEvaluator, frechet_distance, get_covar
 from .manifold import knn_radii, manifold_coverage, precision_recall
 from .lpips import LPIPS
 from .perceptual import PerceptualLoss, create_perception_loss
+from .discriminator import NLayerDiscriminatorv2, VQGANLoss, create_discriminator
 from .image_transform import ImageTransform, transformed
 from .inception import InceptionV3, get_inception_model
 from .editing import inpaint, sample_from_tokens
@@ -25,6 +26,7 @@ __all__ = ["BaseModel", "Bert", "LFQBert", "ConvVQModel", "OriginalVQModel", "sa
            "combine_factorized_tokens", "split_factorized_tokens", "eval_labels", "generate_uint8", "mask_token_for", "to_evaluator_uint8",
            "TokenizerEvaluator", "eval_reconstruction", "inpaint", "sample_from_tokens",
            "get_mask_tokens", "MLMLoss", "MaskedTokenEvaluator", "eval_masked_prediction", "LPIPS", "PerceptualLoss", "create_perception_loss",
+           "NLayerDiscriminatorv2", "VQGANLoss", "create_discriminator",
            "GeneratorEvaluator", "eval_generation", "frechet_distance", "inception_score", "get_covariance",
            "InceptionV3", "get_inception_model", "check_checkpoint", "CheckpointReport",
            "knn_radii", "manifold_coverage", "precision_recall", "ImageTransform", "transformed"]

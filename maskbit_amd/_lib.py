@@ -210,6 +210,18 @@ SIGNATURES = {
     "mb_resnet_stem_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mb_resnet_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mb_resnet_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "mb_disc_create": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_void_p)]),
+    "mb_disc_destroy": (None, [C.c_void_p]),
+    "mb_disc_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "mb_disc_forward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4),
+    "mb_disc_saturation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int, C.c_void_p]),
+    "mb_convbn_layer_leaky": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(C.c_uint)] + [C.c_int] * 16 + [C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mb_disc_cols": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "mb_disc_down_chunks": (C.c_int, [C.c_int] * 3),
+    "mb_disc_downsample": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "mb_disc_groupnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint)] + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "mb_disc_pool": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "mb_disc_logits": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_void_p]),
     "mb_taming_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mb_taming_destroy": (None, [C.c_void_p]),
     "mb_taming_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

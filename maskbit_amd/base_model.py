@@ -240,6 +240,12 @@ class PairLoss(BaseModel):
         """which loaders to call first, while weights are missing"""
         raise NotImplementedError
 
+    def note_loaded_keys(self, keys) -> None:
+        """Counts as loaded every part of the network that the state-dict keys ``keys`` (relative to this module) cover completely.  The
+        module's own ``load_state_dict`` calls it; a parent that loaded this module's entries through torch's recursive loader (``VQGANLoss``)
+        calls it with its own keys, stripped of the prefix."""
+        raise NotImplementedError
+
     def _chunk(self, H: int, W: int) -> int:
         return int(self.max_pairs_per_call)
 

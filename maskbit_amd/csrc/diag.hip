@@ -10,6 +10,7 @@
 #include "mb_abi.h"
 #include "mb_autoenc.h"
 #include "mb_conv.h"
+#include "mb_disc.h"
 #include "mb_image.h"
 #include "mb_kernels.h"
 #include "mb_spattn.h"
@@ -670,6 +671,64 @@ int mb_image_coeffs(int in_size, int out_size, int filter, int first, int count,
   if (ksize != mb::image_ksize(in_size, out_size, filter)) return fail(-1, "mb_image_coeffs: ksize %d, the axis has %d", ksize, mb::image_ksize(in_size, out_size, filter));
   mb::image_coeffs_launch(in_size, out_size, filter, first, count, ksize, xmin, n, taps, (hipStream_t)stream);
   return launched();
+}
+
+// ---- the discriminator's kernels (discriminator.hip), each through the launcher the handle calls
+int mb_disc_cols(const float* images, void* cols_h16, int B, int H, int W, int clamp01, mb_stream stream) {
+  if (!images || !cols_h16 || B < 1 || H < 1 || W < 1 || (size_t)B * H * W >= (1u << 30)) return fail(-1, "mb_disc_cols: bad arguments");
+  mb::launch_disc_cols((hipStream_t)stream, images, (h16*)cols_h16, B, H, W, clamp01);
+  return launched();
+}
+int mb_disc_down_chunks(int Ho, int Wo, int C) { return Ho < 1 || Wo < 1 || C < 8 || C % 8 ? -1 : mb::disc_down_chunks(Ho, Wo, C); }
+int mb_disc_downsample(const void* x_h16, void* y_h16, float* part, int B, int H, int W, int C, int K, mb_stream stream) {
+  if (!x_h16 || !y_h16) return fail(-1, "mb_disc_downsample: null argument");
+  if (K != 0 && (K < 3 || K > 5)) return fail(-1, "mb_disc_downsample: K %d: 3, 4, 5, or 0 for the average pool", K);
+  if (B < 1 || B > 65535 || H < 2 || W < 2 || C < 8 || C % 8 || C > 2048 || (size_t)B * H * W >= (1u << 30))
+    return fail(-1, "mb_disc_downsample: [%d, %d, %d, %d]: 1 <= B <= 65535, H and W >= 2, C a multiple of 8 up to 2048", B, H, W, C);
+  if (part && C % 32) return fail(-1, "mb_disc_downsample: the GroupNorm partials need C %% 32 == 0, got %d", C);
+  mb::launch_disc_down((hipStream_t)stream, (const h16*)x_h16, (h16*)y_h16, part, B, H, W, C, K);
+  return launched();
+}
+int mb_disc_groupnorm(void* x_h16, const float* part, int nchunk, const float* gamma, const float* beta, unsigned* saturated, int B, int HW, int C,
+                      float slope, mb_stream stream) {
+  if (!x_h16 || !part || !gamma || !beta) return fail(-1, "mb_disc_groupnorm: null argument");
+  if (B < 1 || B > 65535 || HW < 1 || nchunk < 1 || C < 32 || C % 32 || C > 2048 || !(slope >= 0.f && slope <= 1.f))
+    return fail(-1, "mb_disc_groupnorm: B %d, HW %d, C %d, %d chunks, slope %g: C a multiple of 32 up to 2048, slope in [0, 1]", B, HW, C, nchunk, (double)slope);
+  hipStream_t s = (hipStream_t)stream;
+  mb::DevArena m;
+  float2* ss = nullptr;
+  unsigned* sat = nullptr;
+  m.get(&ss, (size_t)B * C); m.zeroed(&sat, 1);
+  if (int rc = m.failed("mb_disc_groupnorm")) return rc;
+  mb::launch_disc_gn(s, (h16*)x_h16, part, nchunk, gamma, beta, ss, sat, B, HW, C, mb::DISC_GN_EPS, slope);
+  const int rc = launched();
+  unsigned nsat = 0;
+  const bool ok = hipMemcpyAsync(&nsat, sat, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_disc_groupnorm: copy failed");     // the scratch is freed on return
+  if (saturated) *saturated = nsat;
+  return rc;
+}
+int mb_disc_pool(const void* x_h16, void* y_h16, int B, int H, int W, int C, mb_stream stream) {
+  if (!x_h16 || !y_h16) return fail(-1, "mb_disc_pool: null argument");
+  if (B < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || C < 8 || C % 8 || (size_t)B * H * W >= (1u << 30))
+    return fail(-1, "mb_disc_pool: [%d, %d, %d, %d]: C a multiple of 8", B, H, W, C);
+  mb::launch_disc_pool((hipStream_t)stream, (const h16*)x_h16, (h16*)y_h16, B, H, W, C);
+  return launched();
+}
+int mb_disc_logits(const void* x_h16, const float* w_oihw, const float* bias, float* logits, double* stats, double* sum, int B, int C, mb_stream stream) {
+  if (!x_h16 || !w_oihw || !bias) return fail(-1, "mb_disc_logits: null argument");
+  if (B < 1 || B > 65535 || C < 8 || C % 8 || C > (1 << 16)) return fail(-1, "mb_disc_logits: B %d, C %d: C a multiple of 8", B, C);
+  if (sum && !stats) return fail(-1, "mb_disc_logits: the running sum needs the per-image sums");
+  hipStream_t s = (hipStream_t)stream;
+  mb::DevArena m;
+  float* w = nullptr;
+  m.get(&w, (size_t)25 * C);
+  if (int rc = m.failed("mb_disc_logits")) return rc;
+  mb::launch_disc_logits_weight(s, w_oihw, w, C);
+  mb::launch_disc_logits(s, (const h16*)x_h16, w, bias, logits, stats, sum, B, C);
+  const int rc = launched();
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(-10, "mb_disc_logits: synchronise failed");        // the weights are freed on return
+  return rc;
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 //   Epilogue: v = fma(acc, scale[c], shift[c]) in fp32 (BatchNorm in evaluation mode, eps 1e-3; the scale stays out of the fp16 weights because
 // the checkpoint's variances span decades), ReLU, fp16 store saturating at 65504 and counted.  Two more epilogues serve ResNet-50's bottlenecks
 // (resnet.hip): linear (no ReLU; saturation on |v|) and residual (relu(v + identity), the identity an fp16 channel slice, the add in fp32).
+// A fourth serves the VQGAN+ discriminator (discriminator.hip): LeakyReLU with the slope as an argument (scale = 1, shift = the bias).
 // The epilogue is a template parameter: the ReLU form's instructions are what they were.
 //
 // Two instantiations: <4, 4> (64 pixels x 64 channels a wave: 16 MFMAs per 8 fragment loads) from 512 such tiles up, else <2, 2> (the 8 x 8 maps,
@@ -140,7 +141,14 @@ __global__ __launch_bounds__(IC_THREADS) void convbn_kernel(ConvBnArgs a) {
             v[0] = fmaf(acc[i][j][0], sc.x, sh.x); v[1] = fmaf(acc[i][j][1], sc.y, sh.y);
             v[2] = fmaf(acc[i][j][2], sc.z, sh.z); v[3] = fmaf(acc[i][j][3], sc.w, sh.w);
             nsat += fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) > MB_H16_MAX ? 1u : 0u;
-          } else {                                                 // the end of a bottleneck: + identity in fp32, ReLU, one rounding
+          } else if constexpr (EPI == CONVBN_LEAKY) {              // the discriminator's LeakyReLU: v or v * slope, saturation on |v|
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float t = fmaf(acc[i][j][e], e == 0 ? sc.x : e == 1 ? sc.y : e == 2 ? sc.z : sc.w, e == 0 ? sh.x : e == 1 ? sh.y : e == 2 ? sh.z : sh.w);
+              v[e] = t >= 0.f ? t : __fmul_rn(t, q.slope);
+            }
+            nsat += fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) > MB_H16_MAX ? 1u : 0u;
+          } else {                                             // the end of a bottleneck: + identity in fp32, ReLU, one rounding
             const h16x4 id = *(const h16x4*)(q.idn + (size_t)p * q.idn_cs + q.idn_off + nl);
             v[0] = fmaxf(__fadd_rn(fmaf(acc[i][j][0], sc.x, sh.x), (float)id[0]), 0.f);
             v[1] = fmaxf(__fadd_rn(fmaf(acc[i][j][1], sc.y, sh.y), (float)id[1]), 0.f);
@@ -303,7 +311,8 @@ const char* convbn_refusal(const ConvBn& q) {
   if (q.H + 2 * q.ph < q.kh || q.W + 2 * q.pw < q.kw) return "the image is smaller than the kernel";
   if (q.in_off < 0 || q.in_off % 8 || q.in_cs % 8 || q.in_off + (q.cin + 7) / 8 * 8 > q.in_cs)
     return "input slice: offset and stride must be multiples of 8 channels and hold Cin rounded up to 8";
-  if (q.epi < CONVBN_RELU || q.epi > CONVBN_RESIDUAL) return "epilogue must be 0 (ReLU), 1 (linear) or 2 (residual + ReLU)";
+  if (q.epi < CONVBN_RELU || q.epi > CONVBN_LEAKY) return "epilogue must be 0 (ReLU), 1 (linear), 2 (residual + ReLU) or 3 (LeakyReLU)";
+  if (q.epi == CONVBN_LEAKY && !(q.slope >= 0.f && q.slope <= 1.f)) return "LeakyReLU: the slope must be in [0, 1]";
   if (q.epi == CONVBN_RESIDUAL && (!q.idn || q.idn_off < 0 || q.idn_off % 4 || q.idn_cs % 4 || q.idn_off + q.cout > q.idn_cs))
     return "identity slice: a pointer, and offset and stride multiples of 4 channels that hold Cout";
   if (q.cout % 4 || q.out_off < 0 || q.out_off % 4 || q.out_cs % 4 || q.out_off + q.cout > q.out_cs)
@@ -331,12 +340,14 @@ void launch_convbn(hipStream_t s, const ConvBn& q, int variant) {
     const dim3 grid((a.ntiles + 3) / 4), block(IC_THREADS);
     if (q.epi == CONVBN_RELU) hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_RELU>), grid, block, 0, s, a);
     else if (q.epi == CONVBN_LINEAR) hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_LINEAR>), grid, block, 0, s, a);
+    else if (q.epi == CONVBN_LEAKY) hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_LEAKY>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((convbn_kernel<4, 4, CONVBN_RESIDUAL>), grid, block, 0, s, a);
   } else {
     a.ntn = a.cout_pad / 32; a.ntiles = ((a.M + 31) / 32) * a.ntn;
     const dim3 grid((a.ntiles + 3) / 4), block(IC_THREADS);
     if (q.epi == CONVBN_RELU) hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_RELU>), grid, block, 0, s, a);
     else if (q.epi == CONVBN_LINEAR) hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_LINEAR>), grid, block, 0, s, a);
+    else if (q.epi == CONVBN_LEAKY) hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_LEAKY>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((convbn_kernel<2, 2, CONVBN_RESIDUAL>), grid, block, 0, s, a);
   }
 }
@@ -621,13 +632,13 @@ int mb_inception_saturation_count(mb_inception* h, unsigned* count, int reset, m
 }
 
 // ---- diagnostic entries (include/maskbit_hip_diag.h) ----
-int mb_convbn_layer_ex(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
-                       int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
-                       int epilogue, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream) {
+int mb_convbn_layer_leaky(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B,
+                          int H, int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs,
+                          int variant, int epilogue, float slope, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!w_oihw || variant < 0 || variant > 2) return fail(-1, "mb_convbn_layer: bad arguments");
   ConvBn q{(const h16*)in_h16, nullptr, scale, shift, (h16*)out_h16, nullptr, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, in_off, in_cs, out_off, out_cs,
-           epilogue, (const h16*)identity_h16, idn_off, idn_cs};
+           epilogue, slope, (const h16*)identity_h16, idn_off, idn_cs};
   if (const char* why = convbn_refusal(q)) return fail(-1, "mb_convbn_layer: %s", why);
   DevArena m;
   h16* w = nullptr;
@@ -643,6 +654,15 @@ int mb_convbn_layer_ex(const void* in_h16, const float* w_oihw, const float* sca
   if (hipStreamSynchronize(s) != hipSuccess || !ok) return fail(-10, "mb_convbn_layer: copy failed");
   if (saturated) *saturated = nsat;
   return rc;
+}
+
+// the three epilogues of the feature networks; the LeakyReLU one (3) is mb_convbn_layer_leaky's
+int mb_convbn_layer_ex(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,
+                       int W, int Cin, int Cout, int kh, int kw, int stride, int ph, int pw, int in_off, int in_cs, int out_off, int out_cs, int variant,
+                       int epilogue, const void* identity_h16, int idn_off, int idn_cs, mb_stream stream) {
+  if (epilogue < CONVBN_RELU || epilogue > CONVBN_RESIDUAL) return fail(-1, "mb_convbn_layer: epilogue must be 0 (ReLU), 1 (linear) or 2 (residual + ReLU)");
+  return mb_convbn_layer_leaky(in_h16, w_oihw, scale, shift, out_h16, saturated, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, in_off, in_cs, out_off, out_cs,
+                               variant, epilogue, 0.f, identity_h16, idn_off, idn_cs, stream);
 }
 
 int mb_convbn_layer(const void* in_h16, const float* w_oihw, const float* scale, const float* shift, void* out_h16, unsigned* saturated, int B, int H,

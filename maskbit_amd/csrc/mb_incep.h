@@ -24,7 +24,8 @@ constexpr float IC_BN_EPS = 1e-3f;        // Inception's BatchNorm epsilon (ResN
 // the epilogues of the convolution, v = fma(acc, scale, shift) in fp32:
 enum { CONVBN_RELU = 0,                   // fp16(relu(v)): BasicConv2d, and the first two convolutions of a bottleneck
        CONVBN_LINEAR = 1,                 // fp16(v): a bottleneck's downsample branch; saturation is counted on |v|
-       CONVBN_RESIDUAL = 2 };             // fp16(relu(v + float(identity[p][c]))): the add in fp32, one rounding
+       CONVBN_RESIDUAL = 2,               // fp16(relu(v + float(identity[p][c]))): the add in fp32, one rounding
+       CONVBN_LEAKY = 3 };                // fp16(v >= 0 ? v : v * slope): the discriminator's LeakyReLU; saturation on |v|
 
 // One BasicConv2d: out = fp16(relu(scale * conv(in, w) + shift)), see include/maskbit_hip_diag.h mb_convbn_layer for the geometry taken
 struct ConvBn {
@@ -33,6 +34,7 @@ struct ConvBn {
   int kh, kw, stride, ph, pw;
   int in_off, in_cs, out_off, out_cs;
   int epi = CONVBN_RELU;
+  float slope = 0.f;                      // CONVBN_LEAKY: the negative slope (in what was the padding in front of idn: no other member moves)
   const h16* idn = nullptr;               // CONVBN_RESIDUAL: channels [idn_off, idn_off + cout) of fp16 [B, Ho, Wo, idn_cs]
   int idn_off = 0, idn_cs = 0;
 };

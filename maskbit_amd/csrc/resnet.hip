@@ -275,7 +275,7 @@ const h16* run_trunk(mb_resnet* h, const h16* img, int N, int S, const RnOut& o,
         idn = h->buf[RN_D];
       }
       launch_convbn(s, ConvBn{h->buf[RN_T2], c3.w, c3.scale, c3.shift, h->buf[yi], h->cn.sat, N, ho, ho, width, cout, 1, 1, 1, 0, 0, 0, width, 0, cout,
-                              CONVBN_RESIDUAL, idn, 0, cout});
+                              CONVBN_RESIDUAL, 0.f, idn, 0, cout});
       ci += b == 0 ? 4 : 3;
       xi = yi; hw = ho; cin = cout;
     }

@@ -75,6 +75,9 @@ class TokenizerEvaluator:
         self.last_per_image: Optional[torch.Tensor] = None
         # the attached pair losses in the order of result(): the result key, the model (None: detached), the float64 device sum, the last batch's [B] values
         self._pair_losses = [SimpleNamespace(key=key, model=None, sum=None, last=None) for key in ("LPIPS", "PerceptualLoss")]
+        self._disc = None                                                                     # use_discriminator(): the model, its loss kind, float64 [2, 5] sums
+        self._disc_loss = "hinge"
+        self._disc_sums: Optional[torch.Tensor] = None
         self._inception = None                                                                # use_inception(): the extractor and its three states
         self._rfid = self._inception_score = False
         self._is_stats = self._rfid_real = self._rfid_fake = None
@@ -103,6 +106,8 @@ class TokenizerEvaluator:
         for stats in (self._is_stats, self._rfid_real, self._rfid_fake):
             if stats is not None:
                 stats.reset()
+        if self._disc_sums is not None:
+            self._disc_sums.zero_()
 
     def use_inception(self, extractor, rfid: bool = True, inception_score: bool = True) -> None:
         """Attaches a feature extractor with the contract of the reference's ``get_inception_model()`` -- uint8 [B, 3, H, W] in,
@@ -139,6 +144,29 @@ class TokenizerEvaluator:
         ``reset_metrics()``."""
         from .perceptual import PerceptualLoss
         self._use_pair_loss(self._pair_losses[1], model, PerceptualLoss, "use_perceptual")
+
+    def use_discriminator(self, model, loss: str = "hinge") -> None:
+        """Attaches a loaded ``maskbit_amd.NLayerDiscriminatorv2`` on the evaluator's device (``None`` detaches): ``update()`` then also adds the
+        five logit sums (``NLayerDiscriminatorv2.logit_stats``) of the real and of the fake batch to float64 device sums, without a
+        synchronisation, and ``result()`` reports ``"LogitsReal"`` and ``"LogitsFake"`` (the mean logit), ``"DiscriminatorLoss"`` and
+        ``"GeneratorLoss"`` of the kind ``loss`` (``"hinge"``, ``"vanilla"``, ``"non-saturating"``: the ``discriminator_loss`` of the training
+        config) over all logits counted -- what the training step logs as ``logits_real``, ``logits_fake``, ``discriminator_loss`` (without
+        the LeCam term) and ``gan_loss``, on held-out images.  The reference's evaluator has no such entries; the keys are there only while a
+        model is attached.  Attach before the first ``update()`` of a pass, or call ``reset_metrics()``."""
+        from .discriminator import D_LOSSES, NLayerDiscriminatorv2
+        if model is None:
+            self._disc = None
+            return
+        if not isinstance(model, NLayerDiscriminatorv2):
+            raise TypeError(f"use_discriminator() takes a maskbit_amd.NLayerDiscriminatorv2, got {type(model).__name__}")
+        if loss not in D_LOSSES:
+            raise ValueError(f"use_discriminator(): loss {loss!r}: one of {sorted(D_LOSSES)}")
+        dev = model._require_cuda("use_discriminator")
+        if (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device.index:
+            raise ValueError(f"the NLayerDiscriminatorv2 model is on {dev}, the evaluator on {self._device}")
+        self._disc, self._disc_loss = model, loss
+        if self._disc_sums is None:
+            self._disc_sums = torch.zeros((2, 5), dtype=torch.float64, device=self._device)
 
     def _use_pair_loss(self, row, model, cls, who: str) -> None:
         if model is None:
@@ -181,6 +209,8 @@ class TokenizerEvaluator:
         attached = [row for row in self._pair_losses if row.model is not None]
         for row in attached:
             row.model.check_images(tuple(fake_images.shape), tuple(fake_images.shape))         # sizes the engine does not take: ValueError, no device work
+        if self._disc is not None:
+            self._disc.check_images(tuple(fake_images.shape))
         lib = _lib.load()
         need = int(lib.mb_eval_workspace_bytes(B, C, H, W)) if self._metrics else 0
         if self._metrics and need == 0:
@@ -213,6 +243,9 @@ class TokenizerEvaluator:
                     self._rfid_fake.add(pool_fake)
             for row in attached:                                                                # evaluator.py:366-368
                 row.last = row.model._run(real_images.reshape(fake_images.shape), fake_images, clamp, row.sum)
+            if self._disc is not None:
+                self._disc.logit_stats(real_images.reshape(fake_images.shape), clamp, self._disc_sums[0])
+                self._disc.logit_stats(fake_images, clamp, self._disc_sums[1])
             if self._codebook:
                 idx = codebook_indices.to(device=self._device, dtype=torch.int64).contiguous()
                 _lib.check(lib.mb_eval_codebook(idx.data_ptr(), idx.numel(), self._num_codebook_entries, self._hist.data_ptr(),
@@ -241,6 +274,9 @@ class TokenizerEvaluator:
         if self._rfid:
             for stats in (self._rfid_real, self._rfid_fake):
                 parts += [stats.total, stats.full_sigma().reshape(-1)]
+        at_disc = sum(int(p.numel()) for p in parts)                                           # where the discriminator's sums begin
+        if self._disc is not None:
+            parts.append(self._disc_sums.reshape(-1))
         host = torch.cat(parts).cpu()                                                           # the one copy
         if self._codebook and host[cb + 1] != 0:
             raise IndexError(f"{int(host[cb + 1])} codebook indices outside [0, {self._num_codebook_entries})")
@@ -264,6 +300,13 @@ class TokenizerEvaluator:
             eval_score["rFID"] = frechet_distance(t_real / n, get_covariance(s_real, t_real, n), t_fake / n, get_covariance(s_fake, t_fake, n))
         for i, row in enumerate(attached):
             eval_score[row.key] = host[4 + i].item() / n                                        # evaluator.py:453-455
+        if self._disc is not None:
+            from .discriminator import D_LOSSES, G_LOSSES, logits_mean
+            stats = host[at_disc:at_disc + 10].reshape(2, 5) / n                                  # the sums of the average image
+            real, fake = stats[0:1], stats[1:2]
+            eval_score["LogitsReal"], eval_score["LogitsFake"] = logits_mean(real).item(), logits_mean(fake).item()
+            eval_score["DiscriminatorLoss"] = D_LOSSES[self._disc_loss](real, fake).item()
+            eval_score["GeneratorLoss"] = G_LOSSES[self._disc_loss](fake).item()
         if self._enable_codebook_usage_measure:
             eval_score["CodebookUsage"] = float(int(host[cb])) / self._num_codebook_entries
         if self._enable_codebook_entropy_measure:

@@ -72,10 +72,13 @@ class LPIPS(PairLoss):
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         res = super().load_state_dict(state_dict, strict=strict, **kw)
-        keys = set(state_dict)
+        self.note_loaded_keys(state_dict)
+        return res
+
+    def note_loaded_keys(self, keys) -> None:
+        keys = set(keys)
         self._vgg_loaded = self._vgg_loaded or all(k in keys for k in vgg16_keys())
         self._lin_loaded = self._lin_loaded or all(k in keys for k in self.lin_keys())
-        return res
 
     def load_vgg16(self, path_or_state_dict: StateLike) -> None:
         """The thirteen convolutions from a checkpoint path or state dict in the reference layout (``net.sliceK.N.*``), torchvision's

@@ -79,9 +79,12 @@ class PerceptualLoss(PairLoss):
     # ---- weights ------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         res = super().load_state_dict(state_dict, strict=strict, **kw)
-        keys = set(state_dict)
-        self._loaded = self._loaded or all("model." + k in keys for k in resnet50_keys(counters=False))
+        self.note_loaded_keys(state_dict)
         return res
+
+    def note_loaded_keys(self, keys) -> None:
+        keys = set(keys)
+        self._loaded = self._loaded or all("model." + k in keys for k in resnet50_keys(counters=False))
 
     def load_resnet50(self, path_or_state_dict: StateLike) -> None:
         """The network from a checkpoint path or a state dict in torchvision's layout (``conv1.weight``, ...) or the reference's

@@ -568,3 +568,39 @@ def make_resnet50_weights(seed: int) -> StateDict:
     sd["fc.weight"] = torch.randn(n, d, generator=g) / math.sqrt(d)
     sd["fc.bias"] = torch.randn(n, generator=g) * 0.1
     return sd
+
+
+DISC_LOGIT_GAIN = 1.5
+
+
+def make_discriminator_weights(seed: int, hidden_channels: int = 128, num_stages: int = 3, blur_kernel_size: int = 4) -> StateDict:
+    """Seeded weights of the reference's ``NLayerDiscriminatorv2`` under its own keys (``blur_kernel_size`` 3, 4, 5: with the
+    ``blocks.{i}.1.kernel`` buffers of ``blur_resample=True``; 0: the average-pool variant, without).  No trained discriminator is available
+    here; these stand in for one.
+
+    He-normal convolutions (std = sqrt(2 / fan_in)) with N(0, 0.1) biases; GroupNorm gamma in [0.6, 1.4), beta N(0, 0.2) -- neither the unit
+    nor the zero of a fresh module; ``to_logits.2``: N(0, DISC_LOGIT_GAIN / sqrt(fan_in)) weights and a bias of 0.1, which spreads the logits of
+    uniform-noise images over roughly +-2: a hinge sum has terms on both sides of its kink, and nothing comes near the fp16 range."""
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+
+    def conv(key: str, cout: int, cin: int, k: int, gain: float = math.sqrt(2.0)) -> None:
+        sd[key + ".weight"] = torch.randn(cout, cin, k, k, generator=g) * (gain / math.sqrt(cin * k * k))
+        sd[key + ".bias"] = torch.randn(cout, generator=g) * 0.1
+
+    conv("block_in.0", hidden_channels, 3, 5)
+    cin = hidden_channels
+    for i in range(num_stages):
+        cout = hidden_channels << i
+        conv(f"blocks.{i}.0", cout, cin, 3)
+        if blur_kernel_size:
+            row = torch.tensor({3: (1, 2, 1), 4: (1, 3, 3, 1), 5: (1, 4, 6, 4, 1)}[blur_kernel_size], dtype=torch.float32)
+            k2 = row[None, :] * row[:, None]
+            sd[f"blocks.{i}.1.kernel"] = (k2 / k2.sum())[None, None]
+        sd[f"blocks.{i}.2.weight"] = 0.6 + 0.8 * torch.rand(cout, generator=g)
+        sd[f"blocks.{i}.2.bias"] = torch.randn(cout, generator=g) * 0.2
+        cin = cout
+    conv("to_logits.0", cin, cin, 1)
+    conv("to_logits.2", 1, cin, 5, gain=DISC_LOGIT_GAIN)
+    sd["to_logits.2.bias"] = torch.full((1,), 0.1)
+    return sd
