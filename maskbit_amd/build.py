@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmaskbit_hip.so")
-SOURCES = ["engine.hip", "diag.hip", "gemm.hip", "gemm_ht.hip", "gemm_f32.hip", "norm_embed.hip", "attention.hip", "sampling.hip", "edit.hip", "session.hip", "conv.hip", "decoder.hip", "vq.hip", "evaluator.hip", "mlm.hip", "lpips.hip", "fid.hip", "manifold.hip", "image.hip", "inception.hip", "resnet.hip", "discriminator.hip", "spatial_attention.hip", "taming.hip"]
+SOURCES = ["engine.hip", "sampler.hip", "diag.hip", "gemm.hip", "gemm_ht.hip", "gemm_f32.hip", "norm_embed.hip", "attention.hip", "sampling.hip", "edit.hip", "session.hip", "conv.hip", "decoder.hip", "vq.hip", "evaluator.hip", "mlm.hip", "lpips.hip", "fid.hip", "manifold.hip", "image.hip", "inception.hip", "resnet.hip", "discriminator.hip", "spatial_attention.hip", "taming.hip"]
 
 
 def hipcc() -> str:

@@ -1,7 +1,7 @@
 // Diagnostic entry points (include/maskbit_hip_diag.h): single kernels and single layers on caller buffers, for the tests and the tools.
 // No host binding of the product needs them.  Argument checks, a scratch arena (mb::DevArena) where a layer needs one, and the launchers' own calls
 // only: this file holds no kernel of its own (mb_autoenc.h brings the loader's affine_kernel along for mb_autoenc_block).
-// (mb_gen_set_alo, the one entry of that header that needs the generator handle's members, is in engine.hip.)
+// (mb_gen_set_alo and mb_gen_set_walk, the entries that set a member of the generator handle, see it through mb_gen.h.)
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -11,6 +11,7 @@
 #include "mb_autoenc.h"
 #include "mb_conv.h"
 #include "mb_disc.h"
+#include "mb_gen.h"
 #include "mb_image.h"
 #include "mb_kernels.h"
 #include "mb_spattn.h"
@@ -118,6 +119,21 @@ int embed_weight(const char* who, mb::DevArena& arena, mb::EmbedArgs& e, const f
 extern "C" {
 
 int mb_set_cu_count(int n) { mb::set_cu_count(n); return 0; }
+
+// the two study knobs of the generator handle (mb_gen.h: alo_mask, walk)
+int mb_gen_set_alo(mb_gen* g, int gemm_mask) {
+  if (!g || gemm_mask < 0 || gemm_mask > 15) return fail(-1, "mb_gen_set_alo: mask outside [0, 15]");
+  if (gemm_mask & ~g->alo_mask_built)
+    return fail(-1, "mb_gen_set_alo: the handle was created (precision %d) with the activation-lo operands of GEMM mask %d only", g->c.precision, g->alo_mask_built);
+  g->alo_mask = gemm_mask;
+  return 0;
+}
+int mb_gen_set_walk(mb_gen* g, int mode) {
+  if (!g || (mode != 0 && mode != 1)) return fail(-1, "mb_gen_set_walk: mode 0 (every launch front to back) or 1 (alternating)");
+  g->walk = mode;
+  return 0;
+}
+
 int mb_diag_set_walk(int reverse) {
   if (reverse != 0 && reverse != 1) return fail(-1, "mb_diag_set_walk: direction 0 or 1");
   g_walk_reverse = reverse;

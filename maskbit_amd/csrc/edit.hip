@@ -1,5 +1,5 @@
 // Image editing with the masked-token sampler (inpainting, outpainting, regenerating a region under another label): the helpers in front of and
-// behind a sampling run that starts from a partly known token map (mb_sample_edit, engine.hip; the per-sample threshold rule is the <true> form of
+// behind a sampling run that starts from a partly known token map (mb_sample_edit, sampler.hip; the per-sample threshold rule is the <true> form of
 // sample_thresh_kernel, sampling.hip).  The reference has no counterpart: its sample() always starts from the all-masked state (sampling.py:65-71).
 //   edit_token_mask_kernel -- pixel mask -> token mask: a token is regenerated if any pixel of its stride x stride block is.
 //   edit_init_kernel       -- the encoder's codes + the token mask -> grouped tokens with the mask token at the slots to regenerate, and their count.

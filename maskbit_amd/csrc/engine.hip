@@ -1,105 +1,20 @@
-// The generator handle of libmaskbit_hip.so (include/maskbit_hip.h): checkpoint ingest with h16 repack, the two forward schedules (plain and
-// differential CFG), the fused sampling step and the whole sampling loop; and the three ABI-wide entries (mb_abi_version, mb_last_error, mb_prof_*).
-// The tokenizer handle's entry points are in decoder.hip, the diagnostic ones (include/maskbit_hip_diag.h) in diag.hip -- all but mb_gen_set_alo,
-// which needs struct mb_gen; the error path, the device-allocation arena and the profiling scopes they all share are in mb_abi.h.
+// The generator handle of libmaskbit_hip.so (include/maskbit_hip.h; its members: mb_gen.h): create, checkpoint ingest with h16 repack, the three forward
+// schedules (plain, differential CFG, fp32 reference) behind gen_forward / gen_forward_cfg; and the three ABI-wide entries (mb_abi_version, mb_last_error,
+// mb_prof_*).  What samples with the handle -- the step entries, the whole-run loops, the session -- is in sampler.hip, the tokenizer handle's entry points in
+// decoder.hip, the diagnostic ones (include/maskbit_hip_diag.h) in diag.hip; the error path, the device-allocation arena and the profiling scopes they all share are in mb_abi.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/maskbit_hip_diag.h"
-#include "mb_abi.h"
-#include "mb_kernels.h"
+#include "mb_gen.h"
 
 using mb::fail;
 using mb::g_prof;
 using mb::launched;
 using mb::ProfScope;
-
-// ================================================================================================
-// generator
-// ================================================================================================
-// An e2m1 (MX-fp4) copy of an activation: values at the row stride of the fp16 sibling (2 * width bytes, the first width / 2 used) and their
-// block-scale bytes in lane order, [width / 64][sequences][256]
-struct F4Buf { uint8_t *v = nullptr, *s = nullptr; };
-
-struct mb_gen {
-  mb_gen_cfg c{};
-  int max_seqs = 0, chunk_seqs = 0, N = 0, C = 0, gbits = 0, device = 0;   // chunk_seqs: sequences per forward pass (workspace size)
-  struct Layer {
-    h16 *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
-    float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
-    float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-  };
-  std::vector<Layer> layers;
-  float *w_in = nullptr, *b_in = nullptr, *class_emb = nullptr, *pos = nullptr, *ln0g = nullptr, *ln0b = nullptr;
-  h16 *wl = nullptr, *wp = nullptr;
-  float *bl = nullptr, *lnhg = nullptr, *lnhb = nullptr, *bp = nullptr;
-  float *lnag = nullptr, *lnab = nullptr;              // norm_after_transformer (pre-norm variant)
-  float *tables = nullptr, *bias_pos = nullptr;       // Bert: embedding tables [m][C+1][d]; output bias [seq][m*C]
-  unsigned* split_tmp = nullptr;                        // scratch of the head weights' hi / lo split
-  // workspace
-  float *y_f32 = nullptr, *ln_stats = nullptr;       // fp32 residual stream (pre-LayerNorm rows) and {mean, rstd} per row
-  h16 *x_h16 = nullptr, *x_lo = nullptr, *qkv = nullptr, *att = nullptr, *h = nullptr;   // x_lo: lo halves of x_h16 (head GEMMs; precision >= 1: QKV / FFN-up of plain forwards)
-  // precision >= 1: differential CFG forward (pair_ok = the shape allows it).  precision >= 2 (mini_ok = the shape allows it): every trunk GEMM carries the
-  // MX-fp4 weight-correction mini-tiles (gemm_ht.hip, XP = 6) -- in the guided forward on the conditional rows, in the plain forward (257-token sequences)
-  // on every row: x4 / att4 / h4 hold e2m1 of the LayerNorm outputs, attention outputs and FFN hiddens,
-  // w4lo / w4los e2m1 of the weights' fp16 rounding errors.  precision 3 additionally corrects the fp16 rounding of the LayerNorm OUTPUTS
-  // in the guided forward's FFN-up GEMM: xl4 = e2m1 of their lo halves, w4 / w4s = e2m1 of the (fp16) weight net.0.
-  bool pair_ok = false, mini_ok = false;
-  F4Buf x4, xl4;
-  std::vector<uint8_t*> w4, w4s;                                                         // [4 * layer + {qkv, o, 1, 2}]: the GEMMs of alo_mask_built only
-  float* logits_tmp = nullptr;                          // guided forwards over more pairs than one pass holds
-  // The two head GEMMs run hi + lo inputs against hi + lo WEIGHTS in every mode (GemmArgs.W2: three sweeps): their rounding reaches the logits
-  // un-averaged -- fp16 head weights alone were a quarter of the sampled-logit error variance left after the trunk's weight correction
-  // (tests/diag/error_budget.py) -- and the two GEMMs are 0.4 % of a forward.  wl / wp = fp16(w 2^S), wl_lo / wp_lo = the remainders, head_scale = 2^-S.
-  // (Bert's tied head, embed_tables: wp holds the tables' first C rows per group as single fp16, no lo plane.)
-  h16 *wl_lo = nullptr, *wp_lo = nullptr;
-  float* head_scale = nullptr;
-  unsigned* sat = nullptr;                              // lanes of the QKV / FFN-up epilogues that clamped a fp16 store (mb_gen_saturation_count)
-  std::vector<uint8_t*> w4lo, w4los;                                                     // [4 * layer + {qkv, o, 1, 2}]
-  F4Buf att4, h4;                                       // e2m1 of the conditional attention outputs / FFN hiddens
-  F4Buf attl4, hl4;                                     // precision 4: e2m1 of their fp16 LO HALVES (activation-lo sets of out-proj / FFN-down)
-  // The run the sampling loop is in the middle of (step chunks).  id = what every chunk of one run shares: samples, total steps, guidance flag and
-  // kind -- 0 plain, 1 an EDIT run (mb_sample_edit: started from the caller's tokens; num_regen = its initial masked count per sample, [max_seqs]),
-  // 2 a SEEDED run (mb_sample_seeded: an edit run whose steps generate their noise); next = the step the next chunk must begin with (-1: no run).
-  // cfg_labels / cfg_B: during one call of the loop, gen_forward_cfg's lab_cfg / drop_cfg already hold [labels | labels] / [0 | 1] for this many pairs.
-  struct Run {
-    struct Id {
-      int B = 0, steps = 0, guided = 0, kind = 0;
-      bool operator==(const Id& o) const { return B == o.B && steps == o.steps && guided == o.guided && kind == o.kind; }
-    } id;
-    int next = -1;
-    const int64_t* cfg_labels = nullptr;
-    int cfg_B = 0;
-  } run;
-  int* num_regen = nullptr;
-  // precision >= 3: which GEMMs carry the activation-lo set (1 QKV, 2 out-proj, 4 FFN-up, 8 FFN-down).  Coverage measured on the reference's own runs in round 6
-  // (profiles/r06_coverage.md: four 14-bit / 256-step runs, four 12-bit runs, three trained-like runs; mismatches / guided-forward time of 64 pairs):
-  //   none 595 / 263 / 271 at 29.9 ms;  FFN-up of layers >= depth / 2 (round 5's precision 3) 506 / 222 / 276 at 30.5;  out-proj + FFN-up 384 / 186 / 219 at 31.6;
-  //   out-proj + FFN-up + FFN-down 241 / 115 / 203 at 33.4;  all four 228 / 116 / 200 at 34.3 -- the QKV set buys nothing (as round 5 found for precision 3).
-  // precision 3 = out-proj + FFN-up of every layer (6); precision 4 = + FFN-down (14).  mb_gen_set_alo (diagnostic) narrows within what the handle was created with.
-  int alo_mask = 0, alo_mask_built = 0;
-  // Walk order of the trunk launches (mb_kernels.h walk_tile / walk_seq): 1 = every launch of a forward walks the batch opposite to the launch in front of
-  // it, so that it starts on what its producer wrote last (the product); 0 = every launch front to back (mb_gen_set_walk, diagnostic: the A/B of the two)
-  int walk = 1;
-  // precision MB_PREC_F32, the fp32 reference mode (gemm_f32.hip): the GEMM weights stay the checkpoint's fp32 (layers32, wl32, wp32 -- Bert's tied
-  // head: the tables' first C rows per group), the workspace is fp32 only -- x_f32 = the LayerNorm output rows (GEMM operand AND residual), y_f32 = the
-  // pre-LayerNorm sum, qkv32 / att32 / h32 -- and none of the fp16 / e2m1 buffers above exist.  Every forward of such a handle is gen_forward_f32_impl.
-  bool f32 = false;
-  struct Layer32 { float *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr; };
-  std::vector<Layer32> layers32;
-  float *wl32 = nullptr, *wp32 = nullptr;
-  float *x_f32 = nullptr, *qkv32 = nullptr, *att32 = nullptr, *h32 = nullptr;
-  int64_t *tok_a = nullptr, *tok_b = nullptr, *tok_cfg = nullptr, *lab_cfg = nullptr, *pred = nullptr, *codes = nullptr;
-  uint8_t* drop_cfg = nullptr;
-  float* logits = nullptr;
-  mb::DevArena mem;
-  int loaded = 0;
-};
 
 namespace {
 
@@ -389,10 +304,13 @@ int gen_forward_pass(mb_gen* g, const int64_t* tokens, const int64_t* labels, co
   return gen_forward_impl(g, tokens, labels, drop, logits, nb, s, attn);
 }
 
+}  // namespace
+
+namespace mb {   // (declared in mb_gen.h: sampler.hip calls the two)
+
 // The kernels index with 32-bit element / byte offsets (rows * mlp * 4 < 2^32): forwards over more sequences than that allows run as
 // independent chunks (sequences never interact), which also bounds the workspace of very large batches.
-int gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, int nb, hipStream_t s,
-                float* attn = nullptr) {
+int gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, int nb, hipStream_t s, float* attn) {
   const int chunk = g->chunk_seqs;
   g_prof.begin_forward(true);
   if (nb <= chunk) return gen_forward_pass(g, tokens, labels, drop, logits, nb, s, attn);
@@ -419,7 +337,7 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
     // (the fused pair embedding reads the conditional tokens only: the twins' copy is needed by the two-kernel path and the plain fallback)
     if (!(pair && !g->c.embed_tables && g->c.bits <= 24))
       HIP_TRY(hipMemcpyAsync(g->tok_cfg + nc * P, tokens + (size_t)b0 * P, nc * P * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (!(nc == B && g->run.cfg_labels == labels && g->run.cfg_B == B)) {       // (the sampling loop marks them ready for the steps of one call)
+    if (!(nc == B && g->run.cfg_labels == labels && g->run.cfg_B == B)) {       // (the ready mark: sampler.hip forward_and_step sets it and states its contract)
       g->run.cfg_labels = nullptr;                      // whatever they were marked ready for is overwritten: a session's mark outlives its call
       HIP_TRY(hipMemcpyAsync(g->lab_cfg, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemcpyAsync(g->lab_cfg + nc, labels + b0, nc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
@@ -439,7 +357,7 @@ int gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, flo
   return 0;
 }
 
-}  // namespace
+}  // namespace mb
 
 extern "C" {
 
@@ -653,20 +571,6 @@ int mb_gen_load(mb_gen* g, const char* name, const float* data, const int64_t* s
   return 0;
 }
 
-int mb_gen_set_alo(mb_gen* g, int gemm_mask) {
-  if (!g || gemm_mask < 0 || gemm_mask > 15) return fail(-1, "mb_gen_set_alo: mask outside [0, 15]");
-  if (gemm_mask & ~g->alo_mask_built)
-    return fail(-1, "mb_gen_set_alo: the handle was created (precision %d) with the activation-lo operands of GEMM mask %d only", g->c.precision, g->alo_mask_built);
-  g->alo_mask = gemm_mask;
-  return 0;
-}
-
-int mb_gen_set_walk(mb_gen* g, int mode) {
-  if (!g || (mode != 0 && mode != 1)) return fail(-1, "mb_gen_set_walk: mode 0 (every launch front to back) or 1 (alternating)");
-  g->walk = mode;
-  return 0;
-}
-
 int mb_gen_saturation_count(mb_gen* g, unsigned* count, int reset, mb_stream stream) {
   if (!g || !count) return fail(-1, "mb_gen_saturation_count: null argument");
   return mb::read_counter("mb_gen_saturation_count", g->sat, count, reset, (hipStream_t)stream);
@@ -676,13 +580,13 @@ int mb_gen_forward(mb_gen* g, const int64_t* tokens, const int64_t* labels, cons
                    int nb, mb_stream stream) {
   if (!g || !tokens || !labels || !logits) return fail(-1, "mb_gen_forward: null argument");
   if (nb <= 0 || nb > g->max_seqs) return fail(-1, "mb_gen_forward: nb=%d outside [1, %d]", nb, g->max_seqs);
-  return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream);
+  return mb::gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream);
 }
 
 int mb_gen_forward_cfg(mb_gen* g, const int64_t* tokens, const int64_t* labels, float* logits, int B, mb_stream stream) {
   if (!g || !tokens || !labels || !logits) return fail(-1, "mb_gen_forward_cfg: null argument");
   if (B <= 0 || 2 * B > g->max_seqs) return fail(-1, "mb_gen_forward_cfg: B=%d needs %d sequences, engine holds %d", B, 2 * B, g->max_seqs);
-  return gen_forward_cfg(g, tokens, labels, logits, B, (hipStream_t)stream);
+  return mb::gen_forward_cfg(g, tokens, labels, logits, B, (hipStream_t)stream);
 }
 
 int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels, const uint8_t* drop, float* logits, float* attn,
@@ -690,477 +594,7 @@ int mb_gen_forward_attn(mb_gen* g, const int64_t* tokens, const int64_t* labels,
   if (!g || !tokens || !labels || !logits || !attn) return fail(-1, "mb_gen_forward_attn: null argument");
   if (nb <= 0 || nb > g->max_seqs) return fail(-1, "mb_gen_forward_attn: nb=%d outside [1, %d]", nb, g->max_seqs);
   if (g->f32) return fail(-3, "mb_gen_forward_attn: attention maps are not available in the fp32 reference mode (precision %d)", (int)MB_PREC_F32);
-  return gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
-}
-
-// One step, from the three step entries and from the loop.  who: the entry's name in the messages; num_regen != null: the edit step, which reads
-// mask_ratio instead of a.k_mask_len; a.seeds != null: the seeded step, which generates its noise from (seeds, step, rand_temp, conf_w) instead of
-// reading a.exp_noise / a.conf_noise.  a.tokens is tokens_out, a.pred pred_out, a.P = n m (0: n or m was not positive).
-static int sample_step_checked(const char* who, const mb::StepArgs& a, const int64_t* tokens_in, const int32_t* num_regen, float mask_ratio, hipStream_t s) {
-  if (!a.logits_c || (!a.seeds && (!a.exp_noise || !a.conf_noise)) || !tokens_in || !a.tokens) return fail(-1, "%s: null argument", who);
-  if (tokens_in == a.tokens) return fail(-1, "%s: tokens_in and tokens_out must not alias", who);
-  if (a.B <= 0 || a.P <= 0 || a.C <= 0) return fail(-1, "%s: bad sizes", who);
-  ProfScope p(a.req ? "sample_step_requests" : a.seeds ? "sample_step_seeded" : num_regen ? "sample_step_edit" : "sample_step", s);
-  if (mb::sample_step(s, a, tokens_in, num_regen, mask_ratio)) return fail(-1, "%s: C=%d or n*m=%d too large", who, a.C, a.P);
-  return launched();
-}
-
-static int step_slots(int n, int m) { return n > 0 && m > 0 ? n * m : 0; }
-
-int mb_sample_step(const float* logits_c, const float* logits_u, float scale, float temperature,
-                   const float* exp_noise, const float* conf_noise, int k_mask_len, const int64_t* tokens_in,
-                   int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  mb::StepArgs a{};
-  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
-  a.exp_noise = exp_noise; a.conf_noise = conf_noise; a.k_mask_len = k_mask_len;
-  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
-  return sample_step_checked("mb_sample_step", a, tokens_in, nullptr, 0.f, (hipStream_t)stream);
-}
-
-int mb_sample_step_edit(const float* logits_c, const float* logits_u, float scale, float temperature, const float* exp_noise, const float* conf_noise,
-                        float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m,
-                        int C, mb_stream stream) {
-  if (!num_regen) return fail(-1, "mb_sample_step_edit: null argument");
-  mb::StepArgs a{};
-  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
-  a.exp_noise = exp_noise; a.conf_noise = conf_noise;
-  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
-  return sample_step_checked("mb_sample_step_edit", a, tokens_in, num_regen, mask_ratio, (hipStream_t)stream);
-}
-
-int mb_sample_step_seeded(const float* logits_c, const float* logits_u, float scale, float temperature, const int64_t* seeds, int step,
-                          float randomize_temperature, float conf_weight, float mask_ratio, const int32_t* num_regen, const int64_t* tokens_in,
-                          int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  if (!seeds || !num_regen) return fail(-1, "mb_sample_step_seeded: null argument");
-  if (step < 0) return fail(-1, "mb_sample_step_seeded: step = %d is negative", step);
-  if (pred_out && (pred_out == tokens_out || pred_out == tokens_in)) return fail(-1, "mb_sample_step_seeded: pred_out must not alias tokens_in or tokens_out");
-  mb::StepArgs a{};
-  a.logits_c = logits_c; a.logits_u = logits_u; a.scale = scale; a.temperature = temperature;
-  a.seeds = seeds; a.step = step; a.rand_temp = randomize_temperature; a.conf_w = conf_weight;
-  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
-  return sample_step_checked("mb_sample_step_seeded", a, tokens_in, num_regen, mask_ratio, (hipStream_t)stream);
-}
-
-static_assert(sizeof(mb::RequestStep) == sizeof(mb_request_step) && sizeof(mb_request_step) == 24, "mb_request_step is the kernels' RequestStep");
-
-int mb_sample_step_requests(const float* logits_c, const float* logits_u, const mb_request_step* table_row, const int64_t* seeds, const int32_t* num_regen,
-                            const int64_t* tokens_in, int64_t* tokens_out, int64_t* pred_out, int B, int n, int m, int C, mb_stream stream) {
-  if (!table_row || !seeds || !num_regen) return fail(-1, "mb_sample_step_requests: null argument");
-  if (pred_out && (pred_out == tokens_out || pred_out == tokens_in)) return fail(-1, "mb_sample_step_requests: pred_out must not alias tokens_in or tokens_out");
-  mb::StepArgs a{};
-  a.logits_c = logits_c; a.logits_u = logits_u;
-  a.seeds = seeds; a.req = (const mb::RequestStep*)table_row;
-  a.tokens = tokens_out; a.pred = pred_out; a.B = B; a.P = step_slots(n, m); a.C = C;
-  return sample_step_checked("mb_sample_step_requests", a, tokens_in, num_regen, 0.f, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// whole loop (sampling.py:55-136)
-// ================================================================================================
-namespace {
-
-// Where a run's noise comes from: the caller's tensors of this chunk's steps (mb_sample, mb_sample_edit), or the samples' seeds (mb_sample_seeded: the
-// step kernel generates it; conf_weight = host [num_steps], indexed by the absolute step like the plan's arrays)
-struct RunNoise {
-  const float* exp_noise = nullptr; const float* conf_noise = nullptr;
-  const int64_t* seeds = nullptr; float rand_temp = 0.f; const float* conf_weight = nullptr;
-};
-// What the three run entries differ in.  mask_len (mb_sample: the run starts all-masked) or mask_ratio (an edit run: the step reads the ratio and the
-// per-sample counts the first chunk left in g->num_regen); init_tokens: the tokens an edit run starts from (mb_sample_seeded: may be null = all-masked,
-// num_regen[b] = n m); noise.seeds != null: a seeded run.
-struct RunSpec {
-  const char* who = nullptr;                           // the entry's name in the messages
-  int num_steps = 0, use_guidance = 0, step_begin = 0, step_end = 0;
-  const float* scale = nullptr; const float* temperature = nullptr;
-  const int* mask_len = nullptr; const float* mask_ratio = nullptr;
-  const int64_t* init_tokens = nullptr;
-  RunNoise noise;
-};
-struct RunOut { int64_t* step_tokens; int64_t* codes; float* img_nchw; uint8_t* img_nhwc_u8; };   // each may be null
-
-const char* const kRunKind[3] = {"plain", "edit", "seeded"};
-const char* const kStepEntry[3] = {"mb_sample_step", "mb_sample_step_edit", "mb_sample_step_seeded"};
-
-// (mb_sample_plan and mb_edit_plan differ in their third array alone)
-template <class Plan>
-RunSpec run_spec(const char* who, const Plan& p) {
-  RunSpec r;
-  r.who = who; r.num_steps = p.num_steps; r.use_guidance = p.use_guidance; r.step_begin = p.step_begin; r.step_end = p.step_end;
-  r.scale = p.scale; r.temperature = p.temperature;
-  return r;
-}
-
-// The null checks of the caller's own pointers are the entries'; g and labels are theirs too.
-int sample_run(mb_gen* g, mb_dec* d, const RunSpec& r, const int64_t* labels, int B, const RunOut& out, hipStream_t s) {
-  const char* who = r.who;
-  const RunNoise& nz = r.noise;
-  const bool edit = r.mask_ratio != nullptr, seeded = nz.seeds != nullptr;
-  const int num_steps = r.num_steps;
-  if (!r.scale || !r.temperature || !(edit ? (const void*)r.mask_ratio : (const void*)r.mask_len) || num_steps <= 0) return fail(-1, "%s: incomplete plan", who);
-  const mb_gen::Run::Id id{B, num_steps, r.use_guidance != 0, seeded ? 2 : edit ? 1 : 0};
-  const int nbf = id.guided ? 2 * B : B;
-  if (B <= 0 || nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
-  if (!d && (out.img_nchw || out.img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
-  const mb_gen_cfg& c = g->c;
-  const int n = c.seq, m = c.splits, C = g->C;
-  const size_t P = (size_t)n * m;
-  // state init (sampling.py:65-71): every position masked; CFG batch = [cond | label-dropped]
-  // A run may be fed in step chunks (plan->step_begin / step_end: the noise of a whole 256-step run at batch 100 is 6.7 GB): chunk [0, e) starts from
-  // the all-masked state, later chunks continue from the token state the engine kept; exp_noise / conf_noise / step_tokens hold THIS chunk's steps.
-  const int s0 = r.step_end > 0 ? r.step_begin : 0, s1 = r.step_end > 0 ? r.step_end : num_steps;
-  if (s0 < 0 || s1 > num_steps || s0 >= s1) return fail(-1, "%s: step chunk [%d, %d) outside [0, %d)", who, s0, s1, num_steps);
-  // A run fed in chunks keeps its token state in the engine: a chunk is accepted only as the exact continuation of the run in progress (same batch,
-  // plan length, guidance flag and kind -- plain, edit or seeded --, beginning where the previous chunk ended).  The handle is not re-entrant while a run is in progress.
-  mb_gen::Run& run = g->run;
-  if (s0 == 0) {
-    if (r.init_tokens) mb::edit_load_tokens(s, r.init_tokens, g->tok_a, g->num_regen, B, (int)P, C);   // the caller's tokens; num_regen[b] = sample b's masked count
-    else {
-      mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
-      if (seeded) mb::edit_load_tokens(s, g->tok_a, nullptr, g->num_regen, B, (int)P, C);          // the per-sample rule from the all-masked state: num_regen[b] = n m
-    }
-    run.id = id;
-  }
-  else if (!(run.id == id && run.next == s0))
-    return fail(-1, "%s: step chunk [%d, %d) of a %d-step %s run with B = %d does not continue the run in progress (next step %d of %d, B = %d, %s %s run)",
-                who, s0, s1, num_steps, kRunKind[id.kind], B, run.next, run.id.steps, run.id.B, run.id.kind == 1 ? "an" : "a", kRunKind[run.id.kind]);
-  run.next = -1;                                       // (set again below when this chunk has been enqueued and more follow)
-  int64_t* cur = (s0 & 1) ? g->tok_b : g->tok_a;
-  int64_t* nxt = (s0 & 1) ? g->tok_a : g->tok_b;
-  int64_t* last_pred = g->pred;
-  // lab_cfg / drop_cfg are marked ready for the steps of this call only: whichever way it returns
-  struct CfgReady { mb_gen::Run& run; ~CfgReady() { run.cfg_labels = nullptr; } } cfg_ready{run};
-  run.cfg_labels = nullptr;
-  mb::StepArgs a{};
-  a.logits_c = g->logits; a.B = B; a.P = (int)P; a.C = C;
-  a.seeds = nz.seeds; a.rand_temp = nz.rand_temp;
-  for (int i = s0; i < s1; ++i) {
-    int rc;
-    // sampling.py:98-99 combines c + s_i (c - u).  Where the annealed scale s_i is exactly 0 -- the first steps of the cosine schedule: (i / N)^p pi
-    // is below float32's cos() resolution -- the unconditional logits do not enter the result (c + 0 (c - u) == c for finite logits), so that
-    // forward is not run: the step is the plain conditional forward, bit for bit what the guided expression evaluates to.
-    // (precision 4: the guided forward is also the MORE PRECISE conditional forward -- its pair tiles carry the activation-lo sets, the plain tiles do not --
-    // and the first, almost fully masked steps are where near-ties flip: the zero-scale steps run it too; its unconditional half is then multiplied by 0)
-    if (id.guided && (r.scale[i] != 0.0f || (!g->f32 && g->pair_ok && c.precision >= 4))) {
-      rc = gen_forward_cfg(g, cur, labels, g->logits, B, s);
-      a.logits_u = g->logits + (size_t)B * P * C;
-      if (B <= g->chunk_seqs / 2) { run.cfg_labels = labels; run.cfg_B = B; }   // lab_cfg / drop_cfg stay valid for the rest of this call
-    } else {
-      rc = gen_forward(g, cur, labels, nullptr, g->logits, B, s);
-      a.logits_u = nullptr;
-    }
-    if (rc) return rc;
-    const size_t k = (size_t)(i - s0);                 // the noise / step_tokens buffers hold this chunk's steps
-    a.scale = r.scale[i]; a.temperature = r.temperature[i];
-    a.tokens = nxt; a.pred = out.step_tokens ? out.step_tokens + k * B * P : g->pred;
-    if (seeded) { a.step = i; a.conf_w = nz.conf_weight[i]; }
-    else { a.exp_noise = nz.exp_noise + k * B * P * C; a.conf_noise = nz.conf_noise + k * B * P; }
-    if (!edit) a.k_mask_len = r.mask_len[i];
-    rc = sample_step_checked(kStepEntry[id.kind], a, cur, edit ? g->num_regen : nullptr, edit ? r.mask_ratio[i] : 0.f, s);
-    if (rc) return rc;
-    last_pred = a.pred;
-    int64_t* t = cur; cur = nxt; nxt = t;
-  }
-  if (s1 < num_steps) {                                // more chunks follow: keep the last predictions only if they are the engine's own buffer
-    if (int rc = launched()) return rc;
-    run.next = s1;
-    return 0;
-  }
-  // combine_factorized_tokens (factorization.py:7-24) on the LAST step's predictions, kept as integers
-  int64_t* codes = out.codes ? out.codes : g->codes;
-  mb::combine_groups(s, last_pred, codes, (size_t)B * n, m, g->gbits);
-  if (d) {
-    int rc = mb_dec_decode(d, codes, out.img_nchw, out.img_nhwc_u8, B, (mb_stream)s);
-    if (rc) return rc;
-  }
-  return launched();
-}
-
-// The fourth kind of run, "requests" (include/maskbit_hip.h "per-sample sampling arguments"): a seeded run whose step t covers the prefix
-// [0, active[t]) of the batch and whose step kernels read their constants per sample from plan.table.  A sibling of sample_run that shares its pieces --
-// the start state, the two forwards, the checked step, combine and decode -- and has none of its step chunks.  Every argument check is in front of the
-// first launch, those that need no handle in front of the handle's own (the entry is refused the same way with or without a device).
-int sample_requests_run(mb_gen* g, mb_dec* d, const mb_request_plan& plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
-                        const RunOut& out, hipStream_t s) {
-  const char* who = "mb_sample_requests";
-  const int S = plan.num_steps;
-  if (!plan.active || !plan.table || !labels || !seeds) return fail(-1, "%s: null argument", who);
-  if (S <= 0 || B <= 0) return fail(-1, "%s: bad sizes (num_steps = %d, B = %d)", who, S, B);
-  for (int t = 0; t < S; ++t) {
-    if (plan.active[t] < 1 || plan.active[t] > B) return fail(-1, "%s: active[%d] = %d outside [1, %d]", who, t, plan.active[t], B);
-    if (t && plan.active[t] < plan.active[t - 1])
-      return fail(-1, "%s: active[] is not non-decreasing (active[%d] = %d after %d): order the requests by num_steps descending", who, t, plan.active[t], plan.active[t - 1]);
-  }
-  if (plan.active[S - 1] != B) return fail(-1, "%s: active[%d] = %d, but all %d requests run the last step", who, S - 1, plan.active[S - 1], B);
-  if (!d && (out.img_nchw || out.img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
-  if (!g) return fail(-1, "%s: null argument (no generator handle)", who);
-  const bool guided = plan.use_guidance != 0;
-  const int nbf = guided ? 2 * B : B;
-  if (nbf > g->max_seqs) return fail(-1, "%s: B=%d needs %d sequences, engine holds %d", who, B, nbf, g->max_seqs);
-  const mb_gen_cfg& c = g->c;
-  const int n = c.seq, m = c.splits, C = g->C;
-  const size_t P = (size_t)n * m;
-  mb_gen::Run& run = g->run;
-  run.next = -1;                                       // ends any run in progress: no chunk of another kind continues this one
-  // The start state in BOTH token buffers: a request that becomes active at step t reads whichever buffer is `cur` then, and nothing has touched its rows
-  if (init_tokens) mb::edit_load_tokens(s, init_tokens, g->tok_a, g->num_regen, B, (int)P, C);
-  else {
-    mb::fill_i64(s, g->tok_a, (int64_t)C, (size_t)B * P);
-    mb::edit_load_tokens(s, g->tok_a, nullptr, g->num_regen, B, (int)P, C);
-  }
-  HIP_TRY(hipMemcpyAsync(g->tok_b, g->tok_a, (size_t)B * P * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-  int64_t* cur = g->tok_a;
-  int64_t* nxt = g->tok_b;
-  int64_t* last_pred = g->pred;
-  struct CfgReady { mb_gen::Run& run; ~CfgReady() { run.cfg_labels = nullptr; } } cfg_ready{run};
-  run.cfg_labels = nullptr;
-  mb::StepArgs a{};
-  a.logits_c = g->logits; a.P = (int)P; a.C = C;
-  a.seeds = seeds;
-  for (int t = 0; t < S; ++t) {
-    const int Bt = plan.active[t];
-    int rc;
-    // The forward is chosen by the run's flag alone, never by the scales of the step: a request with scale 0 gets c + 0 (c - u) from the guided forward
-    if (guided) {
-      rc = gen_forward_cfg(g, cur, labels, g->logits, Bt, s);
-      a.logits_u = g->logits + (size_t)Bt * P * C;
-      if (Bt <= g->chunk_seqs / 2) { run.cfg_labels = labels; run.cfg_B = Bt; }   // valid until the prefix grows: gen_forward_cfg then refreshes lab_cfg / drop_cfg
-      else run.cfg_labels = nullptr;
-    } else {
-      rc = gen_forward(g, cur, labels, nullptr, g->logits, Bt, s);
-      a.logits_u = nullptr;
-    }
-    if (rc) return rc;
-    a.B = Bt;
-    a.req = (const mb::RequestStep*)plan.table + (size_t)t * B;
-    a.tokens = nxt; a.pred = out.step_tokens ? out.step_tokens + (size_t)t * B * P : g->pred;
-    rc = sample_step_checked(who, a, cur, g->num_regen, 0.f, s);
-    if (rc) return rc;
-    last_pred = a.pred;                                // (the last step runs all B requests: its predictions are the whole batch's)
-    int64_t* tmp = cur; cur = nxt; nxt = tmp;
-  }
-  int64_t* codes = out.codes ? out.codes : g->codes;
-  mb::combine_groups(s, last_pred, codes, (size_t)B * n, m, g->gbits);
-  if (d) {
-    int rc = mb_dec_decode(d, codes, out.img_nchw, out.img_nhwc_u8, B, (mb_stream)s);
-    if (rc) return rc;
-  }
-  return launched();
-}
-
-}  // namespace
-
-extern "C" {
-
-int mb_sample_requests(mb_gen* g, mb_dec* d, const mb_request_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
-                       int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!plan) return fail(-1, "mb_sample_requests: null argument");
-  return sample_requests_run(g, d, *plan, labels, B, init_tokens, seeds, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
-}
-
-int mb_sample(mb_gen* g, mb_dec* d, const mb_sample_plan* plan, const int64_t* labels, int B, const float* exp_noise,
-              const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
-              uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!plan || !g || !labels || !exp_noise || !conf_noise) return fail(-1, "mb_sample: null argument");
-  RunSpec r = run_spec("mb_sample", *plan);
-  r.mask_len = plan->mask_len;
-  r.noise.exp_noise = exp_noise; r.noise.conf_noise = conf_noise;
-  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
-}
-
-int mb_sample_edit(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const float* exp_noise,
-                   const float* conf_noise, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw, uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_edit: %s", plan ? "incomplete plan" : "null argument");
-  if (!g || !labels || !exp_noise || !conf_noise || !init_tokens) return fail(-1, "mb_sample_edit: null argument");
-  RunSpec r = run_spec("mb_sample_edit", *plan);
-  r.mask_ratio = plan->mask_ratio;
-  r.init_tokens = init_tokens;
-  r.noise.exp_noise = exp_noise; r.noise.conf_noise = conf_noise;
-  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
-}
-
-int mb_sample_seeded(mb_gen* g, mb_dec* d, const mb_edit_plan* plan, const int64_t* labels, int B, const int64_t* init_tokens, const int64_t* seeds,
-                     float randomize_temperature, const float* conf_weight, int64_t* step_tokens, int64_t* tokens_out, float* img_nchw,
-                     uint8_t* img_nhwc_u8, mb_stream stream) {
-  if (!plan || !plan->mask_ratio) return fail(-1, "mb_sample_seeded: %s", plan ? "incomplete plan" : "null argument");
-  if (!seeds || !conf_weight || !g || !labels) return fail(-1, "mb_sample_seeded: null argument");
-  RunSpec r = run_spec("mb_sample_seeded", *plan);
-  r.mask_ratio = plan->mask_ratio;
-  r.init_tokens = init_tokens;
-  r.noise.seeds = seeds; r.noise.rand_temp = randomize_temperature; r.noise.conf_weight = conf_weight;
-  return sample_run(g, d, r, labels, B, RunOut{step_tokens, tokens_out, img_nchw, img_nhwc_u8}, (hipStream_t)stream);
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// sampling session (include/maskbit_hip.h "sampling session"; kernels: session.hip)
-// ================================================================================================
-// The session object: the device state of max_active rows (allocated by the first admit that passes its checks) and the HOST MIRROR of the rule the
-// kernels apply -- per active row its ticket, local step and N --, from which a tick knows k, the moves and the finished tickets without reading the
-// device.  tok[cur] is the buffer the next tick reads.
-struct mb_session {
-  int n = 0, m = 0, C = 0, gbits = 0, cap = 0, max_steps = 0;
-  bool guided = false, allocated = false;
-  size_t P = 0;
-  struct Row { uint64_t ticket; int local_step, N; };
-  std::vector<Row> rows;                                // [A]
-  uint64_t next_ticket = 0;
-  int64_t* tok[2] = {nullptr, nullptr};
-  int cur = 0;
-  int64_t *pred = nullptr, *codes_all = nullptr, *codes = nullptr;
-  mb::SessionRows st{};
-  mb::RequestStep* row = nullptr;                       // [cap]: the step's table row
-  int* plan = nullptr;                                  // the snapshot of a tick's retire step (mb::session_plan_ints)
-  bool cfg_dirty = true;                                // membership changed since the handle's lab_cfg / drop_cfg were filled from st.label
-  mb::DevArena mem;
-};
-
-namespace {
-
-int session_allocate(mb_session* s) {
-  if (s->allocated) return 0;
-  mb::DevArena& m = s->mem;
-  const size_t cap = (size_t)s->cap;
-  m.get(&s->tok[0], cap * s->P); m.get(&s->tok[1], cap * s->P); m.get(&s->pred, cap * s->P);
-  m.get(&s->codes_all, cap * s->n); m.get(&s->codes, cap * s->n);
-  m.get(&s->st.label, cap); m.get(&s->st.seed, cap);
-  m.get(&s->st.num_regen, cap); m.get(&s->st.slot, cap); m.zeroed(&s->st.local_step, cap); m.zeroed(&s->st.N, cap);
-  m.get(&s->st.pool, cap * s->max_steps);
-  m.get(&s->row, cap); m.get(&s->plan, mb::session_plan_ints(s->cap));
-  if (int rc = m.failed("mb_session_admit")) return rc;
-  std::vector<int> iota(cap);
-  for (size_t r = 0; r < cap; ++r) iota[r] = (int)r;    // every pool slot free: row r would take slot r
-  HIP_TRY(hipMemcpy(s->st.slot, iota.data(), cap * sizeof(int), hipMemcpyHostToDevice));
-  s->st.cap = s->cap; s->st.max_steps = s->max_steps;
-  s->allocated = true;
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mb_session_create(int seq, int splits, int bits, int max_active, int max_steps, int use_guidance, mb_session** out) {
-  if (!out) return fail(-1, "mb_session_create: null argument");
-  if (max_active < 1 || max_steps < 1) return fail(-1, "mb_session_create: bad sizes (max_active = %d, max_steps = %d: both at least 1)", max_active, max_steps);
-  if (seq < 1 || splits < 1 || bits < 1 || bits > 24 || bits % splits || (size_t)seq * splits > 8192 || (1 << (bits / splits)) > 4096)
-    return fail(-1, "mb_session_create: seq = %d, splits = %d, bits = %d is no generator configuration (mb_gen_create)", seq, splits, bits);
-  if ((size_t)max_active * max_steps > ((size_t)1 << 27)) return fail(-1, "mb_session_create: max_active * max_steps = %zu schedule records exceed 2^27", (size_t)max_active * max_steps);
-  mb_session* s = new mb_session();
-  s->n = seq; s->m = splits; s->gbits = bits / splits; s->C = 1 << s->gbits; s->P = (size_t)seq * splits;
-  s->cap = max_active; s->max_steps = max_steps; s->guided = use_guidance != 0;
-  s->rows.reserve(max_active);
-  *out = s;
-  return 0;
-}
-
-void mb_session_destroy(mb_session* s) { delete s; }
-
-int mb_session_active(const mb_session* s) { return s ? (int)s->rows.size() : -1; }
-
-int mb_session_due(const mb_session* s) {
-  if (!s) return -1;
-  int due = 0;
-  for (const mb_session::Row& r : s->rows) due += r.local_step + 1 == r.N;
-  return due;
-}
-
-int mb_session_admit(mb_session* s, int K, const int64_t* labels, const int64_t* seeds, const int* num_steps, const mb_request_step* schedule,
-                     const int64_t* init_tokens, uint64_t* tickets, mb_stream stream) {
-  const char* who = "mb_session_admit";
-  if (K < 1) return fail(-1, "%s: bad sizes (K = %d)", who, K);
-  if (!s || !labels || !seeds || !num_steps || !schedule || !tickets) return fail(-1, "%s: null argument", who);
-  for (int k = 0; k < K; ++k)
-    if (num_steps[k] < 1 || num_steps[k] > s->max_steps) return fail(-1, "%s: num_steps[%d] = %d outside [1, %d]", who, k, num_steps[k], s->max_steps);
-  const int A = (int)s->rows.size();
-  if (K > s->cap - A) return fail(-1, "%s: %d active + %d new requests exceed max_active = %d", who, A, K, s->cap);
-  if (int rc = session_allocate(s)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  // the start state goes into the buffer the next tick reads; the other one is written by that tick's step before anything reads it
-  mb::session_admit(st, s->st, s->tok[s->cur], init_tokens, num_steps, labels, seeds, (const mb::RequestStep*)schedule, A, K, (int)s->P, s->C);
-  for (int k = 0; k < K; ++k) {
-    tickets[k] = s->next_ticket;
-    s->rows.push_back({s->next_ticket++, 0, num_steps[k]});
-  }
-  s->cfg_dirty = true;
-  return launched();
-}
-
-int mb_session_tick(mb_session* s, mb_gen* g, mb_dec* d, int64_t* pred_out, int64_t* codes_out, float* img_nchw, uint8_t* img_nhwc_u8, uint64_t* finished,
-                    uint64_t* ran, int* num_finished, mb_stream stream) {
-  const char* who = "mb_session_tick";
-  if (!s || !num_finished) return fail(-1, "%s: null argument", who);
-  *num_finished = 0;
-  const int A = (int)s->rows.size();
-  if (A == 0) return 0;                                  // an empty session: nothing to run, nothing launched
-  if (!finished && mb_session_due(s) > 0) return fail(-1, "%s: null argument (%d requests finish, no ticket array)", who, mb_session_due(s));
-  if (!d && (img_nchw || img_nhwc_u8)) return fail(-1, "%s: image requested without a decoder", who);
-  if (!g) return fail(-1, "%s: null argument (no generator handle)", who);
-  const mb_gen_cfg& c = g->c;
-  if (c.seq != s->n || c.splits != s->m || g->C != s->C)
-    return fail(-1, "%s: the session was created for %d positions x %d groups of %d codes, the generator has %d x %d of %d", who, s->n, s->m, s->C, c.seq, c.splits, g->C);
-  const int nbf = s->guided ? 2 * A : A;
-  if (nbf > g->max_seqs) return fail(-1, "%s: %d active requests need %d sequences, engine holds %d", who, A, nbf, g->max_seqs);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t P = s->P;
-  mb_gen::Run& run = g->run;
-  run.next = -1;                                         // ends any chunked run in progress, as mb_sample_requests does
-  // 1. the step's table row, gathered on the device
-  mb::session_row_table(st, s->st, s->row, A);
-  // 2. one global step of sample_requests_run over the A rows.  lab_cfg / drop_cfg of the handle stay marked ready ACROSS ticks (nothing else leaves a
-  // mark behind, and gen_forward_cfg drops it when it overwrites them), but never across a change of membership: the label buffer keeps its address
-  int64_t* cur = s->tok[s->cur];
-  int64_t* nxt = s->tok[s->cur ^ 1];
-  if (s->cfg_dirty && run.cfg_labels == s->st.label) run.cfg_labels = nullptr;
-  mb::StepArgs a{};
-  a.logits_c = g->logits; a.B = A; a.P = (int)P; a.C = s->C;
-  a.seeds = s->st.seed; a.req = s->row;
-  int rc;
-  if (s->guided) {
-    rc = gen_forward_cfg(g, cur, s->st.label, g->logits, A, st);
-    a.logits_u = g->logits + (size_t)A * P * s->C;
-    if (A <= g->chunk_seqs / 2) { run.cfg_labels = s->st.label; run.cfg_B = A; }
-    else run.cfg_labels = nullptr;
-    s->cfg_dirty = false;
-  } else {
-    rc = gen_forward(g, cur, s->st.label, nullptr, g->logits, A, st);
-  }
-  if (rc) return rc;
-  int64_t* pred = pred_out ? pred_out : s->pred;
-  a.tokens = nxt; a.pred = pred;
-  rc = sample_step_checked(who, a, cur, s->st.num_regen, 0.f, st);
-  if (rc) return rc;
-  s->cur ^= 1;
-  // 3. retire and compact: the mirror applies the kernels' rule -- F ascending, holes = F below A', movers = the unfinished rows at or above A'
-  std::vector<mb_session::Row>& rows = s->rows;
-  int k = 0;
-  for (int r = 0; r < A; ++r) {
-    if (ran) ran[r] = rows[r].ticket;
-    if (++rows[r].local_step == rows[r].N) finished[k++] = rows[r].ticket;
-  }
-  *num_finished = k;
-  if (k == 0) return launched();
-  const int Ap = A - k;
-  int moves = 0;
-  for (int hole = 0, mover = Ap; hole < Ap; ++hole) {
-    if (rows[hole].local_step != rows[hole].N) continue;
-    while (rows[mover].local_step == rows[mover].N) ++mover;   // (as many unfinished rows at or above A' as finished ones below)
-    rows[hole] = rows[mover++];
-    ++moves;
-  }
-  rows.resize(Ap);
-  s->cfg_dirty = true;
-  if (run.cfg_labels == s->st.label) run.cfg_labels = nullptr;
-  int64_t* codes = codes_out ? codes_out : s->codes;
-  mb::session_retire(st, s->st, s->plan, s->tok[s->cur], pred, s->codes_all, codes, A, s->n, s->m, s->gbits, k, moves);
-  // 4. decode the k finished requests
-  if (d && (img_nchw || img_nhwc_u8)) {
-    rc = mb_dec_decode(d, codes, img_nchw, img_nhwc_u8, k, (mb_stream)st);
-    if (rc) return rc;
-  }
-  return launched();
+  return mb::gen_forward(g, tokens, labels, drop, logits, nb, (hipStream_t)stream, attn);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Internal launcher declarations shared between the kernel translation units, engine.hip and diag.hip.
+// Internal launcher declarations shared between the kernel translation units, engine.hip, sampler.hip and diag.hip.
 #pragma once
 #include "mb_common.h"
 

@@ -1,4 +1,4 @@
-// The device-side bookkeeping of a sampling session (include/maskbit_hip.h "sampling session"; the host side is mb_session_* in engine.hip): the
+// The device-side bookkeeping of a sampling session (include/maskbit_hip.h "sampling session"; the host side is mb_session_* in sampler.hip): the
 // active requests are the dense row prefix [0, A) of the session's buffers, and membership changes at every tick without a host round trip.
 //   session_row_table_kernel -- row[r] = pool[slot[r]][local_step[r]], local_step[r] += 1: the step's table row, gathered from the schedule pool.
 //   session_admit_kernel     -- K new rows at [A, A + K): label, seed, N, local step 0, and the request's N schedule records into the row's pool slot
